@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- LiteralKG aggregation hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
 
 With --gpus N > 1 and no torch.distributed environment the script starts its own N workers (a child
 `python -m torch.distributed.run`, before anything touches the GPU) and passes their JSON line and exit code through;
@@ -17,6 +17,13 @@ A_in holds a real refreshed attention (edge logits + row softmax from the fused 
 Workload at N = 1: synthetic KG 1M entities / 10M edges, D = 256 (the config the metric is quoted on);
 at N > 1 every rank contributes a head-row range of 625k entities / 12.5M edges (N = 8 is BASELINE config[3]:
 5M entities / 100M edges): weak scaling.
+
+A plain N = 1 run sets up, warms up, times the K steps and prints the JSON line.  --full adds what the headline does not
+need: the spot check of 8 output rows against a direct evaluation, the CPU baseline (`cpu_baseline`) and the context
+timings (`extra`: the cache-free 5M / 100M pair, attention refresh, GEMM and gate rooflines, whole pre_training steps).
+--dump-outputs DIR (N = 1) writes what the last timed step computed, the forward `side` and the backward `grad_ego`,
+as float32 DIR/side.npy and DIR/grad_ego.npy: the same seeded sample of rows of each (32 MB in all).  The inputs are
+seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import hashlib
@@ -454,6 +461,18 @@ def spot_rows(g, val, table, rows):
     return torch.cat(out)
 
 
+def dump_outputs(path, arrays, budget=32 << 20, seed=0):
+    """--dump-outputs: the same fixed, seeded rows of every array (as many as fit `budget` bytes in all), float32, one
+    `<name>.npy` per array."""
+    n = min(a.shape[0] for a in arrays.values())
+    k = max(1, min(n, budget // (4 * sum(a.shape[1] for a in arrays.values()))))
+    rows = np.sort(np.random.default_rng(seed).choice(n, size=k, replace=False))
+    idx = torch.from_numpy(rows).to(next(iter(arrays.values())).device)
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a[idx].float().cpu().numpy())
+
+
 class Timer:
     """K timed steps between barrier + device sync on both sides; MAX over ranks."""
 
@@ -525,8 +544,12 @@ def main():
     ap.add_argument("--entities", type=int, default=None, help="per-GPU entities (default 1M at N=1, 625k at N>1)")
     ap.add_argument("--edges", type=int, default=None, help="per-GPU edges (default 10M at N=1, 12.5M at N>1)")
     ap.add_argument("--skew", default="zipf", choices=["zipf", "uniform"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the whole-path context timings (N=1)")
+    ap.add_argument("--full", action="store_true",
+                    help="N=1: also the spot check, the CPU baseline and the whole-path context timings (off: the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="N=1: write the last timed step's outputs (a seeded sample of rows) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the whole-path context timings (N=1)")
     ap.add_argument("--chunks", type=int, default=4, help="rows scheme: tail-row chunks of the backward (comm overlap)")
     ap.add_argument("--sharding", default="both", choices=["both", "features", "rows"],
                     help="N>1: 'features' = column-sharded tables, no collective in the SpMM, all-to-all exchange (the "
@@ -541,6 +564,8 @@ def main():
                     help="debug only: all ranks share cuda:0 and talk over gloo (N>1 code path on a 1-GPU box); "
                          "the numbers of such a run are meaningless")
     args = ap.parse_args()
+    if args.dump_outputs and int(os.environ.get("WORLD_SIZE", args.gpus)) > 1:
+        ap.error("--dump-outputs: N = 1 only")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         raise SystemExit(self_launch(args))
@@ -581,6 +606,7 @@ def main():
     lo, hi = rank * n_loc, (rank + 1) * n_loc
     schemes = ["none"] if world == 1 else (["features", "rows"] if args.sharding == "both" else [args.sharding])
     timer = Timer(world, cdev)
+    check = args.full or world > 1                 # the spot check of 8 output rows (N = 1: --full only)
 
     # every rank draws the triples of ITS head rows (heads inside [lo, hi), tails over all entities)
     t0 = time.perf_counter()
@@ -610,8 +636,9 @@ def main():
         ent = xavier_table(n_glob, d, dev, seed=2022)              # full replica of the source table on every rank
         val, _ = ops.edge_softmax(g_own, ent, relemb, row_lo=lo, row_hi=hi)     # real attention values, own rows
         shard = ShardedAggregation(g_own, val, lo, hi, n_chunks=args.chunks if world > 1 else 1)
-        want = spot_rows(g_own, val, ent, probe)
-        grad_side = torch.randn((hi - lo, d), device=dev)
+        want = spot_rows(g_own, val, ent, probe) if check else None
+        # seeded like every other input (an unseeded draw differs from run to run): runs compare output for output
+        grad_side = torch.randn((hi - lo, d), device=dev, generator=torch.Generator(device=dev).manual_seed(2023 + rank))
         side = torch.empty((hi - lo, d), device=dev)
         grad_table = torch.empty((n_glob, d), device=dev)
 
@@ -626,9 +653,12 @@ def main():
                 ev[2].record()
         for _ in range(max(args.warmup, 1)):
             step()
-        ok = torch.allclose(side[[i - lo for i in probe]], want, rtol=1e-4, atol=1e-6)
+        ok = torch.allclose(side[[i - lo for i in probe]], want, rtol=1e-4, atol=1e-6) if check else True
         elapsed, events = timer.run(step, args.steps, 3)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"side": side, "grad_ego": grad_table})
         ok, total = reduce_flags(ok, g_own.nnz, True)
+        ok = ok if check else None
         fwd = float(np.mean([e[0].elapsed_time(e[1]) for e in events]))
         bwd = float(np.mean([e[1].elapsed_time(e[2]) for e in events]))
         res = {"elapsed": elapsed, "total_entries": total, "valid": ok, "fwd_ms": fwd, "bwd_ms": bwd,
@@ -780,7 +810,8 @@ def main():
                 "exchange": res["exchange"],
                 "skew": args.skew,
                 "host_graph_build_s": round(t_build, 2),
-                "spot_check": "ok" if res["valid"] else "MISMATCH: 8 output rows per rank differ from a direct evaluation",
+                "spot_check": "not run (--full runs it)" if res["valid"] is None else "ok" if res["valid"] else
+                              "MISMATCH: 8 output rows per rank differ from a direct evaluation",
                 "spmm_only_ms_per_step": res.get("spmm_only_ms"),
                 "spmm_only_edges_per_s": (2 * total / res["spmm_only_ms"] * 1e3) if res.get("spmm_only_ms") else None,
             },
@@ -876,9 +907,9 @@ def main():
 
     if rank == 0:
         out = assemble()
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(g_own, results["none"]["val"], n_glob, d, 2022)
-        if world == 1 and not args.no_extra:
+        if world == 1 and args.full and not args.no_extra:
             results.clear()
             torch.cuda.empty_cache()
             c4 = c4_regime_timing(d, dev)          # (first: its 5 GB tables want fresh, unfragmented device memory)

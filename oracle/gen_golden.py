@@ -17,6 +17,7 @@ Fixture families:
   transe_*     a9 TransE loss (model_bce.py) + gradients
   heads_*      f1 fine-tuning loss, calc_score matrix, predict_links
   statedict    key -> shape manifest of the reference's state_dict
+  kg_*         a triple file of the reference's data, the text's sha256 beside it (--only-kg-file)
 """
 import json
 import os
@@ -271,6 +272,16 @@ def loader_sampler_case(name, n, h, t, r, neg_rate, seed):
     save(name, **out)
 
 
+def kg_file_case(name, rel_path):
+    """A triple file of the reference's data, as int32 columns in file order plus the sha256 of its text: the tests write
+    the same bytes back (one "h r t" line per triple) and parse that file."""
+    import hashlib
+    path = os.path.join(REF, rel_path)
+    a = np.loadtxt(path, dtype=np.int64).reshape(-1, 3)
+    save(name, h=a[:, 0].astype(np.int32), r=a[:, 1].astype(np.int32), t=a[:, 2].astype(np.int32),
+         sha256=np.array(hashlib.sha256(open(path, "rb").read()).hexdigest()))
+
+
 def mlp_case(cls, name, args, n, h, t, r, seed, rng, init_mlp):
     """mode='mlp' (model.py:499-519 / model_bce.py:423-436): train-mode forward (BatchNorm batch statistics, running
     buffers updated), BCE backward as main_finetuning_BCE.py does, then an eval-mode forward."""
@@ -328,6 +339,9 @@ def main():
         rng = np.random.default_rng(4242)
         lh, lt, lr = random_graph(rng, 260, 2600, 5, 10)       # (h,r,t) distinct, some (h,t) under two relations
         loader_laplacian_case("laplacian_rand260", 260, lh, lt, lr)
+        return
+    if "--only-kg-file" in sys.argv:
+        kg_file_case("kg_pre_training_train", os.path.join("data", "Test", "pre_training_train.txt"))
         return
     if "--only-trajectory" in sys.argv:
         rng = np.random.default_rng(777)

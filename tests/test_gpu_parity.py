@@ -2083,14 +2083,14 @@ def test_mlp_head_matches_reference_fixture(L, gpu_device, name):
 
 # ----------------------------------------------------------------------------- bench.py output contract
 def test_bench_prints_one_contract_line(gpu_device):
-    """`python bench.py` prints exactly one JSON line with the driver's keys plus `roofline` and `cpu_baseline`
+    """`python bench.py --full` prints exactly one JSON line with the driver's keys plus `roofline` and `cpu_baseline`
     (small graph here; the default run uses the BASELINE shape)."""
     import json
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1",
+    res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--steps", "3", "--warmup", "1",
                           "--entities", "50000", "--edges", "500000"], capture_output=True, text=True, timeout=600,
                          cwd=root)
     assert res.returncode == 0, res.stderr[-2000:]
@@ -2113,6 +2113,35 @@ def test_bench_prints_one_contract_line(gpu_device):
     for key in ("value", "unit", "cores", "kind", "sample"):
         assert key in c, key
     assert c["kind"] in ("port", "reference") and c["value"] > 0
+
+
+def test_bench_plain_run_is_the_headline_and_dumps_its_outputs(gpu_device, tmp_path):
+    """A plain `python bench.py` times the steps it is given and reports them, and nothing else (no spot check, no
+    `cpu_baseline`, no `extra`); `--dump-outputs DIR` writes what the last timed step computed -- the same seeded rows of
+    the forward `side` and the backward `grad_ego`, float32, 64 MB at most -- and a second run writes the same arrays."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    dumps = []
+    for k in range(2):
+        out = tmp_path / f"run{k}"
+        res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "4", "--warmup", "1",
+                              "--entities", "50000", "--edges", "500000", "--dump-outputs", str(out)],
+                             capture_output=True, text=True, timeout=600, cwd=root)
+        assert res.returncode == 0, res.stderr[-2000:]
+        lines = [ln for ln in res.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1, lines
+        j = json.loads(lines[0])
+        assert j["steps"] == 4 and j["warmup"] == 1 and j["ms_per_step"] > 0 and j["dtype"] == "f32"
+        assert abs(j["value"] - j["config"]["edge_aggregations_per_step"] / j["ms_per_step"] * 1e3) < 1e-6 * j["value"]
+        assert "cpu_baseline" not in j and "extra" not in j and j["config"]["spot_check"].startswith("not run")
+        assert sorted(os.listdir(out)) == ["grad_ego.npy", "side.npy"]
+        dumps.append({name: np.load(out / f"{name}.npy") for name in ("side", "grad_ego")})
+    assert sum(a.nbytes for a in dumps[0].values()) <= 64 << 20
+    for name, a in dumps[0].items():
+        assert a.dtype == np.float32 and a.shape == (16384, 256) and np.isfinite(a).all() and np.abs(a).max() > 0
+        np.testing.assert_allclose(dumps[1][name], a, rtol=1e-5, atol=1e-6)
 
 
 @pytest.mark.timeout(600)

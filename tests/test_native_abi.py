@@ -167,10 +167,18 @@ def test_initial_a_in_matches_loader_restatement(native, kind):
         io.initial_a_in(5, np.array([0]), np.array([1]), np.array([0]), "other")
 
 
-REF_KG = "/root/reference/data/Test/pre_training_train.txt"
+@pytest.fixture
+def ref_kg(tmp_path):
+    """The reference's only complete KG file (data/Test/pre_training_train.txt), written back byte for byte from the
+    fixture's columns; the sha256 of the original text pins that."""
+    import hashlib
+    gd = load_golden("kg_pre_training_train")
+    path = tmp_path / "pre_training_train.txt"
+    np.savetxt(path, np.stack([gd["h"], gd["r"], gd["t"]], 1), fmt="%d", delimiter=" ")
+    assert hashlib.sha256(path.read_bytes()).hexdigest() == str(gd["sha256"])
+    return str(path)
 
 
-@pytest.mark.skipif(not os.path.exists(REF_KG), reason="reference mount absent (GPU box): build-container check only")
 def test_triples_file_parsed_and_deduplicated_by_many_threads(native, tmp_path):
     """Files beyond a few MB are parsed over line-aligned byte ranges by several threads and de-duplicated bucket by bucket
     (lkg_triples_read / lkg_triples_dedup): same answer as pandas' drop_duplicates(keep='first') in file order
@@ -203,14 +211,14 @@ def test_triples_file_parsed_and_deduplicated_by_many_threads(native, tmp_path):
         io.load_triples(str(path))
 
 
-def test_ingest_the_reference_kg_file(native):
+def test_ingest_the_reference_kg_file(native, ref_kg):
     """The reference's only complete KG file: parse, drop duplicates and build A_in like its DataLoader
     (dataloader.py:186-190, 449-495), against pandas / the oracle's restatement."""
     import pandas as pd
     from literalkg_amd import io
     from oracle import literalkg_oracle as O
-    h, r, t = io.load_triples(REF_KG)
-    want = pd.read_csv(REF_KG, sep=" ", names=["h", "r", "t"]).drop_duplicates()
+    h, r, t = io.load_triples(ref_kg)
+    want = pd.read_csv(ref_kg, sep=" ", names=["h", "r", "t"]).drop_duplicates()
     assert np.array_equal(np.stack([h, r, t], 1), want.to_numpy())
     assert len(h) == 217463 and len(set(r.tolist())) == 15          # SURVEY.md section 4
     n = int(max(h.max(), t.max())) + 1

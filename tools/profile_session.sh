@@ -14,5 +14,5 @@ timeout -k 10 200 rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum --kernel-trace --outp
 python3 tools/pmc_traffic.py $out/pmc_fetch $out/pmc_write $out/pmc_tcc > $out/pmc_traffic.json || exit 5
 python3 tools/kernel_trace_summary.py $out/stats spmm_csr_kernel 11345828676 > $out/spmm_trace_summary.json || exit 6
 cp $(find $out/stats -name '*kernel_stats.csv' | head -1) $out/kernel_stats.csv
-timeout -k 10 300 python3 bench.py > $out/bench.json 2> $out/bench.err
+timeout -k 10 300 python3 bench.py --full > $out/bench.json 2> $out/bench.err
 cat $out/pmc_traffic.json; head -40 $out/spmm_trace_summary.json; head -c 1500 $out/bench_profiled.json
