@@ -613,6 +613,32 @@ int lkg_linear_act_layernorm_fwd_f32(int64_t m, int32_t n, int32_t n_panels, con
                                      float *save_rstd, float drop_p, uint64_t seed, void *workspace,
                                      int64_t workspace_bytes, void *stream);
 
+/* Filtered link-prediction ranking (lkg_rank.hip; literalkg_amd/ranking.py).  Candidates are the n_cand rows of p (f32,
+ * row stride ldp, k columns); a query row q_i (row stride ldq) scores candidate c as
+ *     s(i, c) = pn[c] - 2 q_i . p_c          (lower is better; pn NULL = 0: dot scoring, s = -2 q.p)
+ * the squared distance ||q_i - p_c||^2 less the row constant ||q_i||^2.  The dot product is the exact-f32 MFMA chain
+ * (v_mfma_f32_16x16x4_f32, a fixed k order); every score below comes from that same arithmetic, bit for bit.
+ *
+ * lkg_rank_sqnorm_f32 : out[c] = ||p_c||^2.
+ * lkg_rank_queries_f32: q[i,:] = p[ids[i],:] + alpha * e[rel[i],:]   (e nullable: a plain gather; rel nullable: row 0).
+ * lkg_rank_prepare_f32: thr[i] = s(i, truth[i]) and, with a filter, better[i] / equal[i] = MINUS the number of filtered
+ *     candidates c != truth[i] with s(i, c) < thr[i] / == thr[i] (else 0).  The filter is a structure of
+ *     lkg_csr_build_device over n_cand rows (rowptr int32[n_cand+1], col, eptr, rel): query i drops every col[e] of
+ *     row filter_row[i] that has a raw edge with relation filter_rel[i].  rowptr NULL = no filter.
+ * lkg_rank_count_f32  : better[i] += #{c != truth[i] : s(i, c) < thr[i]}, equal[i] += #{c != truth[i] : s == thr[i]}
+ *     (int32 atomics, one per row per workgroup; the n_q x n_cand scores are never stored).  After prepare + count,
+ *     better / equal are the filtered counts.  A NaN score counts nowhere.  64-bit addressing throughout.      */
+int lkg_rank_sqnorm_f32(int64_t n, int32_t k, const float *p, int64_t ldp, float *out, void *stream);
+int lkg_rank_queries_f32(int64_t n, int32_t k, const float *p, int64_t ldp, const int64_t *ids, const float *e,
+                         int64_t lde, const int64_t *rel, float alpha, float *q, int64_t ldq, void *stream);
+int lkg_rank_prepare_f32(int64_t n_q, int64_t n_cand, int32_t k, const float *q, int64_t ldq, const float *p,
+                         int64_t ldp, const float *pn, const int64_t *truth, const int64_t *filter_row,
+                         const int64_t *filter_rel, const int32_t *rowptr, const int32_t *col, const int32_t *eptr,
+                         const int32_t *rel, float *thr, int32_t *better, int32_t *equal, void *stream);
+int lkg_rank_count_f32(int64_t n_q, int64_t n_cand, int32_t k, const float *q, int64_t ldq, const float *p,
+                       int64_t ldp, const float *pn, const float *thr, const int64_t *truth, int32_t *better,
+                       int32_t *equal, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,5 +10,6 @@ CPU fallback: importing works anywhere, computing needs the library and a GPU.
 from .gate import Gate, GateMul          # noqa: F401
 from .model import Aggregator, LiteralKG  # noqa: F401
 from .graph import KGStructure           # noqa: F401
+from .ranking import KnownTriples, RankResult, evaluate_ranking   # noqa: F401
 
-__all__ = ["LiteralKG", "Aggregator", "Gate", "GateMul", "KGStructure"]
+__all__ = ["LiteralKG", "Aggregator", "Gate", "GateMul", "KGStructure", "KnownTriples", "RankResult", "evaluate_ranking"]

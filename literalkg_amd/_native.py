@@ -92,6 +92,10 @@ PROTOTYPES = {
     "lkg_bi_mix_fwd_f32": [i64, i32, vp, i64, vp, i64, vp, i64, f32, vp, i64, vp, i64, vp],
     "lkg_bi_mix_bwd_f32": [i64, i32, vp, i64, vp, i64, vp, i64, vp, i64, i32, f32, vp, vp, vp, vp],
     "lkg_adam_step_f32": [i64, vp, vp, vp, vp, f32, f32, f32, f32, f32, i64, vp],
+    "lkg_rank_sqnorm_f32": [i64, i32, vp, i64, vp, vp],
+    "lkg_rank_queries_f32": [i64, i32, vp, i64, vp, vp, i64, vp, f32, vp, i64, vp],
+    "lkg_rank_prepare_f32": [i64, i64, i32, vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+    "lkg_rank_count_f32": [i64, i64, i32, vp, i64, vp, i64, vp, vp, vp, vp, vp, vp],
 }
 _RESTYPE = {"lkg_last_error": C.c_char_p, "lkg_csr_build_device_workspace": C.c_int64,
             "lkg_gemm_tall_workspace": C.c_int64, "lkg_gemm_workspace": C.c_int64,

@@ -684,6 +684,14 @@ class LiteralKG(nn.Module):
         lo, hi = s.min(), s.max()
         return ((s - lo) / (hi - lo) > self.milestone_score).int()
 
+    def rank_triples(self, h, r, t, side: str = "tail", known=None, scoring: Optional[str] = None,
+                     batch_size: Optional[int] = None):
+        """Filtered link-prediction ranks of the triples (h, r, t) on the inference table (literalkg_amd/ranking.py):
+        side 'tail' / 'head' / 'both', scoring 'transr' / 'transe' / 'dot' (default: self.scoring), known a
+        ranking.KnownTriples filter.  Returns a ranking.RankResult (better, equal, rank)."""
+        from .ranking import rank_triples
+        return rank_triples(self, h, r, t, side=side, known=known, scoring=scoring, batch_size=batch_size)
+
     def initialize_MLP(self):
         """The pair-classification head of model.py:499-504 (same module names, so checkpoints interchange)."""
         self.fc1 = nn.Linear(self.scale_gat_dim * 2, 128)

@@ -2122,3 +2122,86 @@ def gather_rows(table: torch.Tensor, ids: torch.Tensor) -> torch.Tensor:
     N.call("lkg_gather_rows_f32", ids.numel(), table.shape[1], N.ptr(table), _ld(table), N.ptr(ids), None, N.ptr(out),
            table.shape[1], _stream())
     return out
+
+
+# ----------------------------------------------------------------------------- filtered ranking (lkg_rank.hip)
+def group_by_key(keys: torch.Tensor, n_keys: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(perm int32[n], seg int32[n_keys + 1]) of lkg_group_by_key_i64: positions of ``keys`` in stable key order and the
+    first position of every key.  The keys must already lie in [0, n_keys) (checked_ids)."""
+    _need_gpu(keys)
+    keys = _i64(keys.reshape(-1))
+    perm = torch.empty(keys.numel(), dtype=torch.int32, device=keys.device)
+    seg = torch.empty(int(n_keys) + 1, dtype=torch.int32, device=keys.device)
+    N.call("lkg_group_by_key_i64", keys.numel(), int(n_keys), N.ptr(keys), N.ptr(perm), N.ptr(seg), None, _stream())
+    return perm, seg
+
+
+def csr_build_device(n: int, rows: torch.Tensor, cols: torch.Tensor, rels: torch.Tensor):
+    """(rowptr, col, eptr, rel) of lkg_csr_build_device over the (row, col, rel) triples: the cols of every row ascending
+    and unique, entry e covering the sorted raw edges eptr[e] .. eptr[e+1] whose relations rel lists."""
+    _need_gpu(rows, cols, rels)
+    rows, cols, rels = _i64(rows), _i64(cols), _i64(rels)
+    e = rows.numel()
+    i32 = dict(dtype=torch.int32, device=rows.device)
+    rowptr, col, eptr = torch.empty(int(n) + 1, **i32), torch.empty(max(e, 1), **i32), torch.empty(e + 1, **i32)
+    rel, order = torch.empty(max(e, 1), **i32), torch.empty(max(e, 1), **i32)
+    counts = torch.empty(2, dtype=torch.int64, device=rows.device)
+    ws_bytes = N.load().lkg_csr_build_device_workspace(int(n), e)
+    ws = torch.empty(max(int(ws_bytes), 1), dtype=torch.uint8, device=rows.device)
+    N.call("lkg_csr_build_device", int(n), e, N.ptr(rows), N.ptr(cols), N.ptr(rels), N.ptr(rowptr), N.ptr(col),
+           N.ptr(eptr), N.ptr(rel), N.ptr(order), N.ptr(counts), N.ptr(ws), int(ws_bytes), _stream())
+    nnz, n_bad = (int(x) for x in counts.tolist())
+    if n_bad:
+        raise IndexError(f"{n_bad} triple(s) with an entity id outside [0, {n}) or a relation id outside int32")
+    return rowptr, col[:max(nnz, 1)], eptr[:nnz + 1], rel
+
+
+def rank_sqnorm(p: torch.Tensor) -> torch.Tensor:
+    """||p_c||^2 per row (lkg_rank_sqnorm_f32)."""
+    _need_gpu(p)
+    p = _f32_rows(p)
+    out = torch.empty(p.shape[0], dtype=torch.float32, device=p.device)
+    N.call("lkg_rank_sqnorm_f32", p.shape[0], p.shape[1], N.ptr(p), _ld(p), N.ptr(out), _stream())
+    return out
+
+
+def rank_queries(p: torch.Tensor, ids: torch.Tensor, e: Optional[torch.Tensor] = None, rel: Optional[torch.Tensor] = None,
+                 alpha: float = 1.0) -> torch.Tensor:
+    """q[i] = p[ids[i]] + alpha * e[rel[i]] (e None: a plain row gather) -- lkg_rank_queries_f32.  Ids in range."""
+    _need_gpu(p, ids, e, rel)
+    p, ids = _f32_rows(p), _i64(ids.reshape(-1))
+    e = _f32_rows(e) if e is not None else None
+    rel = _i64(rel.reshape(-1)) if rel is not None else None
+    q = torch.empty((ids.numel(), p.shape[1]), dtype=torch.float32, device=p.device)
+    N.call("lkg_rank_queries_f32", ids.numel(), p.shape[1], N.ptr(p), _ld(p), N.ptr(ids), N.ptr(e),
+           _ld(e) if e is not None else 0, N.ptr(rel), float(alpha), N.ptr(q), p.shape[1], _stream())
+    return q
+
+
+def rank_count(q: torch.Tensor, p: torch.Tensor, pn: Optional[torch.Tensor], truth: torch.Tensor,
+               filt=None, filter_row: Optional[torch.Tensor] = None, filter_rel: Optional[torch.Tensor] = None):
+    """(better, equal, thr) int32 / int32 / f32 per query row of q against every row of p: lkg_rank_prepare_f32 (the
+    truth's score, minus the filtered candidates it would count) then lkg_rank_count_f32.  filt = (rowptr, col, eptr, rel)
+    of csr_build_device over p's rows; query i drops the cols of row filter_row[i] under relation filter_rel[i]."""
+    _need_gpu(q, p, pn, truth)
+    q, p, truth = _f32_rows(q), _f32_rows(p), _i64(truth.reshape(-1))
+    n_q, k = q.shape
+    if p.shape[1] != k or truth.numel() != n_q or (pn is not None and pn.numel() != p.shape[0]):
+        raise ValueError(f"rank_count: queries {tuple(q.shape)}, candidates {tuple(p.shape)}, {truth.numel()} truths")
+    dev = q.device
+    better = torch.empty(n_q, dtype=torch.int32, device=dev)
+    equal = torch.empty(n_q, dtype=torch.int32, device=dev)
+    thr = torch.empty(n_q, dtype=torch.float32, device=dev)
+    if filt is not None:
+        rowptr, col, eptr, rel = filt
+        if rowptr.numel() != p.shape[0] + 1:
+            raise ValueError(f"rank_count: the filter covers {rowptr.numel() - 1} rows, the candidates {p.shape[0]}")
+        filter_row, filter_rel = _i64(filter_row.reshape(-1)), _i64(filter_rel.reshape(-1))
+        fargs = [N.ptr(filter_row), N.ptr(filter_rel), N.ptr(rowptr), N.ptr(col), N.ptr(eptr), N.ptr(rel)]
+    else:
+        fargs = [None] * 6
+    N.call("lkg_rank_prepare_f32", n_q, p.shape[0], k, N.ptr(q), _ld(q), N.ptr(p), _ld(p), N.ptr(pn), N.ptr(truth),
+           *fargs, N.ptr(thr), N.ptr(better), N.ptr(equal), _stream())
+    N.call("lkg_rank_count_f32", n_q, p.shape[0], k, N.ptr(q), _ld(q), N.ptr(p), _ld(p), N.ptr(pn), N.ptr(thr),
+           N.ptr(truth), N.ptr(better), N.ptr(equal), _stream())
+    return better, equal, thr

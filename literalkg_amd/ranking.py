@@ -1,0 +1,207 @@
+"""Filtered link-prediction ranking: MR, MRR and Hits@k of held-out triples under the model's own scoring function.
+
+For a test triple (h, r, t) the tail side ranks the truth t among all N entities as the tail of (h, r, .), the head side
+ranks h among all N as the head of (., r, t).  Lower distance is better ('transr': ||T_h W_r + e_r - T_c W_r||^2,
+'transe': ||T_h + e_r - T_c||^2); for 'dot' (T_h . T_c, the calc_score head) higher is better.  A candidate other than
+the truth that forms a ``known`` triple is dropped (the filtered setting); the truth is never compared with itself.
+``better`` counts the kept candidates strictly better than the truth, ``equal`` the ties, and
+rank = 1 + better + equal / 2 (ties share the mean of their positions; optimistic and pessimistic ranks follow from the two
+counts).  A NaN score is neither better nor equal.
+
+Every score is computed on the device by lkg_rank.hip: a GEMM whose output is never stored (its epilogue compares each
+score with the truth's and counts), the truth's score and the filtered candidates' scores from the same exact-f32 MFMA
+arithmetic, so a candidate whose table row equals the truth's ties exactly.  TransR projects the
+table once per relation present in the queries (the tall GEMM), and that projection serves both sides.
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass
+from typing import Dict, Optional, Sequence
+
+import torch
+
+from . import ops
+
+SIDES = ("tail", "head", "both")
+SCORINGS = ("transr", "transe", "dot")
+
+
+def _check_side(side: str) -> str:
+    if side not in SIDES:
+        raise ValueError(f"side must be one of {SIDES}, got {side!r}")
+    return side
+
+
+def _check_scoring(scoring: str) -> str:
+    if scoring not in SCORINGS:
+        raise ValueError(f"scoring must be one of {SCORINGS}, got {scoring!r}")
+    return scoring
+
+
+def _check_ks(ks: Sequence[int]) -> tuple:
+    ks = tuple(ks)
+    for k in ks:
+        if isinstance(k, bool) or int(k) != k or k <= 0:
+            raise ValueError(f"Hits@k needs positive integers k, got {k!r}")
+    return tuple(int(k) for k in ks)
+
+
+def _check_triples(h, r, t):
+    for name, x in (("h", h), ("r", r), ("t", t)):
+        if not isinstance(x, torch.Tensor) or x.dim() != 1:
+            raise ValueError(f"{name} must be a 1-D tensor of ids")
+    if not h.numel() == r.numel() == t.numel():
+        raise ValueError(f"h, r, t have different lengths ({h.numel()}, {r.numel()}, {t.numel()})")
+
+
+class KnownTriples:
+    """The filter: every (h, r, t) of the splits the caller wants to filter by, held on the device as two structures of
+    lkg_csr_build_device -- rows = heads with their tails (the tail side drops the tails of (h, r, .)) and rows = tails with
+    their heads (the head side) -- each entry listing the relations under which the pair is known.  Memory
+    O(N + |known|); duplicates are merged."""
+
+    def __init__(self, h: torch.Tensor, r: torch.Tensor, t: torch.Tensor, n_entities: int, n_relations: int):
+        _check_triples(h, r, t)
+        self.n_entities, self.n_relations = int(n_entities), int(n_relations)
+        for ids, n, what in ((h, self.n_entities, "entity"), (t, self.n_entities, "entity"),
+                             (r, self.n_relations, "relation")):
+            bad = ops.count_ids_outside(n, ids)
+            if bad:
+                raise IndexError(f"KnownTriples: {bad} {what} id(s) outside [0, {n})")
+        self.n_triples = h.numel()
+        self.device = h.device
+        self.by_head = ops.csr_build_device(self.n_entities, h, t, r)     # tail side
+        self.by_tail = ops.csr_build_device(self.n_entities, t, h, r)     # head side
+
+    def for_side(self, side: str):
+        return self.by_head if side == "tail" else self.by_tail
+
+
+@dataclass
+class RankResult:
+    """Per query: ``better`` / ``equal`` (int64) and ``rank`` = 1 + better + equal / 2 (float64).  For side='both' the
+    tensors are 2 x B: row 0 the tail side, row 1 the head side."""
+    better: torch.Tensor
+    equal: torch.Tensor
+    rank: torch.Tensor
+    side: str
+
+
+def realistic_rank(better: torch.Tensor, equal: torch.Tensor) -> torch.Tensor:
+    return 1.0 + better.double() + 0.5 * equal.double()
+
+
+def metrics_from_counts(better: torch.Tensor, equal: torch.Tensor, ks: Sequence[int] = (1, 3, 10)) -> Dict[str, float]:
+    """{'mr', 'mrr', 'hits@k'..., 'n'} of the ranks 1 + better + equal / 2 (all zero for an empty set, 'n' = 0)."""
+    ks = _check_ks(ks)
+    rank = realistic_rank(torch.as_tensor(better).reshape(-1), torch.as_tensor(equal).reshape(-1))
+    n = rank.numel()
+    out = {"n": n}
+    if n == 0:
+        out.update({"mr": 0.0, "mrr": 0.0}, **{f"hits@{k}": 0.0 for k in ks})
+        return out
+    out["mr"] = float(rank.mean())
+    out["mrr"] = float((1.0 / rank).mean())
+    for k in ks:
+        out[f"hits@{k}"] = float((rank <= k).double().mean())
+    return out
+
+
+def _count_group(model, scoring, side, p, pn, pos, h, r, t, known, batch_size, better, equal):
+    """better / equal of one side for the queries at positions pos, against the candidate rows p (squared norms pn)."""
+    q_ids, truth = (h, t) if side == "tail" else (t, h)
+    alpha = 1.0 if side == "tail" else -1.0              # q = T_h W_r + e_r  /  q = T_t W_r - e_r
+    filt = known.for_side(side) if known is not None else None
+    ids, tru, rel = q_ids[pos], truth[pos], r[pos]
+    q = ops.rank_queries(p, ids, None if scoring == "dot" else model.relation_embed.weight.detach(), rel, alpha)
+    step = pos.numel() if batch_size is None else int(batch_size)
+    for lo in range(0, pos.numel(), step):
+        hi = min(lo + step, pos.numel())
+        bb, ee, _ = ops.rank_count(q[lo:hi], p, pn, tru[lo:hi], filt, ids[lo:hi], rel[lo:hi])
+        better[pos[lo:hi]] = bb
+        equal[pos[lo:hi]] = ee
+
+
+def rank_triples(model, h: torch.Tensor, r: torch.Tensor, t: torch.Tensor, side: str = "tail",
+                 known: Optional[KnownTriples] = None, scoring: Optional[str] = None,
+                 batch_size: Optional[int] = None) -> RankResult:
+    """Filtered ranks of the triples (h, r, t) on the model's inference table (see the module docstring).  The model's
+    mode is left as it is (evaluate_ranking switches to eval); nothing of the model is changed."""
+    side = _check_side(side)
+    scoring = _check_scoring(scoring if scoring is not None else model.scoring)
+    _check_triples(h, r, t)
+    if batch_size is not None and (int(batch_size) != batch_size or batch_size <= 0):
+        raise ValueError(f"batch_size must be a positive integer, got {batch_size!r}")
+    if scoring == "transr" and getattr(model, "gat_trans_M", None) is None:
+        raise ValueError("scoring='transr' needs a model with gat_trans_M (built with scoring='transr')")
+    if known is not None and known.n_entities != model.n_entities:
+        raise ValueError(f"known triples over {known.n_entities} entities, the model has {model.n_entities}")
+    sides = ("tail", "head") if side == "both" else (side,)
+    dev = model.entity_embed.weight.device
+    b = h.numel()
+    if b == 0:
+        z = torch.zeros((len(sides), 0) if side == "both" else (0,), dtype=torch.int64, device=dev)
+        return RankResult(z, z.clone(), z.double(), side)
+    h, t = ops.checked_ids(model.n_entities, h.to(dev), t.to(dev))
+    (r,) = ops.checked_ids(model.n_relations, r.to(dev), what="relation")
+    ops.check_deferred_errors()
+    if known is not None and known.device != dev:
+        raise ValueError(f"known triples live on {known.device}, the model on {dev}")
+    model.device = dev                   # (as forward(..., device=) records it: the literal tables follow it)
+    with torch.no_grad():
+        table = model._table_for_inference().detach()
+        c = table.shape[1]
+        if scoring == "transe" and c != model.relation_dim:
+            raise ValueError(f"scoring='transe' needs the table width ({c}) to equal relation_dim ({model.relation_dim})")
+        if scoring == "transr":
+            w = model.gat_trans_M.detach()
+            if w.shape[1] != c:
+                raise ValueError(f"gat_trans_M is {tuple(w.shape)} for a table of width {c}")
+            perm, seg = ops.group_by_key(r, model.n_relations)
+            perm, seg = perm.long(), seg.tolist()
+            rowmax = ops.row_absmax(table)
+
+            def groups():      # one projection P_r = T W_r per relation present, alive while both sides use it
+                for rr in range(model.n_relations):
+                    if seg[rr + 1] > seg[rr]:
+                        p = ops.gemm_tall([table], [[w[rr]]], trans_b=False, rowmax=rowmax)
+                        yield p, ops.rank_sqnorm(p), perm[seg[rr]:seg[rr + 1]]
+        else:
+            def groups():
+                yield table, (ops.rank_sqnorm(table) if scoring == "transe" else None), torch.arange(b, device=dev)
+
+        better = torch.empty((len(sides), b), dtype=torch.int32, device=dev)
+        equal = torch.empty((len(sides), b), dtype=torch.int32, device=dev)
+        for p, pn, pos in groups():
+            for j, s_ in enumerate(sides):
+                _count_group(model, scoring, s_, p, pn, pos, h, r, t, known, batch_size, better[j], equal[j])
+            del p, pn
+    better, equal = better.long(), equal.long()
+    if side != "both":
+        better, equal = better[0], equal[0]
+    return RankResult(better, equal, realistic_rank(better, equal), side)
+
+
+def evaluate_ranking(model, h: torch.Tensor, r: torch.Tensor, t: torch.Tensor, known: Optional[KnownTriples] = None,
+                     ks: Sequence[int] = (1, 3, 10), side: str = "both", scoring: Optional[str] = None,
+                     batch_size: Optional[int] = None) -> Dict:
+    """{'mr', 'mrr', 'hits@k'..., 'n', 'tail': {...}, 'head': {...}}: filtered ranking metrics of the triples; the top
+    level is over every rank computed (2B for side='both').  Runs in eval mode, as the reference's evaluate does, and
+    restores the model's previous mode."""
+    ks = _check_ks(ks)
+    side = _check_side(side)
+    _check_scoring(scoring if scoring is not None else model.scoring)
+    was_training = model.training
+    model.eval()
+    try:
+        res = rank_triples(model, h, r, t, side=side, known=known, scoring=scoring, batch_size=batch_size)
+    finally:
+        model.train(was_training)
+    better, equal = res.better.cpu(), res.equal.cpu()
+    out = metrics_from_counts(better, equal, ks)
+    if side == "both":
+        out["tail"] = metrics_from_counts(better[0], equal[0], ks)
+        out["head"] = metrics_from_counts(better[1], equal[1], ks)
+    else:
+        out[side] = metrics_from_counts(better, equal, ks)
+    return out
