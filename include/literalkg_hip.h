@@ -639,6 +639,30 @@ int lkg_rank_count_f32(int64_t n_q, int64_t n_cand, int32_t k, const float *q, i
                        int64_t ldp, const float *pn, const float *thr, const int64_t *truth, int32_t *better,
                        int32_t *equal, void *stream);
 
+/* Filtered top-k link prediction (lkg_topk.hip; literalkg_amd/topk.py).  Queries, candidates and the score s(i, c) as
+ * for lkg_rank_* above, with the same arithmetic bit for bit.  For every query i the top_k candidates of smallest
+ * (s(i, c), id(c)) -- float comparison, then the entity id id(c) = cand_ids[c] (cand_ids NULL: c), NaN never selected --
+ * among those not dropped by the filter: query i drops every candidate whose id is a col of row filter_row[i] of the
+ * lkg_csr_build_device structure (rowptr, col, eptr, rel) with a raw edge of relation filter_rel[i] (filter_rel[i] < 0:
+ * of any relation).  rowptr NULL = no filter.  The n_q x n_cand scores are never stored.
+ *
+ * lkg_topk_splits    : the number S of candidate splits for n_q queries (requested in [1, LKG_TOPK_MAX_SPLITS], or 0 =
+ *     automatic), clamped to the candidate tiles; 0 for bad arguments.  The result does not depend on S.
+ * lkg_topk_select_f32: per split, each query's best top_k of that split's candidates, sorted, padded with
+ *     (+inf, INT32_MAX), into ws_s / ws_i [S][n_q][top_k] (splits = lkg_topk_splits(n_q, n_cand, splits)).
+ * lkg_topk_merge_f32 : out_ids[i, j] / out_scores[i, j] = the j-th best id / s over the S lists; out_values[i, j] =
+ *     qn[i] + s (qn non-NULL: the squared distance, qn = ||q_i||^2) or -s / 2 (the dot product).  Fewer than top_k
+ *     eligible candidates: ids -1, scores and values NaN past them.  top_k in [1, LKG_TOPK_MAX].                */
+#define LKG_TOPK_MAX 128
+#define LKG_TOPK_MAX_SPLITS 64
+int32_t lkg_topk_splits(int64_t n_q, int64_t n_cand, int32_t requested);
+int lkg_topk_select_f32(int64_t n_q, int64_t n_cand, int32_t k, const float *q, int64_t ldq, const float *p,
+                        int64_t ldp, const float *pn, const int64_t *cand_ids, const int64_t *filter_row,
+                        const int64_t *filter_rel, const int32_t *rowptr, const int32_t *col, const int32_t *eptr,
+                        const int32_t *rel, int32_t top_k, int32_t splits, float *ws_s, int32_t *ws_i, void *stream);
+int lkg_topk_merge_f32(int64_t n_q, int32_t top_k, int32_t splits, const float *ws_s, const int32_t *ws_i,
+                       const float *qn, int64_t *out_ids, float *out_scores, float *out_values, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -96,6 +96,9 @@ PROTOTYPES = {
     "lkg_rank_queries_f32": [i64, i32, vp, i64, vp, vp, i64, vp, f32, vp, i64, vp],
     "lkg_rank_prepare_f32": [i64, i64, i32, vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
     "lkg_rank_count_f32": [i64, i64, i32, vp, i64, vp, i64, vp, vp, vp, vp, vp, vp],
+    "lkg_topk_splits": [i64, i64, i32],
+    "lkg_topk_select_f32": [i64, i64, i32, vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp],
+    "lkg_topk_merge_f32": [i64, i32, i32, vp, vp, vp, vp, vp, vp, vp],
 }
 _RESTYPE = {"lkg_last_error": C.c_char_p, "lkg_csr_build_device_workspace": C.c_int64,
             "lkg_gemm_tall_workspace": C.c_int64, "lkg_gemm_workspace": C.c_int64,

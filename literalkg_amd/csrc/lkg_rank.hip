@@ -8,46 +8,20 @@
 // score (the threshold) and the scores of filtered candidates come from rank_pair_scores below, which feeds the same
 // lane -> k map as the counting kernel.  A candidate whose row is bit-identical to the truth's ties exactly.
 //
-// k order (both kernels, load4 / mfma_chunk): k is taken in chunks of 16; lane l holds elements 4(l>>4) .. 4(l>>4)+3 of
-// the chunk for row l & 15; MFMA j of the chunk feeds element j, so the chain runs 0,4,8,12, 1,5,9,13, ... of each chunk.
-// Elements past k are zero (x + 0 * 0 = x).
+// k order (both kernels, load4 / mfma_chunk of lkg_rank_common.h, shared with lkg_topk.hip): k is taken in chunks of 16;
+// lane l holds elements 4(l>>4) .. 4(l>>4)+3 of the chunk for row l & 15; MFMA j of the chunk feeds element j.
 //
 // Counting: 256-thread workgroups over a 64-query x 256-candidate tile (4 waves, 64 x 64 each = 4 x 4 MFMA tiles);
 // operands come straight from global memory (the 4 waves share the query tile through L1, consecutive workgroups share
 // the candidate block through L2).  Per-row counts reduce in registers, across the 16 lanes of a row, across the waves
 // in LDS, and leave with one atomic per row per workgroup.  The B x N scores are never stored.
-#include "lkg_common.h"
+#include "lkg_rank_common.h"
 
 namespace {
 
 constexpr int RK_THREADS = 256;
 constexpr int RK_ROWS = 64;          // queries per workgroup
 constexpr int RK_COLS = 256;         // candidates per workgroup (64 per wave)
-
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-
-template <bool VEC>
-__device__ __forceinline__ float4 load4(const float *__restrict__ row, int kk, int k) {
-    if (VEC && kk + 4 <= k) return *reinterpret_cast<const float4 *>(row + kk);
-    float4 v;
-    v.x = kk < k ? row[kk] : 0.f;
-    v.y = kk + 1 < k ? row[kk + 1] : 0.f;
-    v.z = kk + 2 < k ? row[kk + 2] : 0.f;
-    v.w = kk + 3 < k ? row[kk + 3] : 0.f;
-    return v;
-}
-
-__device__ __forceinline__ void mfma_chunk(f32x4 &acc, const float4 &a, const float4 &b) {
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, b.x, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, b.y, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, b.z, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, b.w, acc, 0, 0, 0);
-}
-
-// the score both kernels derive from a dot product (one rounding)
-__device__ __forceinline__ float rank_score(float dot, const float *__restrict__ pn, long c) {
-    return __builtin_fmaf(-2.f, dot, pn ? pn[c] : 0.f);
-}
 
 template <bool VEC>
 __global__ __launch_bounds__(RK_THREADS) void rank_count_kernel(long n_q, long n_c, int k, const float *__restrict__ q,

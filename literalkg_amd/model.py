@@ -692,6 +692,16 @@ class LiteralKG(nn.Module):
         from .ranking import rank_triples
         return rank_triples(self, h, r, t, side=side, known=known, scoring=scoring, batch_size=batch_size)
 
+    def predict_topk(self, ids, r=None, side: str = "tail", k: int = 10, known=None, scoring: Optional[str] = None,
+                     candidates=None, batch_size: Optional[int] = None, splits: int = 0):
+        """The k best tails of (ids, r, ?) (side 'tail') or heads of (?, r, ids) (side 'head') on the inference table,
+        known triples dropped (literalkg_amd/topk.py): scoring 'transr' / 'transe' / 'dot' (default: self.scoring),
+        known a ranking.KnownTriples filter, candidates an optional subset of entity ids.  Returns a topk.TopKResult
+        (ids, scores, side)."""
+        from .topk import predict_topk
+        return predict_topk(self, ids, r, side=side, k=k, known=known, scoring=scoring, candidates=candidates,
+                            batch_size=batch_size, splits=splits)
+
     def initialize_MLP(self):
         """The pair-classification head of model.py:499-504 (same module names, so checkpoints interchange)."""
         self.fc1 = nn.Linear(self.scale_gat_dim * 2, 128)

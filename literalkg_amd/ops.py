@@ -2205,3 +2205,64 @@ def rank_count(q: torch.Tensor, p: torch.Tensor, pn: Optional[torch.Tensor], tru
     N.call("lkg_rank_count_f32", n_q, p.shape[0], k, N.ptr(q), _ld(q), N.ptr(p), _ld(p), N.ptr(pn), N.ptr(thr),
            N.ptr(truth), N.ptr(better), N.ptr(equal), _stream())
     return better, equal, thr
+
+
+# ----------------------------------------------------------------------------- filtered top-k (lkg_topk.hip)
+TOPK_MAX = 128
+TOPK_MAX_SPLITS = 64
+TOPK_WORKSPACE_BYTES = 256 << 20
+
+
+def topk_select(q: torch.Tensor, p: torch.Tensor, pn: Optional[torch.Tensor], k: int, filt=None,
+                filter_row: Optional[torch.Tensor] = None, filter_rel: Optional[torch.Tensor] = None,
+                cand_ids: Optional[torch.Tensor] = None, splits: int = 0):
+    """(ids int64, scores f32, values f32), each n_q x k: per query row of q the k candidate rows of p with the smallest
+    s = pn[c] - 2 q.p_c (pn None: dot scoring, s = -2 q.p), ties by the smaller id, NaN never selected -- the score
+    lkg_rank_count_f32 compares, bit for bit.  ids are cand_ids[c] (None: c); values are ||q||^2 + s (pn given) or
+    -s / 2 (dot).  filt = (rowptr, col, eptr, rel) of csr_build_device over entity ids; query i drops the cols of row
+    filter_row[i] under relation filter_rel[i] (-1: under any).  Fewer than k eligible: ids -1, scores / values NaN.
+    splits: candidate splits per launch (0 = automatic, at most TOPK_MAX_SPLITS); the result does not depend on it.
+    The queries run in launches whose workspace (S x rows x k x 8 bytes) stays within TOPK_WORKSPACE_BYTES."""
+    _need_gpu(q, p, pn, cand_ids, filter_row, filter_rel)
+    k, splits = int(k), int(splits)
+    if not 1 <= k <= TOPK_MAX:
+        raise ValueError(f"topk_select: k must lie in [1, {TOPK_MAX}], got {k}")
+    if not 0 <= splits <= TOPK_MAX_SPLITS:
+        raise ValueError(f"topk_select: splits must lie in [0, {TOPK_MAX_SPLITS}], got {splits}")
+    q, p = _f32_rows(q), _f32_rows(p)
+    n_q, kd = q.shape
+    n_c = p.shape[0]
+    if p.shape[1] != kd or (pn is not None and pn.numel() != n_c) or (cand_ids is not None and cand_ids.numel() != n_c):
+        raise ValueError(f"topk_select: queries {tuple(q.shape)}, candidates {tuple(p.shape)}")
+    dev = q.device
+    ids = torch.full((n_q, k), -1, dtype=torch.int64, device=dev)
+    scores = torch.full((n_q, k), float("nan"), dtype=torch.float32, device=dev)
+    values = torch.full((n_q, k), float("nan"), dtype=torch.float32, device=dev)
+    if n_q == 0 or n_c == 0:
+        return ids, scores, values
+    qn = rank_sqnorm(q) if pn is not None else None
+    cand_ids = _i64(cand_ids.reshape(-1)) if cand_ids is not None else None
+    if filt is not None:
+        rowptr, col, eptr, rel = filt
+        filter_row = _i64(filter_row.reshape(-1))
+        filter_rel = _i64(filter_rel.reshape(-1))
+        if filter_row.numel() != n_q or filter_rel.numel() != n_q:
+            raise ValueError(f"topk_select: {filter_row.numel()} filter rows for {n_q} queries")
+    lib = N.load()
+    step = max(64, TOPK_WORKSPACE_BYTES // (TOPK_MAX_SPLITS * k * 8) // 64 * 64)     # rows per launch (worst-case S)
+    for lo in range(0, n_q, step):
+        hi = min(n_q, lo + step)
+        m = hi - lo
+        s_ = int(lib.lkg_topk_splits(m, n_c, splits))
+        ws_s = torch.empty(s_ * m * k, dtype=torch.float32, device=dev)
+        ws_i = torch.empty(s_ * m * k, dtype=torch.int32, device=dev)
+        qq = q[lo:hi]
+        fargs = [None] * 6
+        if filt is not None:
+            fargs = [N.ptr(filter_row[lo:hi]), N.ptr(filter_rel[lo:hi]), N.ptr(rowptr), N.ptr(col), N.ptr(eptr),
+                     N.ptr(rel)]
+        N.call("lkg_topk_select_f32", m, n_c, kd, N.ptr(qq), _ld(qq), N.ptr(p), _ld(p), N.ptr(pn), N.ptr(cand_ids),
+               *fargs, k, s_, N.ptr(ws_s), N.ptr(ws_i), _stream())
+        N.call("lkg_topk_merge_f32", m, k, s_, N.ptr(ws_s), N.ptr(ws_i), N.ptr(qn[lo:hi]) if qn is not None else None,
+               N.ptr(ids[lo:hi]), N.ptr(scores[lo:hi]), N.ptr(values[lo:hi]), _stream())
+    return ids, scores, values

@@ -122,6 +122,37 @@ def _count_group(model, scoring, side, p, pn, pos, h, r, t, known, batch_size, b
         equal[pos[lo:hi]] = ee
 
 
+def scoring_groups(model, scoring: str, table: torch.Tensor, r: Optional[torch.Tensor], b: Optional[int] = None):
+    """Check the table's width against the scoring and return a generator of (p, pn, pos): the candidate rows, their
+    squared norms (None for dot) and the positions of the queries they serve.  TransR: one projection P_r = T W_r per
+    relation present in r (the tall GEMM, one rowmax for all), each alive while the caller uses it; otherwise the table
+    itself, serving all b = len(r) queries (r may be None then).  Shared by ranking and top-k (topk.py), so both score
+    with the same P_r, bit for bit."""
+    c = table.shape[1]
+    dev = table.device
+    if scoring == "transe" and c != model.relation_dim:
+        raise ValueError(f"scoring='transe' needs the table width ({c}) to equal relation_dim ({model.relation_dim})")
+    if scoring == "transr":
+        w = model.gat_trans_M.detach()
+        if w.shape[1] != c:
+            raise ValueError(f"gat_trans_M is {tuple(w.shape)} for a table of width {c}")
+        perm, seg = ops.group_by_key(r, model.n_relations)
+        perm, seg = perm.long(), seg.tolist()
+        rowmax = ops.row_absmax(table)
+
+        def groups():
+            for rr in range(model.n_relations):
+                if seg[rr + 1] > seg[rr]:
+                    p = ops.gemm_tall([table], [[w[rr]]], trans_b=False, rowmax=rowmax)
+                    yield p, ops.rank_sqnorm(p), perm[seg[rr]:seg[rr + 1]]
+    else:
+        n = r.numel() if b is None else int(b)
+
+        def groups():
+            yield table, (ops.rank_sqnorm(table) if scoring == "transe" else None), torch.arange(n, device=dev)
+    return groups()
+
+
 def rank_triples(model, h: torch.Tensor, r: torch.Tensor, t: torch.Tensor, side: str = "tail",
                  known: Optional[KnownTriples] = None, scoring: Optional[str] = None,
                  batch_size: Optional[int] = None) -> RankResult:
@@ -150,29 +181,10 @@ def rank_triples(model, h: torch.Tensor, r: torch.Tensor, t: torch.Tensor, side:
     model.device = dev                   # (as forward(..., device=) records it: the literal tables follow it)
     with torch.no_grad():
         table = model._table_for_inference().detach()
-        c = table.shape[1]
-        if scoring == "transe" and c != model.relation_dim:
-            raise ValueError(f"scoring='transe' needs the table width ({c}) to equal relation_dim ({model.relation_dim})")
-        if scoring == "transr":
-            w = model.gat_trans_M.detach()
-            if w.shape[1] != c:
-                raise ValueError(f"gat_trans_M is {tuple(w.shape)} for a table of width {c}")
-            perm, seg = ops.group_by_key(r, model.n_relations)
-            perm, seg = perm.long(), seg.tolist()
-            rowmax = ops.row_absmax(table)
-
-            def groups():      # one projection P_r = T W_r per relation present, alive while both sides use it
-                for rr in range(model.n_relations):
-                    if seg[rr + 1] > seg[rr]:
-                        p = ops.gemm_tall([table], [[w[rr]]], trans_b=False, rowmax=rowmax)
-                        yield p, ops.rank_sqnorm(p), perm[seg[rr]:seg[rr + 1]]
-        else:
-            def groups():
-                yield table, (ops.rank_sqnorm(table) if scoring == "transe" else None), torch.arange(b, device=dev)
-
+        groups = scoring_groups(model, scoring, table, r)
         better = torch.empty((len(sides), b), dtype=torch.int32, device=dev)
         equal = torch.empty((len(sides), b), dtype=torch.int32, device=dev)
-        for p, pn, pos in groups():
+        for p, pn, pos in groups:
             for j, s_ in enumerate(sides):
                 _count_group(model, scoring, s_, p, pn, pos, h, r, t, known, batch_size, better[j], equal[j])
             del p, pn

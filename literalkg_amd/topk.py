@@ -1,0 +1,127 @@
+"""Filtered top-k link prediction: the k most likely tails of (h, r, ?) -- or heads of (?, r, t) -- that are not already
+known, under the model's own scoring function.
+
+side='tail': ``ids`` are heads and the tails are ranked; side='head': ``ids`` are tails and the heads are ranked.  The
+queries are those of ranking.py: q = P_r[h] + e_r / q = P_r[t] - e_r ('transr', P_r = T W_r), the same without W_r
+('transe'), T[id] ('dot').  Candidates are ordered by the kernel score s_c = |p_c|^2 - 2 q.p_c (dot: -2 q.p_c), the
+value lkg_rank_count_f32 compares: ascending s is best first, ties go to the smaller entity id, a NaN score is never
+selected.  The reported score is the squared distance fl(|q|^2 + s) for 'transr' / 'transe' (non-decreasing along the
+list) and the dot product q.p = -s / 2 for 'dot' (exact, non-increasing).  A candidate c is dropped when (query, r, c)
+-- tail side -- or (c, r, query) -- head side -- is in ``known``; nothing is exempt.  With scoring='dot', r may be None:
+a pair known under any relation is dropped then.
+
+The selection runs on the device (lkg_topk.hip): a GEMM on the exact-f32 MFMA whose epilogue keeps a running top-k per
+query instead of storing the B x N scores.
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass
+from typing import Optional
+
+import torch
+
+from . import ops
+from .ranking import KnownTriples, _check_scoring, scoring_groups
+
+SIDES = ("tail", "head")
+
+
+@dataclass
+class TopKResult:
+    """B x k per query, best first: ``ids`` (int64 entity ids, -1 where fewer than k candidates are eligible),
+    ``scores`` (float32 reported scores, NaN where ids == -1) and ``kernel_scores`` (float32 s = |p|^2 - 2 q.p, the value
+    the selection and lkg_rank_count_f32 compare; NaN where ids == -1)."""
+    ids: torch.Tensor
+    scores: torch.Tensor
+    side: str
+    kernel_scores: torch.Tensor
+
+
+def _check_side(side: str) -> str:
+    if side not in SIDES:
+        raise ValueError(f"side must be one of {SIDES} (top-k ranks one side at a time), got {side!r}")
+    return side
+
+
+def _check_k(k) -> int:
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= ops.TOPK_MAX:
+        raise ValueError(f"k must be an integer in [1, {ops.TOPK_MAX}], got {k!r}")
+    return k
+
+
+def _check_ids(name, x):
+    if not isinstance(x, torch.Tensor) or x.dim() != 1 or x.dtype.is_floating_point or x.dtype == torch.bool:
+        raise ValueError(f"{name} must be a 1-D tensor of integer ids")
+
+
+def predict_topk(model, ids: torch.Tensor, r: Optional[torch.Tensor] = None, side: str = "tail", k: int = 10,
+                 known: Optional[KnownTriples] = None, scoring: Optional[str] = None,
+                 candidates: Optional[torch.Tensor] = None, batch_size: Optional[int] = None,
+                 splits: int = 0) -> TopKResult:
+    """The k best eligible candidates of every query on the model's inference table (see the module docstring).
+    candidates: optional 1-D tensor of unique entity ids to select among (ids are still entity ids).  batch_size: queries
+    per launch (None: as many as the workspace bound allows); splits: candidate splits per launch (0 = automatic).
+    Neither changes the result.  The model's mode, parameters and caches are left as they are."""
+    side = _check_side(side)
+    scoring = _check_scoring(scoring if scoring is not None else model.scoring)
+    k = _check_k(k)
+    _check_ids("ids", ids)
+    if r is None:
+        if scoring != "dot":
+            raise ValueError(f"scoring={scoring!r} needs the relations r (only 'dot' can filter without them)")
+    else:
+        _check_ids("r", r)
+        if r.numel() != ids.numel():
+            raise ValueError(f"ids and r have different lengths ({ids.numel()}, {r.numel()})")
+    if candidates is not None:
+        _check_ids("candidates", candidates)
+    if batch_size is not None and (isinstance(batch_size, bool) or int(batch_size) != batch_size or batch_size <= 0):
+        raise ValueError(f"batch_size must be a positive integer, got {batch_size!r}")
+    if isinstance(splits, bool) or int(splits) != splits or not 0 <= splits <= ops.TOPK_MAX_SPLITS:
+        raise ValueError(f"splits must be an integer in [0, {ops.TOPK_MAX_SPLITS}], got {splits!r}")
+    if scoring == "transr" and getattr(model, "gat_trans_M", None) is None:
+        raise ValueError("scoring='transr' needs a model with gat_trans_M (built with scoring='transr')")
+    if known is not None and known.n_entities != model.n_entities:
+        raise ValueError(f"known triples over {known.n_entities} entities, the model has {model.n_entities}")
+    dev = model.entity_embed.weight.device
+    if known is not None and known.device != dev:
+        raise ValueError(f"known triples live on {known.device}, the model on {dev}")
+    b = ids.numel()
+    if b == 0:
+        return TopKResult(torch.full((0, k), -1, dtype=torch.int64, device=dev),
+                          torch.zeros((0, k), dtype=torch.float32, device=dev), side,
+                          torch.zeros((0, k), dtype=torch.float32, device=dev))
+    (ids,) = ops.checked_ids(model.n_entities, ids.to(dev))
+    if r is not None:
+        (r,) = ops.checked_ids(model.n_relations, r.to(dev), what="relation")
+    cand = None
+    if candidates is not None:
+        (cand,) = ops.checked_ids(model.n_entities, candidates.to(dev), what="candidate entity")
+    ops.check_deferred_errors()
+    if cand is not None and torch.unique(cand).numel() != cand.numel():
+        raise ValueError("candidates must be unique entity ids")
+    model.device = dev
+    alpha = 1.0 if side == "tail" else -1.0             # q = P_r[h] + e_r  /  q = P_r[t] - e_r
+    filt = known.for_side(side) if known is not None else None
+    frel_all = r if r is not None else torch.full((b,), -1, dtype=torch.int64, device=dev)
+    out_ids = torch.empty((b, k), dtype=torch.int64, device=dev)
+    out_sc = torch.empty((b, k), dtype=torch.float32, device=dev)
+    out_s = torch.empty((b, k), dtype=torch.float32, device=dev)
+    with torch.no_grad():
+        table = model._table_for_inference().detach()
+        for p, pn, pos in scoring_groups(model, scoring, table, r, b):
+            qid, rel = ids[pos], (r[pos] if r is not None else None)
+            q = ops.rank_queries(p, qid, None if scoring == "dot" else model.relation_embed.weight.detach(), rel, alpha)
+            if cand is not None:                         # the candidate rows, scored with the same bits
+                p = ops.gather_rows(p, cand)
+                pn = ops.rank_sqnorm(p) if pn is not None else None
+            frel = frel_all[pos]
+            step = pos.numel() if batch_size is None else int(batch_size)
+            for lo in range(0, pos.numel(), step):
+                hi = min(lo + step, pos.numel())
+                ii, ss, vv = ops.topk_select(q[lo:hi], p, pn, k, filt, qid[lo:hi], frel[lo:hi], cand, splits)
+                out_ids[pos[lo:hi]] = ii
+                out_s[pos[lo:hi]] = ss
+                out_sc[pos[lo:hi]] = vv
+            del p, pn, q
+    return TopKResult(out_ids, out_sc, side, out_s)
