@@ -546,6 +546,9 @@ int lkg_adam_step_f32(int64_t n, float *param, const float *grad, float *exp_avg
  * Used for nn.Linear forward (trans_b = 1), its data gradient and its weight
  * gradient (model.py:111 etc., gate.py:24-25, linear_gat model.py:309).          */
 int64_t lkg_gemm_workspace(int32_t trans_a, int64_t m, int64_t n, int64_t k);
+/* The engine lkg_gemm_f32 runs this product on, given workspace_bytes of workspace (the choice lkg_gemm_f32 itself makes):
+ * 0 = the f32-input MFMA (a k-ordered chain), 1 = bf16 x 3 with A row-major, 2 = bf16 x 3 with both operands k-major. */
+int lkg_gemm_f32_engine(int32_t trans_a, int32_t trans_b, int64_t m, int64_t n, int64_t k, int64_t workspace_bytes);
 
 /* C[m,n] = opA(A)[m,k] opB(B)[k,n] with float64 accumulation, rounded to float32 once; SMALL products only (m n <= 2^24,
  * m n k <= 2^34).  The GCNII-style residual's weight fold W_lin (W')^T of the device path (model.py:95-98 evaluates

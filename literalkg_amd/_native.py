@@ -72,6 +72,7 @@ PROTOTYPES = {
     "lkg_linear_act_layernorm_fwd_f32": [i64, i32, i32, vp, vp, vp, vp, vp, vp, vp, f32, vp, vp, f32, vp, i64, vp, i64, f32,
                                          vp, vp, f32, u64, vp, i64, vp],
     "lkg_gemm_workspace": [i32, i64, i64, i64],
+    "lkg_gemm_f32_engine": [i32, i32, i64, i64, i64, i64],
     "lkg_gemm_f32": [i32, i32, i64, i64, i64, f32, vp, i64, vp, i64, f32, vp, i64, vp, vp, i64, vp],
     "lkg_gemm_f64acc_f32": [i32, i32, i64, i64, i64, vp, i64, vp, i64, vp, i64, vp],
     "lkg_colsum_f32": [i64, i32, vp, i64, vp, vp],

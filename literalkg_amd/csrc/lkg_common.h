@@ -112,6 +112,22 @@ __device__ __forceinline__ float drop_scale(unsigned row_key, unsigned col, floa
 }
 
 
+// Exponent e with mx * 2^e in [2^13, 2^14): the power-of-two operand scale of the fp16 hi / mid split engines
+// (lkg_gemm_tall.hip, lkg_gemm_wgrad.hip).  Never clamped: e runs from 13 - 127 = -114 (largest finite maximum) to 139, so
+// it is applied with ldexpf (exact for any int exponent; a float 2^e would overflow beyond e = 127) and the epilogue
+// unscales by the same exact ldexpf.  A subnormal maximum takes the exponent of 2^-126, 139: its elements are integer
+// multiples of 2^-149 below 2^23 of them, which land on multiples of 2^-10 below 2^13 -- inside fp16's normal range,
+// carried by hi / mid to 22 bits.  A zero maximum gives 0 (as a wrong zero hint on a non-zero row then leaves the row
+// unscaled and finite, not scaled by 2^139 into inf), an inf / NaN maximum 0 (every output of that row / column is
+// non-finite whatever its scale).  (Written with early returns: the select form of the same function makes the 8-wave
+// gate kernel spill under its 128-VGPR cap.)
+__device__ __forceinline__ int scale_exponent(float mx) {
+    const int ex = (__float_as_int(mx) >> 23) & 0xff;
+    if (ex == 0xff) return 0;
+    if (ex == 0) return mx == 0.f ? 0 : 139;
+    return 140 - ex;
+}
+
 // numerically safe -logsigmoid(x) = softplus(-x), the form ATen uses:
 // -(min(x,0) - log1p(exp(-|x|)))
 __device__ __forceinline__ float neg_logsigmoid(float x) {

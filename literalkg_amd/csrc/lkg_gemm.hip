@@ -5,6 +5,9 @@
 //                  (nn.Linear forward and data gradient);
 //   split engine 2 the same arithmetic, both operands k-major (weight gradients), transposing LDS reads.
 // The description below is the f32 engine's; the split engines are described where they are defined.
+// Stated bound of the f32 engine (tests/op_audit.py): per element r = |err| / (|A||B|) <= max(2 r_torch32,
+// 3e-7, 2 sqrt(k) 2^-24) -- an output is ONE k-ordered chain of k roundings, whose errors add like a random walk; at long
+// k that term, not 2 x torch's blocked reduction, is the limit.
 //
 //   C[m,n] = alpha * sum_k opA(A)[m,k] * opB(B)[k,n] + beta * C[m,n] (+ bias[n])
 //
@@ -150,6 +153,9 @@ struct MContig {
 // and six v_mfma_f32_32x32x16_bf16 (products exact, f32 accumulation) replace eight 32x32x2 f32 MFMAs per 16 k
 // at 2.7x the peak rate.  The dropped terms (am*bl, al*bm, al*bl) are below f32 rounding; measured against f64
 // the result is as accurate as the f32 MFMA chain (fewer accumulator roundings per output: 6 per 16 k, not 8).
+// Stated limit (no operand scales here; test_conditioning_gpu.py): the last term of an element below 2^-110 falls
+// below bf16's normal range, so such an element carries an absolute error <= 2^-134 and elements below 2^-134 drop out;
+// the product is within the f32 bound plus 2^-133 (sum_k |b_kj| + sum_k |a_ik|).
 // K-contiguous operands only (A row-major, B = nn.Linear weight): image [3 planes][128 rows][16 k] of bf16, one
 // ds_read_b128 per lane and plane fetches the 8 consecutive k of v_mfma_f32_32x32x16_bf16 (lane l: row l & 31,
 // k = 8 (l >> 5) + j).  The two 16-byte halves of a row are swapped on rows 16-31 of every 32, which makes the
@@ -607,6 +613,24 @@ extern "C" int64_t lkg_gemm_workspace(int32_t trans_a, int64_t m, int64_t n, int
     return tiles_n * ktiles * 3 * PLANE * (long)sizeof(__bf16);
 }
 
+// LKG_GEMM_F32_ONLY=1 in the environment keeps every product on the f32-input MFMA (the bit-exact k-ordered fmaf chain),
+// e.g. to bisect a numerical difference; read once.
+static bool gemm_f32_only() {
+    static const bool f32_only = [] {
+        const char *e = getenv("LKG_GEMM_F32_ONLY");
+        return e && e[0] == '1';
+    }();
+    return f32_only;
+}
+
+// 0 = f32-input MFMA, 1 = split engine 1 (A row-major, B pre-split into the caller's workspace), 2 = split engine 2
+extern "C" int lkg_gemm_f32_engine(int32_t trans_a, int32_t trans_b, int64_t m, int64_t n, int64_t k, int64_t workspace_bytes) {
+    if (gemm_f32_only()) return 0;
+    const int64_t need = lkg_gemm_workspace(trans_a, m, n, k);
+    if (need > 0 && workspace_bytes >= need) return 1;
+    return (trans_a && !trans_b && k >= 2048) ? 2 : 0;
+}
+
 extern "C" int lkg_gemm_f32(int32_t trans_a, int32_t trans_b, int64_t m, int64_t n, int64_t k, float alpha,
                             const float *a, int64_t lda, const float *b, int64_t ldb, float beta, float *c,
                             int64_t ldc, const float *bias, void *workspace, int64_t workspace_bytes,
@@ -647,26 +671,19 @@ extern "C" int lkg_gemm_f32(int32_t trans_a, int32_t trans_b, int64_t m, int64_t
             return LKG_ERR_HIP;
         }
     }
-    // LKG_GEMM_F32_ONLY=1 in the environment keeps every product on the f32-input MFMA (the bit-exact k-ordered fmaf
-    // chain), e.g. to bisect a numerical difference; read once.
-    static const bool f32_only = [] {
-        const char *e = getenv("LKG_GEMM_F32_ONLY");
-        return e && e[0] == '1';
-    }();
+    const int engine = lkg_gemm_f32_engine(trans_a, trans_b, m, n, k, workspace ? workspace_bytes : 0);
     const int ktiles = (int)((k + BK - 1) / BK);
     // Split engine 1: A row-major and B small enough to pre-split per call (a weight matrix), enough rows to pay for
     // the extra launch -- when the CALLER handed over the workspace for B's planes (lkg_gemm_workspace; no allocation
     // here).  (below ~16 k rows the call is bound by its host-side issue, ~12 us)
-    void *ws = nullptr;
-    const int64_t need = lkg_gemm_workspace(trans_a, m, n, k);
-    if (!f32_only && need > 0 && workspace && workspace_bytes >= need) ws = workspace;
+    void *ws = engine == 1 ? workspace : nullptr;
     if (ws) {
         hipLaunchKernelGGL(presplit_b_kernel, dim3((unsigned)(g.tiles_n * ktiles)), dim3(256), 0, s, b, (long)ldb,
                            (int)(trans_b != 0), (long)n, (long)k, ktiles, reinterpret_cast<__bf16 *>(ws));
         g.bp = reinterpret_cast<const __bf16 *>(ws);
         g.ktiles_b = ktiles;
     }
-    g.split_km = (!f32_only && trans_a && !trans_b && k >= 2048) ? 1 : 0;   // long reductions over rows: weight gradients
+    g.split_km = engine == 2 ? 1 : 0;   // long reductions over rows: weight gradients
     return run(trans_a != 0, trans_b != 0, g, dim3((unsigned)tiles, (unsigned)splits), s);
 }
 

@@ -5,7 +5,9 @@
 //
 // Arithmetic: "f16 x 2" on the fp16 matrix cores (v_mfma_f32_32x32x16_f16, 2.5 PF dense) with f32 accumulation.
 //   Every row of A (and every row of B = output column) is scaled by a power of two so that its largest magnitude lies
-//   in [2^13, 2^14), then every element is split into  hi = fp16(a') (round toward zero: the residual is then exact)  and
+//   in [2^13, 2^14) (any normal maximum up to 2^128, no clamp; a subnormal one is scaled as 2^-126 would be:
+//   scale_exponent, lkg_common.h; scale and unscale are exact ldexpf), then every element is split into
+//   hi = fp16(a') (round toward zero: the residual is then exact)  and
 //   mid = fp16((a' - hi) * 2^11)  -- 11 + 11 significant bits, both in fp16's NORMAL range for every element down to
 //   2^-27 of its row's maximum (below that the absolute error is < 2^-39 of the row maximum).  Then
 //       a'.b' = hi_a hi_b + 2^-11 (hi_a mid_b + mid_a hi_b) + O(2^-22 |a'||b'|)
@@ -109,16 +111,12 @@ struct TallArgs {
     float *mean, *rstd;
 };
 
-// exponent e with max * 2^e in [2^13, 2^14)   (0 for max == 0 / denormal; clamped so that ldexp stays finite)
-__device__ __forceinline__ int scale_exponent(float mx) {
-    const int ex = (__float_as_int(mx) >> 23) & 0xff;
-    if (ex == 0 || ex == 0xff) return 0;
-    return max(-100, min(100, 13 - (ex - 127)));
-}
-
 // one element group -> hi / mid fp16 pairs.  PRE: the residual is stored as it is (mid' = a' - hi, the 2^-11 of the cross
 // terms already inside the operand: fp16 subnormals for elements below 2^-17 of their row maximum) instead of scaled by
 // 2^11 into fp16's normal range -- the one-accumulator kernels of 64 x 128 wave tiles use it and need no scaled copy of hi.
+// Range within a row, as tested (test_conditioning_gpu.py): the "256x2" tiling carries every element with 22 bits down to
+// 2^-27 of its row's maximum, every other tiling down to 2^-16; below that an element's absolute error stays under 2^-34
+// of the row maximum (times |b|).
 template <bool PRE = false>
 __device__ __forceinline__ void split2(float a0, float a1, fp16x2 &hi, fp16x2 &mid) {
     hi = __builtin_amdgcn_cvt_pkrtz(a0, a1);

@@ -5,13 +5,19 @@
 //
 // Both operands arrive k-major (a thread sees 8 consecutive COLUMNS of one k), so the scale that keeps the fp16 split
 // exact has to be per COLUMN of each operand: column j is multiplied by the power of two that puts its largest
-// magnitude into [2^13, 2^14), every element is split into hi = fp16(a') (round toward zero) and
+// magnitude into [2^13, 2^14) (any normal maximum, no clamp; a subnormal one is scaled as 2^-126 would be; the exponent
+// is applied by ldexpf, as 2^e itself would overflow a float beyond e = 127: scale_exponent, lkg_common.h), every
+// element is split into
+// hi = fp16(a') (round toward zero) and
 // mid = fp16((a' - hi) * 2^11), and  a'.b' = hi_a hi_b + hs_a mid_b + mid_a hs_b  with hs = hi * 2^-11 (an exact exponent
 // shift): THREE v_mfma_f32_32x32x16_f16 per 16 k and 32 x 32 tile into ONE f32 accumulator, unscaled by an exact ldexp
 // by -(e_m + e_n) in the epilogue -- against the six bf16 MFMAs (and the three-plane split) of lkg_gemm_f32's engine 2.
 // Elements down to 2^-16 of their column's maximum carry the full 22 bits, smaller ones lose bits of the two cross
 // terms only (their absolute error stays below 2^-35 of the column maximum times |b|): normwise the result is as
-// accurate as an f32 GEMM's (tests against f64).  The column maxima are inputs: the producers of the operands emit
+// accurate as an f32 GEMM's (tests against f64).  Stated per-element bound (tests/op_audit.py):
+// r = |err| / (|A|^T|B|) <= max(3 r_torch32, 5e-7, 2^-22 + 2 sqrt(3 ceil(k/16)) 2^-24) -- 3 MFMA roundings per 16 rows
+// in one f32 chain plus the split's one-signed 2^-22 (round-toward-zero mids); on same-sign operands over many rows the
+// chain term is the limit.  The column maxima are inputs: the producers of the operands emit
 // them while they write (lkg_gate_blend_bwd_f32, lkg_row_absmax_f32's column output) or they are computed once for
 // constant tables (lkg_col_absmax_f32); without them the caller stays on the bf16 x 3 engine.
 //
@@ -45,13 +51,6 @@ struct WgArgs {
     int a_aligned, b_aligned;    // rows 16-byte aligned and k a multiple of 16: whole tiles may use unguarded 16-byte loads
 };
 
-// exponent e with max * 2^e in [2^13, 2^14)   (0 for max == 0 / denormal / non-finite; clamped so that ldexp stays finite)
-__device__ __forceinline__ int scale_exponent(float mx) {
-    const int ex = (__float_as_int(mx) >> 23) & 0xff;
-    if (ex == 0 || ex == 0xff) return 0;
-    return max(-100, min(100, 13 - (ex - 127)));
-}
-
 __device__ __forceinline__ int kmajor_off(int k, int c) {   // element offset of (k, c) inside a plane (lkg_gemm.hip)
     return k * BM + ((((c >> 5) ^ (k & 3)) << 5) | (c & 31));
 }
@@ -68,15 +67,15 @@ __device__ __forceinline__ f16x8 kmajor_frag(const _Float16 *plane, int c0, int 
 }
 
 // 8 consecutive columns of one k row -> their hi / mid halves in the two planes of an operand
-// (the column scales 2^e come from LDS at every step: 16 registers held across the MFMA block would cost an occupancy step)
-__device__ __forceinline__ void split_store(const float (&v)[8], const float *scale8, _Float16 *planes, int t) {
+// (the column exponents e come from LDS at every step: 16 registers held across the MFMA block would cost an occupancy step)
+__device__ __forceinline__ void split_store(const float (&v)[8], const int *exp8, _Float16 *planes, int t) {
     typedef __fp16 fp16x8 __attribute__((ext_vector_type(8)));
     fp16x8 hv, mv;
-    const float4 s0 = *reinterpret_cast<const float4 *>(scale8), s1 = *reinterpret_cast<const float4 *>(scale8 + 4);
-    const float sc[8] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w};
+    const int4 s0 = *reinterpret_cast<const int4 *>(exp8), s1 = *reinterpret_cast<const int4 *>(exp8 + 4);
+    const int sc[8] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w};
 #pragma unroll
     for (int j = 0; j < 8; j += 2) {
-        const float a0 = v[j] * sc[j], a1 = v[j + 1] * sc[j + 1];
+        const float a0 = ldexpf(v[j], sc[j]), a1 = ldexpf(v[j + 1], sc[j + 1]);
         const fp16x2 h = __builtin_amdgcn_cvt_pkrtz(a0, a1);
         const fp16x2 m = __builtin_amdgcn_cvt_pkrtz((a0 - (float)h[0]) * 2048.f, (a1 - (float)h[1]) * 2048.f);
         hv[j] = h[0]; hv[j + 1] = h[1];
@@ -106,9 +105,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
 
     // this thread's 8 columns of either operand and their exponents (fixed for the whole k loop)
     const int kr = t >> 4, c8 = (t & 15) * 8;
-    __shared__ __attribute__((aligned(16))) float scale_s[2][BM];              // 2^e of the tile's columns, per operand
-    if (t < BM) scale_s[0][t] = ldexpf(1.f, scale_exponent(g.a_colmax[min(m0 + t, g.m - 1)]));
-    else scale_s[1][t - BM] = ldexpf(1.f, scale_exponent(g.b_colmax[min(n0 + t - BM, g.n - 1)]));
+    __shared__ __attribute__((aligned(16))) int scale_s[2][BM];                // exponents e of the tile's columns, per operand
+    if (t < BM) scale_s[0][t] = scale_exponent(g.a_colmax[min(m0 + t, g.m - 1)]);
+    else scale_s[1][t - BM] = scale_exponent(g.b_colmax[min(n0 + t - BM, g.n - 1)]);
     __syncthreads();
 
     f32x16 acc[2][2];
@@ -539,11 +538,11 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const float *pa1 = pa0 + 8 * g.lda;
     const float *pb = g.b + (k_lo + kb) * g.ldb + min(n0 + cb, g.n - 4);
     const long step_a = RK * g.lda, step_b = RK * g.ldb;
-    float sa[4], sb[4];                           // 2^e of this thread's columns (both A pieces share theirs)
+    int sa[4], sb[4];                             // exponents e of this thread's columns (both A pieces share theirs)
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-        sa[j] = ldexpf(1.f, scale_exponent(g.a_colmax[min(m0 + ca + j, g.m - 1)]));
-        sb[j] = ldexpf(1.f, scale_exponent(g.b_colmax[min(n0 + cb + j, g.n - 1)]));
+        sa[j] = scale_exponent(g.a_colmax[min(m0 + ca + j, g.m - 1)]);
+        sb[j] = scale_exponent(g.b_colmax[min(n0 + cb + j, g.n - 1)]);
     }
 
     f32x16 acc[2][2];
@@ -572,8 +571,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         const f32x4 v = r[q >> 1];
         const bool isb = (q >> 1) == 2;
         const int keep = (isb ? keep_b : keep_a) & live, e0 = 2 * (q & 1);
-        px[q][0] = __int_as_float(__float_as_int(v[e0]) & keep) * (isb ? sb[e0] : sa[e0]);
-        px[q][1] = __int_as_float(__float_as_int(v[e0 + 1]) & keep) * (isb ? sb[e0 + 1] : sa[e0 + 1]);
+        px[q][0] = ldexpf(__int_as_float(__float_as_int(v[e0]) & keep), isb ? sb[e0] : sa[e0]);
+        px[q][1] = ldexpf(__int_as_float(__float_as_int(v[e0 + 1]) & keep), isb ? sb[e0 + 1] : sa[e0 + 1]);
         ph[q] = __builtin_amdgcn_cvt_pkrtz(px[q][0], px[q][1]);
     };
     auto t2 = [&](int q) {

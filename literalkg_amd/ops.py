@@ -223,6 +223,32 @@ def spmm_raw(rowptr, col, val, x, n_rows: int, out: Optional[torch.Tensor] = Non
     return out
 
 
+GEMM_F32_ENGINES = ("f32_mfma", "bf16x3_rows", "bf16x3_kmajor")        # lkg_gemm_f32_engine's 0 / 1 / 2
+
+
+def gemm_engine(a: torch.Tensor, b: torch.Tensor, trans_a: bool = False, trans_b: bool = False, alpha: float = 1.0,
+                beta: float = 0.0, out: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None) -> str:
+    """The engine ``gemm`` runs this product on (gemm dispatches on exactly this): "skinny", "tall_f16x2", "smallm", "longk"
+    (the bf16 x 3 long-k engine) or one of lkg_gemm_f32's GEMM_F32_ENGINES.  ``out`` None: a fresh output."""
+    a_, b_ = _f32_rows(a), _f32_rows(b)
+    m, k = (a_.shape[1], a_.shape[0]) if trans_a else a_.shape
+    n = b_.shape[0] if trans_b else b_.shape[1]
+    out_ptr, out_ld = (N.ptr(out), _ld(out)) if out is not None else (None, n)
+    if (not trans_a and alpha == 1.0 and _ENGINE != "f32" and (k * n <= 2048 or m < TALL_MIN_ROWS)
+            and N.load().lkg_gemm_skinny_ok(m, n, k, N.ptr(a_), _ld(a_), out_ptr if out is not None else N.ptr(a_), out_ld)):
+        # (a fresh output is contiguous and 256-byte aligned: a_'s own alignment stands in for its address)
+        return "skinny"
+    if not trans_a and k > 0 and tall_ok(m, n, (k,), single_panel_too=tagged_rowmax(a) is not None):
+        return "tall_f16x2"
+    if trans_a and not trans_b and alpha == 1.0 and beta == 0.0 and bias is None and _WGRAD_ENGINE == "longk":
+        if N.load().lkg_gemm_smallm_ok(m, n, k, N.ptr(a_), _ld(a_), N.ptr(b_), _ld(b_)):
+            return "smallm"
+        if N.load().lkg_gemm_longk_ok(m, n, k, N.ptr(a_), _ld(a_), N.ptr(b_), _ld(b_)):
+            return "longk"
+    need = int(N.load().lkg_gemm_workspace(int(trans_a), m, n, k)) if _ENGINE != "f32" else 0
+    return GEMM_F32_ENGINES[int(N.load().lkg_gemm_f32_engine(int(trans_a), int(trans_b), m, n, k, need))]
+
+
 def gemm(a: torch.Tensor, b: torch.Tensor, trans_a: bool = False, trans_b: bool = False, alpha: float = 1.0,
          beta: float = 0.0, out: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
     """out = alpha * op(a) @ op(b) + beta * out (+ bias).  a, b: row-major 2-D fp32 (row stride free)."""
@@ -239,21 +265,19 @@ def gemm(a: torch.Tensor, b: torch.Tensor, trans_a: bool = False, trans_b: bool 
         raise ValueError(f"gemm: out must be a float32 {m} x {n} tensor with unit column stride (got {tuple(out.shape)})")
     if bias is not None and bias.numel() != n:
         raise ValueError(f"gemm: bias of {bias.numel()} elements for {n} output columns")
-    if (not trans_a and alpha == 1.0 and _ENGINE != "f32" and (k * n <= 2048 or m < TALL_MIN_ROWS)
-            and N.load().lkg_gemm_skinny_ok(m, n, k, N.ptr(a), _ld(a), N.ptr(out), _ld(out))):
+    engine = gemm_engine(a, b, trans_a, trans_b, alpha, beta, out, bias)
+    if engine == "skinny":
         # narrow in AND out (the 32 x 32 products of narrow layers): exact f32 on the VALU at streaming rate
         N.call("lkg_gemm_skinny_f32", m, n, k, N.ptr(a), _ld(a), N.ptr(b), _ld(b), int(trans_b), float(beta), N.ptr(out),
                _ld(out), N.ptr(bias), _stream())
         return out
-    if not trans_a and k > 0 and tall_ok(m, n, (k,), single_panel_too=tagged_rowmax(a) is not None):
+    if engine == "tall_f16x2":
         return gemm_tall((a,), ((b,),), bool(trans_b), bias, alpha, beta, out)
-    if (trans_a and not trans_b and alpha == 1.0 and beta == 0.0 and bias is None and _WGRAD_ENGINE == "longk"
-            and N.load().lkg_gemm_smallm_ok(m, n, k, N.ptr(a), _ld(a), N.ptr(b), _ld(b))):
+    if engine == "smallm":
         # a narrow dY (conv_dim 32 / 64) over many rows: exact f32 on the VALU instead of a mostly empty matrix-core tile
         N.call("lkg_gemm_smallm_f32", m, n, k, N.ptr(a), _ld(a), N.ptr(b), _ld(b), N.ptr(out), _ld(out), _stream())
         return out
-    if (trans_a and not trans_b and alpha == 1.0 and beta == 0.0 and bias is None and _WGRAD_ENGINE == "longk"
-            and N.load().lkg_gemm_longk_ok(m, n, k, N.ptr(a), _ld(a), N.ptr(b), _ld(b))):
+    if engine == "longk":
         # weight gradients (a^T @ b over millions of rows): the 256 x 128 engine with three tiles in flight
         N.call("lkg_gemm_longk_f32", m, n, k, N.ptr(a), _ld(a), N.ptr(b), _ld(b), N.ptr(out), _ld(out), _stream())
         return out
@@ -262,7 +286,6 @@ def gemm(a: torch.Tensor, b: torch.Tensor, trans_a: bool = False, trans_b: bool 
     N.call("lkg_gemm_f32", int(trans_a), int(trans_b), m, n, k, float(alpha), N.ptr(a), _ld(a), N.ptr(b), _ld(b),
            float(beta), N.ptr(out), _ld(out), N.ptr(bias), N.ptr(ws), ws.numel() if ws is not None else 0, _stream())
     return out
-
 
 
 def colsum(x: torch.Tensor) -> torch.Tensor:

@@ -213,8 +213,10 @@ def test_drawn_configuration_matches_the_oracle(L, O, gpu_device, seed):
             print("near a LeakyReLU kink:", e, "\n-> the same configuration with other values")
 
 
-def run_case(L, O, gpu_device, c, seed, value_seed):
-    """configuration c on the graph drawn from `seed`, parameters / literals / batch drawn from `value_seed`"""
+def build_case(L, O, gpu_device, c, seed, value_seed):
+    """the model, its float32 parameters, literals, graph and batch of configuration c: the graph drawn from `seed`,
+    parameters / literals / batch drawn from `value_seed` (run_case; test_op_audit_gpu.py audits the same models)"""
+    from types import SimpleNamespace
     from literalkg_amd import io
     from literalkg_amd.synth import make_batch, make_kg
     n, n_rel = c["n"], c["n_rel"]
@@ -246,6 +248,26 @@ def run_case(L, O, gpu_device, c, seed, value_seed):
     pool = min(n, c.get("batch_pool", 0)) or n
     bh, br, bp, bn = (torch.from_numpy(x) for x in make_batch(pool, c["batch"], c["neg"], seed=value_seed + 2))
     br = torch.from_numpy(np.repeat(np.random.default_rng(value_seed + 3).integers(0, n_rel, c["batch"]), c["neg"]))
+    return SimpleNamespace(n=n, n_rel=n_rel, h=h, t=t, r=r, cfg=cfg, num=num, txt=txt, a_in=a_in, m=m, params=params,
+                           bh=bh, br=br, bp=bp, bn=bn)
+
+
+NAMED_SEEDS = [44053, 3130, pytest.param(81374, marks=pytest.mark.xfail(strict=True, reason=(
+    "linear_gat.weight 6.35e-3 of its largest entry from float64 (fp32 oracle 1.5e-5), next to LeakyReLU inputs 4e-10 .. "
+    "5e-9 of the largest on three draws; every device op of the step is within its per-op bound (test_op_audit_gpu.py)")))]
+
+
+@pytest.mark.parametrize("seed", NAMED_SEEDS)
+def test_named_configuration_matches_the_oracle(L, O, gpu_device, seed):
+    """the seeds whose end-to-end misses were investigated, under the sweep's rules, on every run"""
+    test_drawn_configuration_matches_the_oracle(L, O, gpu_device, seed)
+
+
+def run_case(L, O, gpu_device, c, seed, value_seed):
+    """configuration c on the graph drawn from `seed`, parameters / literals / batch drawn from `value_seed`"""
+    k = build_case(L, O, gpu_device, c, seed, value_seed)
+    n, n_rel, h, t, r, cfg, num, txt, a_in, m, params = k.n, k.n_rel, k.h, k.t, k.r, k.cfg, k.num, k.txt, k.a_in, k.m, k.params
+    bh, br, bp, bn = k.bh, k.br, k.bp, k.bn
     dev = lambda *xs: [x.to(gpu_device) for x in xs]
 
     def in_f64(loss_of, params=params):
