@@ -666,6 +666,29 @@ int lkg_topk_select_f32(int64_t n_q, int64_t n_cand, int32_t k, const float *q, 
 int lkg_topk_merge_f32(int64_t n_q, int32_t top_k, int32_t splits, const float *ws_s, const int32_t *ws_i,
                        const float *qn, int64_t *out_ids, float *out_scores, float *out_values, void *stream);
 
+/* The MLP pair head at inference (lkg_pairmlp.hip; literalkg_amd/pairmlp.py).  Queries are the n_q rows of uq, candidates
+ * the n_cand rows of v (f32, 128 columns, row strides ldu / ldv: multiples of 4, 16-byte aligned bases): the two halves
+ * of the head's first layer, already projected (the bias in either of them).  With the folded second and third layer --
+ * w2 64 x 128 row-major contiguous, b2[64], w3[64], b3[1], BatchNorm in inference form folded in -- the logit of a pair is
+ *     z(i, c) = w3 . relu(w2 relu(uq_i + v_c) + b2) + b3
+ * on the exact-f32 MFMA in a fixed operation order: the same bits for a pair wherever and by whichever of the entry
+ * points below it is computed.
+ *
+ * lkg_pair_mlp_scores_f32: out[i * ldo + c] = z(i, c).
+ * lkg_pair_mlp_splits    : as lkg_topk_splits, for lkg_pair_mlp_select_f32.
+ * lkg_pair_mlp_select_f32: as lkg_topk_select_f32 with s(i, c) = -2 z(i, c) (exact): per split each query's best top_k
+ *     (s, id) into ws_s / ws_i [S][n_q][top_k], for lkg_topk_merge_f32 with qn NULL, whose values -s / 2 are the logits.
+ *     The n_q x n_cand logits are never stored.  Filter, cand_ids, tie and NaN rules as for lkg_topk_select_f32.     */
+int lkg_pair_mlp_scores_f32(int64_t n_q, int64_t n_cand, const float *uq, int64_t ldu, const float *v, int64_t ldv,
+                            const float *w2, const float *b2, const float *w3, const float *b3, float *out, int64_t ldo,
+                            void *stream);
+int32_t lkg_pair_mlp_splits(int64_t n_q, int64_t n_cand, int32_t requested);
+int lkg_pair_mlp_select_f32(int64_t n_q, int64_t n_cand, const float *uq, int64_t ldu, const float *v, int64_t ldv,
+                            const float *w2, const float *b2, const float *w3, const float *b3, const int64_t *cand_ids,
+                            const int64_t *filter_row, const int64_t *filter_rel, const int32_t *rowptr,
+                            const int32_t *col, const int32_t *eptr, const int32_t *rel, int32_t top_k, int32_t splits,
+                            float *ws_s, int32_t *ws_i, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

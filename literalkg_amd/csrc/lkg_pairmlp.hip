@@ -1,0 +1,287 @@
+// The MLP pair head at inference (literalkg_amd/pairmlp.py): logits of every (query, candidate) pair, and the filtered
+// top-k of them per query, from the two PROJECTED tables of the head's first layer.
+//
+// With BatchNorm in inference form folded forward the head is
+//     x1 = relu(u_q + v_c)                      u = Uq row (128, bias included), v = V row (128)
+//     x2 = relu(W2' x1 + b2')                   W2' 64 x 128
+//     z  = w3' . x2 + b3'                       the logit
+// fc2 is 16 384 FLOP per pair and runs on the exact-f32 MFMA v_mfma_f32_16x16x4_f32: the A operand is x1 for 16
+// candidates of one query, formed on the fly, the B operand W2'^T, register-resident (32 k-steps x 4 column blocks = 128
+// VGPRs per lane).  A wave owns 16 candidates at a time: their V rows sit in 32 VGPRs (lane (r, s) = (l & 15, l >> 4)
+// holds elements 16 t + 4 s .. + 3, t = 0..7, of candidate r's row) while the wave walks the workgroup's query rows,
+// whose u rows are staged once in LDS and read as broadcasts.  So a V row is read from memory once per workgroup and
+// candidate, a u row once per workgroup, and the per-pair work touches registers and LDS only.
+//
+// Position independence: a pair's logit is a fixed sequence of f32 operations on (u row, v row, folded weights) --
+// k order 16 t + {0, 4, 8, 12} + e for e = 0..3, t = 0..7 (the order of lkg_rank_common.h); the epilogue's in-lane fma
+// chain over the 4 column blocks, then the xor butterfly over the 16 lanes of a row -- whatever tile, wave, row, split
+// or launch computes it, and the same in the store and the select epilogue (both call pm_pair_logits).
+//
+// Selection: the state and the merge of lkg_topk_common.h, fed s = -2 z (exact), so ascending s is descending logit and
+// lkg_topk_merge_f32 reports -s / 2 = z.  After the lane reduction one lane holds a pair's logit; it is pushed when it
+// passes its row's threshold.  A tile brings a row at most 64 candidates and the queues (64 slots) are merged after
+// every tile, so a push always lands.
+#include "lkg_rank_common.h"
+#include "lkg_topk_common.h"
+
+namespace {
+
+constexpr int PM_THREADS = 256;
+constexpr int PM_H1 = 128;           // fc1 outputs = fc2 inputs
+constexpr int PM_H2 = 64;            // fc2 outputs
+constexpr int PM_ROWS = 64;          // query rows per workgroup (at most; TK_ROWS lists)
+constexpr int PM_COLS = 64;          // candidates per tile: 16 per wave
+constexpr int PM_STORE_TILES = 8;    // candidate tiles per workgroup of the store kernel
+static_assert(PM_ROWS == TK_ROWS && PM_COLS <= TK_QUEUE, "one tile must fit the queues");
+
+struct PairWeights {
+    float4 b[PM_H1 / 16][PM_H2 / 16];   // b[t][j]: W2'[16 j + r][16 t + 4 s .. + 3]
+    float b2[PM_H2 / 16], w3[PM_H2 / 16];   // element 16 j + r
+    float b3;
+};
+
+__device__ __forceinline__ void pm_load_weights(PairWeights &w, const float *__restrict__ w2,
+                                                const float *__restrict__ b2, const float *__restrict__ w3,
+                                                const float *__restrict__ b3, int r, int s) {
+#pragma unroll
+    for (int t = 0; t < PM_H1 / 16; ++t)
+#pragma unroll
+        for (int j = 0; j < PM_H2 / 16; ++j)
+            w.b[t][j] = *reinterpret_cast<const float4 *>(w2 + (16 * j + r) * PM_H1 + 16 * t + 4 * s);
+#pragma unroll
+    for (int j = 0; j < PM_H2 / 16; ++j) {
+        w.b2[j] = b2[16 * j + r];
+        w.w3[j] = w3[16 * j + r];
+    }
+    w.b3 = b3[0];
+}
+
+__device__ __forceinline__ float pm_relu(float x) { return x < 0.f ? 0.f : x; }      // (NaN stays NaN)
+
+// the wave's 16 V rows: vf[t] = elements 16 t + 4 s .. + 3 of row `vrow`
+__device__ __forceinline__ void pm_load_v(float4 (&vf)[PM_H1 / 16], const float *__restrict__ vrow, int s) {
+#pragma unroll
+    for (int t = 0; t < PM_H1 / 16; ++t) vf[t] = *reinterpret_cast<const float4 *>(vrow + 16 * t + 4 * s);
+}
+
+// z[v] = the logit of (the query whose u row is at `urow` in LDS, the wave's candidate 4 s + v), the same bits in all
+// 16 lanes r of the row group.  Call with all lanes active.
+__device__ __forceinline__ void pm_pair_logits(float (&z)[4], const float *urow, const float4 (&vf)[PM_H1 / 16],
+                                               const PairWeights &w, int s) {
+    f32x4 acc[PM_H2 / 16];
+#pragma unroll
+    for (int j = 0; j < PM_H2 / 16; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int t = 0; t < PM_H1 / 16; ++t) {
+        const float4 u = *reinterpret_cast<const float4 *>(urow + 16 * t + 4 * s);
+        const float4 x = make_float4(pm_relu(u.x + vf[t].x), pm_relu(u.y + vf[t].y), pm_relu(u.z + vf[t].z),
+                                     pm_relu(u.w + vf[t].w));
+#pragma unroll
+        for (int j = 0; j < PM_H2 / 16; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(x.x, w.b[t][j].x, acc[j], 0, 0, 0);
+#pragma unroll
+        for (int j = 0; j < PM_H2 / 16; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(x.y, w.b[t][j].y, acc[j], 0, 0, 0);
+#pragma unroll
+        for (int j = 0; j < PM_H2 / 16; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(x.z, w.b[t][j].z, acc[j], 0, 0, 0);
+#pragma unroll
+        for (int j = 0; j < PM_H2 / 16; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(x.w, w.b[t][j].w, acc[j], 0, 0, 0);
+    }
+    // acc[j][v]: candidate 4 s + v, fc2 output 16 j + r
+#pragma unroll
+    for (int v = 0; v < 4; ++v) {
+        float p = 0.f;
+#pragma unroll
+        for (int j = 0; j < PM_H2 / 16; ++j) p = __builtin_fmaf(w.w3[j], pm_relu(acc[j][v] + w.b2[j]), p);
+        z[v] = group_sum<16>(p) + w.b3;
+    }
+}
+
+// lane r < 4 of a row group speaks for candidate 4 s + r
+__device__ __forceinline__ float pm_pick(const float (&z)[4], int r) {
+    return r == 0 ? z[0] : r == 1 ? z[1] : r == 2 ? z[2] : z[3];
+}
+
+// stage the u rows q0 .. q0 + nq - 1 in LDS
+__device__ __forceinline__ void pm_stage_u(float *su, const float *__restrict__ uq, long ldu, long q0, int nq) {
+    for (int x = threadIdx.x; x < nq * (PM_H1 / 4); x += PM_THREADS) {
+        const int row = x / (PM_H1 / 4), c4 = x - row * (PM_H1 / 4);
+        *reinterpret_cast<float4 *>(su + row * PM_H1 + 4 * c4) =
+            *reinterpret_cast<const float4 *>(uq + (q0 + row) * ldu + 4 * c4);
+    }
+}
+
+// out[q, c] = z(q, c): a workgroup owns 64 query rows and PM_STORE_TILES candidate tiles
+__global__ __launch_bounds__(PM_THREADS) void pair_mlp_store_kernel(
+    long n_q, long n_c, const float *__restrict__ uq, long ldu, const float *__restrict__ vt, long ldv,
+    const float *__restrict__ w2, const float *__restrict__ b2, const float *__restrict__ w3,
+    const float *__restrict__ b3, float *__restrict__ out, long ldo, long tiles_q, long tiles_c) {
+    __shared__ __attribute__((aligned(16))) float su[PM_ROWS * PM_H1];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int r = lane & 15, s = lane >> 4;
+    const long bid = blockIdx.x;
+    const long q0 = (bid % tiles_q) * PM_ROWS;
+    const long t_lo = (bid / tiles_q) * PM_STORE_TILES;
+    const long t_hi = t_lo + PM_STORE_TILES < tiles_c ? t_lo + PM_STORE_TILES : tiles_c;
+    const int nq = (int)(n_q - q0 < PM_ROWS ? n_q - q0 : PM_ROWS);
+    pm_stage_u(su, uq, ldu, q0, nq);
+    PairWeights w;
+    pm_load_weights(w, w2, b2, w3, b3, r, s);
+    __syncthreads();
+    for (long t = t_lo; t < t_hi; ++t) {
+        const long c0 = t * PM_COLS + wave * 16;
+        const long crow = c0 + r < n_c ? c0 + r : n_c - 1;        // rows past the end: computed, never stored
+        float4 vf[PM_H1 / 16];
+        pm_load_v(vf, vt + crow * ldv, s);
+        const long cw = c0 + 4 * s + (r & 3);
+        const bool mine = r < 4 && cw < n_c;
+        for (int qi = 0; qi < nq; ++qi) {
+            float z[4];
+            pm_pair_logits(z, su + qi * PM_H1, vf, w, s);
+            if (mine) out[(q0 + qi) * ldo + cw] = pm_pick(z, r);
+        }
+    }
+}
+
+template <int KC>
+struct PairSmem {
+    TopkSmem<KC> tk;
+    __attribute__((aligned(16))) float u[PM_ROWS * PM_H1];
+};
+
+// per split and query row the best kk (s = -2 z, id) of the split's candidates into ws [S][n_q][kk]; a workgroup owns
+// qr <= 64 query rows and the split's candidate tiles
+template <int KC>
+__global__ __launch_bounds__(PM_THREADS) void pair_mlp_select_kernel(
+    long n_q, long n_c, const float *__restrict__ uq, long ldu, const float *__restrict__ vt, long ldv,
+    const float *__restrict__ w2, const float *__restrict__ b2, const float *__restrict__ w3,
+    const float *__restrict__ b3, const long *__restrict__ cand, const long *__restrict__ frow,
+    const long *__restrict__ frel, const int *__restrict__ rowptr, const int *__restrict__ col,
+    const int *__restrict__ eptr, const int *__restrict__ rel, int kk, int splits, int qr, long tiles_q, long tiles_c,
+    float *__restrict__ ws_s, int *__restrict__ ws_i) {
+    __shared__ PairSmem<KC> sm;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int r = lane & 15, s = lane >> 4;
+    const long bid = blockIdx.x;
+    const long q0 = (bid % tiles_q) * qr;
+    const int split = (int)(bid / tiles_q);
+    const long t_lo = split * tiles_c / splits, t_hi = (split + 1) * tiles_c / splits;
+    const int nq = (int)(n_q - q0 < qr ? n_q - q0 : qr);
+    for (int x = tid; x < TK_ROWS * KC; x += PM_THREADS) {
+        (&sm.tk.ls[0][0])[x] = __builtin_inff();
+        (&sm.tk.li[0][0])[x] = TK_NONE;
+    }
+    if (tid < TK_ROWS) sm.tk.qn[tid] = 0;
+    pm_stage_u(sm.u, uq, ldu, q0, nq);
+    PairWeights w;
+    pm_load_weights(w, w2, b2, w3, b3, r, s);
+    __syncthreads();
+    for (long t = t_lo; t < t_hi; ++t) {
+        const long c0 = t * PM_COLS + wave * 16;
+        const long crow = c0 + r < n_c ? c0 + r : n_c - 1;        // rows past the end: computed, never pushed
+        float4 vf[PM_H1 / 16];
+        pm_load_v(vf, vt + crow * ldv, s);
+        const long cw = c0 + 4 * s + (r & 3);
+        const bool mine = r < 4 && cw < n_c;
+        const int cid = mine ? (int)(cand ? cand[cw] : cw) : TK_NONE;
+        for (int qi = 0; qi < nq; ++qi) {
+            float z[4];
+            pm_pair_logits(z, sm.u + qi * PM_H1, vf, w, s);
+            if (mine) {
+                const float sv = -2.f * pm_pick(z, r);
+                if (tk_before(sv, cid, sm.tk.ls[qi][kk - 1], sm.tk.li[qi][kk - 1])) {
+                    const int slot = atomicAdd(&sm.tk.qn[qi], 1);
+                    if (slot < TK_QUEUE) {                          // (always: at most PM_COLS pushes per row and tile)
+                        sm.tk.qs[qi][slot] = sv;
+                        sm.tk.qi[qi][slot] = cid;
+                    }
+                }
+            }
+        }
+        __syncthreads();
+        topk_merge_queues<KC, true>(sm.tk, kk, q0, n_q, frow, frel, rowptr, col, eptr, rel);
+        __syncthreads();
+    }
+    for (int x = tid; x < nq * kk; x += PM_THREADS) {
+        const int row = x / kk, j = x - row * kk;
+        const long o = ((long)split * n_q + q0 + row) * kk + j;
+        ws_s[o] = sm.tk.ls[row][j];
+        ws_i[o] = sm.tk.li[row][j];
+    }
+}
+
+// query rows per workgroup of the select kernel: fewer for small batches, so that the splits (at most 64) fill the chip
+long pm_select_rows(long n_q) { return n_q >= 512 ? 64 : n_q >= 128 ? 32 : 16; }
+
+bool pm_operands_ok(const float *uq, long ldu, const float *v, long ldv, const float *w2) {
+    return lkg_aligned16(uq) && lkg_aligned16(v) && lkg_aligned16(w2) && ldu % 4 == 0 && ldv % 4 == 0 && ldu >= PM_H1 &&
+           ldv >= PM_H1;
+}
+
+}  // namespace
+
+extern "C" int32_t lkg_pair_mlp_splits(int64_t n_q, int64_t n_cand, int32_t requested) {
+    if (n_q <= 0 || n_cand <= 0 || requested < 0 || requested > LKG_TOPK_MAX_SPLITS) return 0;
+    const long qr = pm_select_rows(n_q);
+    const long tiles_q = (n_q + qr - 1) / qr, tiles_c = (n_cand + PM_COLS - 1) / PM_COLS;
+    long s_ = requested > 0 ? requested : (2 * 256 + tiles_q - 1) / tiles_q;   // auto: >= 2 workgroups per CU
+    s_ = s_ < LKG_TOPK_MAX_SPLITS ? s_ : LKG_TOPK_MAX_SPLITS;
+    s_ = s_ < tiles_c ? s_ : tiles_c;
+    return (int32_t)(s_ > 1 ? s_ : 1);
+}
+
+extern "C" int lkg_pair_mlp_scores_f32(int64_t n_q, int64_t n_cand, const float *uq, int64_t ldu, const float *v,
+                                       int64_t ldv, const float *w2, const float *b2, const float *w3, const float *b3,
+                                       float *out, int64_t ldo, void *stream) {
+    LKG_REQUIRE(n_q >= 0 && n_cand >= 0 && ldo >= n_cand, "lkg_pair_mlp_scores_f32: bad sizes");
+    if (n_q == 0 || n_cand == 0) return LKG_OK;
+    LKG_REQUIRE(uq && v && w2 && b2 && w3 && b3 && out, "lkg_pair_mlp_scores_f32: null pointer");
+    LKG_REQUIRE(pm_operands_ok(uq, ldu, v, ldv, w2),
+                "lkg_pair_mlp_scores_f32: uq, v and w2 must be 16-byte aligned with row strides that are multiples of 4 "
+                "(at least 128)");
+    const long tiles_q = (n_q + PM_ROWS - 1) / PM_ROWS, tiles_c = (n_cand + PM_COLS - 1) / PM_COLS;
+    const long chunks = (tiles_c + PM_STORE_TILES - 1) / PM_STORE_TILES;
+    LKG_REQUIRE(tiles_q * chunks < INT32_MAX, "lkg_pair_mlp_scores_f32: too many workgroups (split the queries)");
+    hipLaunchKernelGGL(pair_mlp_store_kernel, dim3((unsigned)(tiles_q * chunks)), dim3(PM_THREADS), 0,
+                       (hipStream_t)stream, (long)n_q, (long)n_cand, uq, (long)ldu, v, (long)ldv, w2, b2, w3, b3, out,
+                       (long)ldo, tiles_q, tiles_c);
+    LKG_CHECK_LAUNCH("lkg_pair_mlp_scores_f32");
+    return LKG_OK;
+}
+
+extern "C" int lkg_pair_mlp_select_f32(int64_t n_q, int64_t n_cand, const float *uq, int64_t ldu, const float *v,
+                                       int64_t ldv, const float *w2, const float *b2, const float *w3, const float *b3,
+                                       const int64_t *cand_ids, const int64_t *filter_row, const int64_t *filter_rel,
+                                       const int32_t *rowptr, const int32_t *col, const int32_t *eptr, const int32_t *rel,
+                                       int32_t top_k, int32_t splits, float *ws_s, int32_t *ws_i, void *stream) {
+    LKG_REQUIRE(n_q >= 0 && n_cand > 0 && n_cand < INT32_MAX, "lkg_pair_mlp_select_f32: bad sizes");
+    LKG_REQUIRE(top_k >= 1 && top_k <= LKG_TOPK_MAX, "lkg_pair_mlp_select_f32: top_k must lie in [1, %d]", LKG_TOPK_MAX);
+    if (n_q == 0) return LKG_OK;
+    LKG_REQUIRE(splits >= 1 && splits == lkg_pair_mlp_splits(n_q, n_cand, splits),
+                "lkg_pair_mlp_select_f32: splits must come from lkg_pair_mlp_splits");
+    LKG_REQUIRE(uq && v && w2 && b2 && w3 && b3 && ws_s && ws_i, "lkg_pair_mlp_select_f32: null pointer");
+    LKG_REQUIRE(pm_operands_ok(uq, ldu, v, ldv, w2),
+                "lkg_pair_mlp_select_f32: uq, v and w2 must be 16-byte aligned with row strides that are multiples of 4 "
+                "(at least 128)");
+    LKG_REQUIRE(!rowptr || (filter_row && filter_rel && col && eptr && rel), "lkg_pair_mlp_select_f32: incomplete filter");
+    const long qr = pm_select_rows(n_q);
+    const long tiles_q = (n_q + qr - 1) / qr, tiles_c = (n_cand + PM_COLS - 1) / PM_COLS;
+    LKG_REQUIRE(tiles_q * splits < INT32_MAX, "lkg_pair_mlp_select_f32: too many workgroups (split the queries)");
+    const dim3 grid((unsigned)(tiles_q * splits));
+    const hipStream_t st = (hipStream_t)stream;
+#define LKG_PM_LAUNCH(KC)                                                                                              \
+    hipLaunchKernelGGL((pair_mlp_select_kernel<KC>), grid, dim3(PM_THREADS), 0, st, (long)n_q, (long)n_cand, uq,       \
+                       (long)ldu, v, (long)ldv, w2, b2, w3, b3, (const long *)cand_ids, (const long *)filter_row,      \
+                       (const long *)filter_rel, rowptr, col, eptr, rel, top_k, splits, (int)qr, tiles_q, tiles_c,     \
+                       ws_s, ws_i)
+    if (top_k <= 16) LKG_PM_LAUNCH(16);
+    else if (top_k <= 32) LKG_PM_LAUNCH(32);
+    else if (top_k <= 64) LKG_PM_LAUNCH(64);
+    else LKG_PM_LAUNCH(128);
+#undef LKG_PM_LAUNCH
+    LKG_CHECK_LAUNCH("lkg_pair_mlp_select_f32");
+    return LKG_OK;
+}
+
+int lkg_internal_preload_pairmlp() {
+    hipFuncAttributes attr;
+    return hipFuncGetAttributes(&attr, reinterpret_cast<const void *>(&pair_mlp_store_kernel)) == hipSuccess ? 0 : 1;
+}

@@ -15,113 +15,11 @@
 // against the tightened thresholds.  At the end each list goes to workspace [S][n_q][kk]; topk_merge_kernel merges the
 // S lists of a row into the final sorted, padded output.  The result is the kk smallest (s, id) of the whole candidate
 // set -- a unique set, whatever S, the query batch or the launch shape.
+// The list, the queue and their merge live in lkg_topk_common.h (lkg_pairmlp.hip selects with them too).
 #include "lkg_rank_common.h"
-
-#include <climits>
+#include "lkg_topk_common.h"
 
 namespace {
-
-constexpr int TK_THREADS = 256;
-constexpr int TK_ROWS = 64;          // queries per workgroup
-constexpr int TK_COLS = 256;         // candidates per tile (64 per wave)
-constexpr int TK_QUEUE = 64;         // queue slots per row (one per lane of the merging wave)
-constexpr int TK_MAX_SPLITS = LKG_TOPK_MAX_SPLITS;   // one list per lane in topk_merge_kernel
-constexpr int TK_NONE = INT_MAX;     // the sentinel id
-
-// (a, ia) before (b, ib): float comparison of the scores, then the id; false whenever a is NaN
-__device__ __forceinline__ bool tk_before(float a, int ia, float b, int ib) { return a < b || (a == b && ia < ib); }
-
-// is (query row `f`, relation `want`, candidate id) a known triple?  want < 0: known under any relation
-__device__ __forceinline__ bool tk_known(const int *__restrict__ rowptr, const int *__restrict__ col,
-                                         const int *__restrict__ eptr, const int *__restrict__ rel, long f, int want,
-                                         int id) {
-    int lo = rowptr[f], hi = rowptr[f + 1];
-    while (lo < hi) {                          // first entry with col >= id
-        const int mid = (lo + hi) >> 1;
-        if (col[mid] < id) lo = mid + 1;
-        else hi = mid;
-    }
-    if (lo == rowptr[f + 1] || col[lo] != id) return false;
-    if (want < 0) return true;
-    for (int x = eptr[lo]; x < eptr[lo + 1]; ++x)
-        if (rel[x] == want) return true;
-    return false;
-}
-
-template <int KC>
-struct TopkSmem {
-    float ls[TK_ROWS][KC];           // per row: the sorted list (first kk entries used)
-    int li[TK_ROWS][KC];
-    float qs[TK_ROWS][TK_QUEUE];     // per row: the queue
-    int qi[TK_ROWS][TK_QUEUE];
-    int qn[TK_ROWS];                 // pushes since the last merge (may exceed TK_QUEUE: those did not land)
-};
-
-// Merge every row's queue into its list; wave w owns rows 16 w .. 16 w + 15.  Queue entries that are known triples are
-// dropped.  Each kept entry's new place is (list entries before it) + (kept queue entries before it); each list entry
-// moves right by the kept queue entries before it.  (s, id) pairs are distinct within a row (every candidate is pushed
-// once), so the places form a permutation; whatever lands at kk or beyond falls out.  All reads of a row precede its
-// writes in the wave's program order, so the merge is in place.
-template <int KC>
-__device__ void topk_merge_queues(TopkSmem<KC> &sm, int kk, long q0, long n_q, const long *__restrict__ frow,
-                                  const long *__restrict__ frel, const int *__restrict__ rowptr,
-                                  const int *__restrict__ col, const int *__restrict__ eptr, const int *__restrict__ rel) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int rr = 0; rr < TK_ROWS / 4; ++rr) {
-        const int row = wave * (TK_ROWS / 4) + rr;
-        const int n = min(sm.qn[row], TK_QUEUE);
-        if (n == 0) continue;                                       // (uniform in the wave)
-        float xs = __builtin_inff();
-        int xi = TK_NONE;
-        bool xv = false;
-        if (lane < n) {
-            xs = sm.qs[row][lane];
-            xi = sm.qi[row][lane];
-            xv = true;
-            if (rowptr && q0 + row < n_q)
-                xv = !tk_known(rowptr, col, eptr, rel, frow[q0 + row], (int)frel[q0 + row], xi);
-        }
-        const unsigned long long kept = __ballot(xv);
-        float y0s = __builtin_inff(), y1s = __builtin_inff();
-        int y0i = TK_NONE, y1i = TK_NONE;
-        if (lane < kk) {
-            y0s = sm.ls[row][lane];
-            y0i = sm.li[row][lane];
-        }
-        if (lane + 64 < kk) {
-            y1s = sm.ls[row][lane + 64];
-            y1i = sm.li[row][lane + 64];
-        }
-        int lo = 0, hi = kk;                                        // list entries before x (the list is sorted)
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (tk_before(sm.ls[row][mid], sm.li[row][mid], xs, xi)) lo = mid + 1;
-            else hi = mid;
-        }
-        int cx = 0, c0 = 0, c1 = 0;
-        for (int j = 0; j < n; ++j) {
-            if (!((kept >> j) & 1ull)) continue;                    // (uniform)
-            const float zs = sm.qs[row][j];
-            const int zi = sm.qi[row][j];
-            cx += tk_before(zs, zi, xs, xi) ? 1 : 0;
-            c0 += tk_before(zs, zi, y0s, y0i) ? 1 : 0;
-            c1 += tk_before(zs, zi, y1s, y1i) ? 1 : 0;
-        }
-        if (lane < kk && lane + c0 < kk) {
-            sm.ls[row][lane + c0] = y0s;
-            sm.li[row][lane + c0] = y0i;
-        }
-        if (lane + 64 < kk && lane + 64 + c1 < kk) {
-            sm.ls[row][lane + 64 + c1] = y1s;
-            sm.li[row][lane + 64 + c1] = y1i;
-        }
-        if (xv && lo + cx < kk) {
-            sm.ls[row][lo + cx] = xs;
-            sm.li[row][lo + cx] = xi;
-        }
-        if (lane == 0) sm.qn[row] = 0;
-    }
-}
 
 template <bool VEC, int KC>
 __global__ __launch_bounds__(TK_THREADS) void topk_select_kernel(

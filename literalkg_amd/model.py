@@ -698,12 +698,18 @@ class LiteralKG(nn.Module):
     def predict_topk(self, ids, r=None, side: str = "tail", k: int = 10, known=None, scoring: Optional[str] = None,
                      candidates=None, batch_size: Optional[int] = None, splits: int = 0):
         """The k best tails of (ids, r, ?) (side 'tail') or heads of (?, r, ids) (side 'head') on the inference table,
-        known triples dropped (literalkg_amd/topk.py): scoring 'transr' / 'transe' / 'dot' (default: self.scoring),
-        known a ranking.KnownTriples filter, candidates an optional subset of entity ids.  Returns a topk.TopKResult
+        known triples dropped (literalkg_amd/topk.py): scoring 'transr' / 'transe' / 'dot' (default: self.scoring) or 'mlp'
+        (the trained pair head, literalkg_amd/pairmlp.py), known a ranking.KnownTriples filter, candidates an optional subset of entity ids.  Returns a topk.TopKResult
         (ids, scores, side)."""
         from .topk import predict_topk
         return predict_topk(self, ids, r, side=side, k=k, known=known, scoring=scoring, candidates=candidates,
                             batch_size=batch_size, splits=splits)
+
+    def mlp_scores(self, head_ids, tail_ids, logits: bool = False):
+        """The len(head_ids) x len(tail_ids) probabilities (or logits) of the MLP pair head on the inference table: what
+        mode='mlp' gives in eval mode for every pair, without forming the pairs (literalkg_amd/pairmlp.py)."""
+        from .pairmlp import mlp_scores
+        return mlp_scores(self, head_ids, tail_ids, logits=logits)
 
     def initialize_MLP(self):
         """The pair-classification head of model.py:499-504 (same module names, so checkpoints interchange)."""

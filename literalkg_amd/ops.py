@@ -2289,3 +2289,97 @@ def topk_select(q: torch.Tensor, p: torch.Tensor, pn: Optional[torch.Tensor], k:
         N.call("lkg_topk_merge_f32", m, k, s_, N.ptr(ws_s), N.ptr(ws_i), N.ptr(qn[lo:hi]) if qn is not None else None,
                N.ptr(ids[lo:hi]), N.ptr(scores[lo:hi]), N.ptr(values[lo:hi]), _stream())
     return ids, scores, values
+
+
+# ----------------------------------------------------------------------------- the MLP pair head (lkg_pairmlp.hip)
+PAIR_MLP_H1 = 128            # fc1 outputs = fc2 inputs
+PAIR_MLP_H2 = 64             # fc2 outputs
+
+
+def _pair_mlp_operands(what, uq, v, w2, b2, w3, b3):
+    """The operands as the kernels want them: f32, 128 columns, 16-byte aligned rows; the folded weights contiguous."""
+    _need_gpu(uq, v, w2, b2, w3, b3)
+    uq, v = _f32_rows(uq), _f32_rows(v)
+    if uq.dim() != 2 or v.dim() != 2 or uq.shape[1] != PAIR_MLP_H1 or v.shape[1] != PAIR_MLP_H1:
+        raise ValueError(f"{what}: uq and v must have {PAIR_MLP_H1} columns (got {tuple(uq.shape)}, {tuple(v.shape)})")
+    if tuple(w2.shape) != (PAIR_MLP_H2, PAIR_MLP_H1) or b2.numel() != PAIR_MLP_H2 or w3.numel() != PAIR_MLP_H2 or \
+            b3.numel() != 1:
+        raise ValueError(f"{what}: the folded head must be w2 {PAIR_MLP_H2} x {PAIR_MLP_H1}, b2 / w3 of {PAIR_MLP_H2}, "
+                         f"b3 of 1 (got {tuple(w2.shape)}, {b2.numel()}, {w3.numel()}, {b3.numel()})")
+
+    def rows16(t):
+        return t if t.data_ptr() % 16 == 0 and _ld(t) % 4 == 0 else t.clone(memory_format=torch.contiguous_format)
+
+    def flat(t):
+        t = t.detach().to(torch.float32).contiguous()
+        return t if t.data_ptr() % 16 == 0 else t.clone()
+    return rows16(uq), rows16(v), flat(w2), flat(b2).reshape(-1), flat(w3).reshape(-1), flat(b3).reshape(-1)
+
+
+def pair_mlp_scores(uq: torch.Tensor, v: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor, w3: torch.Tensor,
+                    b3: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[i, c] = w3 . relu(w2 relu(uq[i] + v[c]) + b2) + b3, the logit of the folded MLP pair head for every (query
+    row, candidate row) of the two projected tables (n_q x 128, n_c x 128; lkg_pair_mlp_scores_f32).  out: an optional
+    float32 n_q x n_c tensor with unit column stride (any row stride)."""
+    uq, v, w2, b2, w3, b3 = _pair_mlp_operands("pair_mlp_scores", uq, v, w2, b2, w3, b3)
+    n_q, n_c = uq.shape[0], v.shape[0]
+    if out is None:
+        out = torch.empty((n_q, n_c), dtype=torch.float32, device=uq.device)
+    elif tuple(out.shape) != (n_q, n_c) or out.dtype != torch.float32 or (n_c > 1 and out.stride(1) != 1) or \
+            out.device != uq.device:
+        raise ValueError(f"pair_mlp_scores: out must be a float32 {n_q} x {n_c} tensor with unit column stride on {uq.device}")
+    if n_q == 0 or n_c == 0:
+        return out
+    N.call("lkg_pair_mlp_scores_f32", n_q, n_c, N.ptr(uq), _ld(uq), N.ptr(v), _ld(v), N.ptr(w2), N.ptr(b2), N.ptr(w3),
+           N.ptr(b3), N.ptr(out), out.stride(0) if n_q > 1 else max(n_c, out.stride(0)), _stream())
+    return out
+
+
+def pair_mlp_topk(uq: torch.Tensor, v: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor, w3: torch.Tensor,
+                  b3: torch.Tensor, k: int, filt=None, filter_row: Optional[torch.Tensor] = None,
+                  filter_rel: Optional[torch.Tensor] = None, cand_ids: Optional[torch.Tensor] = None, splits: int = 0):
+    """(ids int64, logits f32), each n_q x k: per query row of uq the k candidate rows of v with the largest logit of
+    pair_mlp_scores -- the same bits -- ties by the smaller id, NaN never selected; the n_q x n_c logits are never stored
+    (lkg_pair_mlp_select_f32, lkg_topk_merge_f32).  ids, filt / filter_row / filter_rel, cand_ids, splits, the padding
+    (-1 / NaN) and the workspace bound are those of topk_select."""
+    k, splits = int(k), int(splits)
+    if not 1 <= k <= TOPK_MAX:
+        raise ValueError(f"pair_mlp_topk: k must lie in [1, {TOPK_MAX}], got {k}")
+    if not 0 <= splits <= TOPK_MAX_SPLITS:
+        raise ValueError(f"pair_mlp_topk: splits must lie in [0, {TOPK_MAX_SPLITS}], got {splits}")
+    _need_gpu(cand_ids, filter_row, filter_rel)
+    uq, v, w2, b2, w3, b3 = _pair_mlp_operands("pair_mlp_topk", uq, v, w2, b2, w3, b3)
+    n_q, n_c = uq.shape[0], v.shape[0]
+    if cand_ids is not None and cand_ids.numel() != n_c:
+        raise ValueError(f"pair_mlp_topk: {cand_ids.numel()} candidate ids for {n_c} candidate rows")
+    dev = uq.device
+    ids = torch.full((n_q, k), -1, dtype=torch.int64, device=dev)
+    logits = torch.full((n_q, k), float("nan"), dtype=torch.float32, device=dev)
+    if n_q == 0 or n_c == 0:
+        return ids, logits
+    scores = torch.empty((n_q, k), dtype=torch.float32, device=dev)          # s = -2 z, the order's key
+    cand_ids = _i64(cand_ids.reshape(-1)) if cand_ids is not None else None
+    if filt is not None:
+        rowptr, col, eptr, rel = filt
+        filter_row = _i64(filter_row.reshape(-1))
+        filter_rel = _i64(filter_rel.reshape(-1))
+        if filter_row.numel() != n_q or filter_rel.numel() != n_q:
+            raise ValueError(f"pair_mlp_topk: {filter_row.numel()} filter rows for {n_q} queries")
+    lib = N.load()
+    step = max(64, TOPK_WORKSPACE_BYTES // (TOPK_MAX_SPLITS * k * 8) // 64 * 64)     # rows per launch (worst-case S)
+    for lo in range(0, n_q, step):
+        hi = min(n_q, lo + step)
+        m = hi - lo
+        s_ = int(lib.lkg_pair_mlp_splits(m, n_c, splits))
+        ws_s = torch.empty(s_ * m * k, dtype=torch.float32, device=dev)
+        ws_i = torch.empty(s_ * m * k, dtype=torch.int32, device=dev)
+        qq = uq[lo:hi]
+        fargs = [None] * 6
+        if filt is not None:
+            fargs = [N.ptr(filter_row[lo:hi]), N.ptr(filter_rel[lo:hi]), N.ptr(rowptr), N.ptr(col), N.ptr(eptr),
+                     N.ptr(rel)]
+        N.call("lkg_pair_mlp_select_f32", m, n_c, N.ptr(qq), _ld(qq), N.ptr(v), _ld(v), N.ptr(w2), N.ptr(b2), N.ptr(w3),
+               N.ptr(b3), N.ptr(cand_ids), *fargs, k, s_, N.ptr(ws_s), N.ptr(ws_i), _stream())
+        N.call("lkg_topk_merge_f32", m, k, s_, N.ptr(ws_s), N.ptr(ws_i), None, N.ptr(ids[lo:hi]), N.ptr(scores[lo:hi]),
+               N.ptr(logits[lo:hi]), _stream())
+    return ids, logits

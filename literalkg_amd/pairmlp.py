@@ -1,0 +1,167 @@
+"""The MLP pair head at inference: all-pairs logits (``mlp_scores``, the MLP counterpart of ``calc_score``) and the
+backend of ``predict_topk(scoring="mlp")``.
+
+The head of mode='mlp' is sigmoid(fc3(bn2(relu(fc2(bn1(relu(fc1([e_h | e_t])))))))).  At inference BatchNorm is affine per
+feature, bn(x) = a x + c with a = gamma / sqrt(running_var + eps), c = beta - running_mean a, and since ReLU comes
+before each BatchNorm both fold forward into the next Linear:
+
+    u_h = W1[:, :C] e_h + b1                     v_t = W1[:, C:] e_t
+    x1  = relu(u_h + v_t)
+    x2  = relu(W2' x1 + b2')       W2' = W2 diag(a1),   b2' = W2 c1 + b2
+    z   = w3' . x2 + b3'           w3' = w3 * a2,       b3' = w3 . c2 + b3
+    p   = sigmoid(z)
+
+fc1 separates over the two entities, so every entity is projected once (the tall GEMM) and the per-pair work -- fc2 on the
+exact-f32 MFMA, fc3 in its epilogue -- runs in lkg_pairmlp.hip, which stores the logits or keeps a running filtered
+top-k per query without storing them.  Everything orders by the logit z: the sigmoid is
+monotone but saturates in f32.  A pair's logit has the same bits wherever it is computed: in ``mlp_scores``, in
+``predict_topk`` on either side, in any batch, split or candidate order.
+
+BatchNorm always uses its running statistics here, whatever ``model.training`` says; the model's mode, parameters,
+buffers and caches are left as they are.
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass
+from typing import Optional
+
+import torch
+
+from . import ops
+
+_SIGMOID_CHUNK = 1 << 24      # elements per float64 temporary of _sigmoid_
+
+
+@dataclass
+class FoldedMLPHead:
+    """The head with BatchNorm folded in, float32 on the model's device: w1h / w1t (128 x C, the head and tail halves of
+    fc1), b1 (128), w2 (64 x 128), b2 (64), w3 (64), b3 (1)."""
+    w1h: torch.Tensor
+    w1t: torch.Tensor
+    b1: torch.Tensor
+    w2: torch.Tensor
+    b2: torch.Tensor
+    w3: torch.Tensor
+    b3: torch.Tensor
+
+
+def _bn_affine(bn, width: int, name: str):
+    """(a, c) of bn(x) = a x + c in float64 from the running statistics."""
+    if getattr(bn, "running_mean", None) is None or getattr(bn, "running_var", None) is None:
+        raise ValueError(f"{name} keeps no running statistics (track_running_stats=False): the inference form of the "
+                         "head is undefined")
+    if bn.running_mean.numel() != width:
+        raise ValueError(f"{name} has {bn.running_mean.numel()} features, the head needs {width}")
+    one = torch.ones(width, dtype=torch.float64, device=bn.running_mean.device)
+    gamma = bn.weight.detach().double() if bn.weight is not None else one
+    beta = bn.bias.detach().double() if bn.bias is not None else torch.zeros_like(one)
+    a = gamma / torch.sqrt(bn.running_var.detach().double() + bn.eps)
+    return a, beta - bn.running_mean.detach().double() * a
+
+
+def fold_mlp_head_f64(model):
+    """The folded head in float64: (w1h, w1t, b1, w2, b2, w3, b3); see the module docstring."""
+    for name in ("fc1", "norm1", "fc2", "norm2", "fc3"):
+        if not hasattr(model, name):
+            raise AttributeError("the model has no MLP head: call initialize_MLP() first")
+    h1, h2 = ops.PAIR_MLP_H1, ops.PAIR_MLP_H2
+    w1, w2, w3 = model.fc1.weight.detach(), model.fc2.weight.detach(), model.fc3.weight.detach()
+    if w1.shape[0] != h1 or w1.shape[1] % 2 or tuple(w2.shape) != (h2, h1) or tuple(w3.shape) != (1, h2):
+        raise ValueError(f"the pair-head kernels take the head 2C -> {h1} -> {h2} -> 1 that initialize_MLP builds (got fc1 "
+                         f"{tuple(w1.shape)}, fc2 {tuple(w2.shape)}, fc3 {tuple(w3.shape)})")
+    for lin, name in ((model.fc1, "fc1"), (model.fc2, "fc2"), (model.fc3, "fc3")):
+        if lin.bias is None:
+            raise ValueError(f"{name} has no bias: not the head initialize_MLP builds")
+    a1, c1 = _bn_affine(model.norm1, h1, "norm1")
+    a2, c2 = _bn_affine(model.norm2, h2, "norm2")
+    c = w1.shape[1] // 2
+    w1, w2, w3 = w1.double(), w2.double(), w3.double().reshape(-1)
+    return (w1[:, :c].contiguous(), w1[:, c:].contiguous(), model.fc1.bias.detach().double(),
+            w2 * a1[None, :], (w2 * c1[None, :]).sum(dim=1) + model.fc2.bias.detach().double(),
+            w3 * a2, ((w3 * c2).sum() + model.fc3.bias.detach().double().reshape(())).reshape(1))
+
+
+def fold_mlp_head(model) -> FoldedMLPHead:
+    """The model's head with both BatchNorms (running statistics) folded forward, computed in float64 and rounded once to
+    float32.  AttributeError without a head (initialize_MLP not called); ValueError for a BatchNorm without running
+    statistics or a head other than 2C -> 128 -> 64 -> 1."""
+    return FoldedMLPHead(*(t.to(torch.float32).contiguous() for t in fold_mlp_head_f64(model)))
+
+
+def _sigmoid_(z: torch.Tensor) -> torch.Tensor:
+    """sigmoid of float32 logits in place, evaluated in float64 and rounded once -- so the probability is monotone in the
+    logit and within an ulp of the true value -- through temporaries of bounded size."""
+    flat = z.view(-1) if z.is_contiguous() else None
+    if flat is None:
+        for row in z:
+            _sigmoid_(row)
+        return z
+    for lo in range(0, flat.numel(), _SIGMOID_CHUNK):
+        part = flat[lo:lo + _SIGMOID_CHUNK]
+        part.copy_(torch.sigmoid(part.double()))
+    return z
+
+
+def _check_ids(name, x):
+    if not isinstance(x, torch.Tensor) or x.dim() != 1 or x.dtype.is_floating_point or x.dtype == torch.bool:
+        raise ValueError(f"{name} must be a 1-D tensor of integer ids")
+
+
+def _table_width_ok(head: FoldedMLPHead, table: torch.Tensor):
+    if table.shape[1] != head.w1h.shape[1]:
+        raise ValueError(f"fc1 takes 2 x {head.w1h.shape[1]} inputs, the inference table is {table.shape[1]} wide")
+
+
+def _project(rows: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """rows @ w^T (+ bias): one half of fc1 over the given table rows, on the tall-GEMM engine."""
+    if rows.shape[0] == 0:
+        return torch.empty((0, w.shape[0]), dtype=torch.float32, device=rows.device)
+    return ops.gemm_tall([rows], [[w]], trans_b=True, bias=bias)
+
+
+def mlp_scores(model, head_ids: torch.Tensor, tail_ids: torch.Tensor, logits: bool = False) -> torch.Tensor:
+    """The len(head_ids) x len(tail_ids) matrix of the head's probabilities p(h_i, t_j) -- or logits -- on the model's
+    inference table: what model(h, t, mode='mlp') gives in eval mode for every pair, without forming the pairs.  Only
+    the rows named are projected.  The result is one float32 tensor of the caller's choosing (rows x cols x 4 bytes)."""
+    _check_ids("head_ids", head_ids)
+    _check_ids("tail_ids", tail_ids)
+    head = fold_mlp_head(model)
+    dev = model.entity_embed.weight.device
+    hid, tid = ops.checked_ids(model.n_entities, head_ids.to(dev), tail_ids.to(dev))
+    ops.check_deferred_errors()
+    model.device = dev
+    with torch.no_grad():
+        table = model._table_for_inference().detach()
+        _table_width_ok(head, table)
+        uq = _project(ops.gather_rows(table, hid), head.w1h, head.b1)
+        v = _project(ops.gather_rows(table, tid), head.w1t)
+        out = ops.pair_mlp_scores(uq, v, head.w2, head.b2, head.w3, head.b3)
+        return out if logits else _sigmoid_(out)
+
+
+def predict_topk_mlp(model, head: FoldedMLPHead, ids, r, side, k, filt, cand, batch_size, splits):
+    """predict_topk's backend for scoring='mlp' (arguments already checked and on the device): (ids, probabilities,
+    logits), each B x k."""
+    dev = ids.device
+    b = ids.numel()
+    with torch.no_grad():
+        table = model._table_for_inference().detach()
+        _table_width_ok(head, table)
+        qrows = ops.gather_rows(table, ids)
+        crows = table if cand is None else ops.gather_rows(table, cand)
+        if side == "tail":                   # pairs (query, c): the query in fc1's head half, with the bias
+            uq, v = _project(qrows, head.w1h, head.b1), _project(crows, head.w1t)
+        else:                                # pairs (c, query): the candidates in the head half, with the bias
+            uq, v = _project(qrows, head.w1t), _project(crows, head.w1h, head.b1)
+        del qrows, crows
+        frel = r if r is not None else torch.full((b,), -1, dtype=torch.int64, device=dev)
+        out_ids = torch.empty((b, k), dtype=torch.int64, device=dev)
+        out_z = torch.empty((b, k), dtype=torch.float32, device=dev)
+        step = b if batch_size is None else int(batch_size)
+        for lo in range(0, b, step):
+            hi = min(lo + step, b)
+            ii, zz = ops.pair_mlp_topk(uq[lo:hi], v, head.w2, head.b2, head.w3, head.b3, k, filt, ids[lo:hi], frel[lo:hi],
+                                       cand, splits)
+            out_ids[lo:hi] = ii
+            out_z[lo:hi] = zz
+        return out_ids, _sigmoid_(out_z.clone()), out_z

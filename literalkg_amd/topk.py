@@ -10,6 +10,10 @@ list) and the dot product q.p = -s / 2 for 'dot' (exact, non-increasing).  A can
 -- tail side -- or (c, r, query) -- head side -- is in ``known``; nothing is exempt.  With scoring='dot', r may be None:
 a pair known under any relation is dropped then.
 
+scoring='mlp' ranks by the trained pair head of mode='mlp' instead (pairmlp.py, lkg_pairmlp.hip): candidates are
+ordered by the head's logit z, descending, ties to the smaller id; ``scores`` is the probability sigmoid(z)
+(non-increasing), ``kernel_scores`` the logit.  r may be None (any relation) or given (that relation only), as for 'dot'.
+
 The selection runs on the device (lkg_topk.hip): a GEMM on the exact-f32 MFMA whose epilogue keeps a running top-k per
 query instead of storing the B x N scores.
 """
@@ -30,7 +34,7 @@ SIDES = ("tail", "head")
 class TopKResult:
     """B x k per query, best first: ``ids`` (int64 entity ids, -1 where fewer than k candidates are eligible),
     ``scores`` (float32 reported scores, NaN where ids == -1) and ``kernel_scores`` (float32 s = |p|^2 - 2 q.p, the value
-    the selection and lkg_rank_count_f32 compare; NaN where ids == -1)."""
+    the selection and lkg_rank_count_f32 compare -- for scoring='mlp' the head's logit; NaN where ids == -1)."""
     ids: torch.Tensor
     scores: torch.Tensor
     side: str
@@ -63,11 +67,14 @@ def predict_topk(model, ids: torch.Tensor, r: Optional[torch.Tensor] = None, sid
     per launch (None: as many as the workspace bound allows); splits: candidate splits per launch (0 = automatic).
     Neither changes the result.  The model's mode, parameters and caches are left as they are."""
     side = _check_side(side)
-    scoring = _check_scoring(scoring if scoring is not None else model.scoring)
+    scoring = scoring if scoring is not None else model.scoring
+    mlp = scoring == "mlp"                               # the pair head (pairmlp.py); ranking.SCORINGS are the embedding scores
+    if not mlp:
+        scoring = _check_scoring(scoring)
     k = _check_k(k)
     _check_ids("ids", ids)
     if r is None:
-        if scoring != "dot":
+        if scoring not in ("dot", "mlp"):
             raise ValueError(f"scoring={scoring!r} needs the relations r (only 'dot' can filter without them)")
     else:
         _check_ids("r", r)
@@ -83,6 +90,12 @@ def predict_topk(model, ids: torch.Tensor, r: Optional[torch.Tensor] = None, sid
         raise ValueError("scoring='transr' needs a model with gat_trans_M (built with scoring='transr')")
     if known is not None and known.n_entities != model.n_entities:
         raise ValueError(f"known triples over {known.n_entities} entities, the model has {model.n_entities}")
+    head = None
+    if mlp:
+        from .pairmlp import fold_mlp_head, predict_topk_mlp
+        if candidates is not None and torch.unique(candidates).numel() != candidates.numel():
+            raise ValueError("candidates must be unique entity ids")
+        head = fold_mlp_head(model)                      # (AttributeError without initialize_MLP)
     dev = model.entity_embed.weight.device
     if known is not None and known.device != dev:
         raise ValueError(f"known triples live on {known.device}, the model on {dev}")
@@ -101,8 +114,11 @@ def predict_topk(model, ids: torch.Tensor, r: Optional[torch.Tensor] = None, sid
     if cand is not None and torch.unique(cand).numel() != cand.numel():
         raise ValueError("candidates must be unique entity ids")
     model.device = dev
-    alpha = 1.0 if side == "tail" else -1.0             # q = P_r[h] + e_r  /  q = P_r[t] - e_r
     filt = known.for_side(side) if known is not None else None
+    if mlp:
+        out_ids, out_p, out_z = predict_topk_mlp(model, head, ids, r, side, k, filt, cand, batch_size, splits)
+        return TopKResult(out_ids, out_p, side, out_z)
+    alpha = 1.0 if side == "tail" else -1.0             # q = P_r[h] + e_r  /  q = P_r[t] - e_r
     frel_all = r if r is not None else torch.full((b,), -1, dtype=torch.int64, device=dev)
     out_ids = torch.empty((b, k), dtype=torch.int64, device=dev)
     out_sc = torch.empty((b, k), dtype=torch.float32, device=dev)
