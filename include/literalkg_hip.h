@@ -678,7 +678,22 @@ int lkg_topk_merge_f32(int64_t n_q, int32_t top_k, int32_t splits, const float *
  * lkg_pair_mlp_splits    : as lkg_topk_splits, for lkg_pair_mlp_select_f32.
  * lkg_pair_mlp_select_f32: as lkg_topk_select_f32 with s(i, c) = -2 z(i, c) (exact): per split each query's best top_k
  *     (s, id) into ws_s / ws_i [S][n_q][top_k], for lkg_topk_merge_f32 with qn NULL, whose values -s / 2 are the logits.
- *     The n_q x n_cand logits are never stored.  Filter, cand_ids, tie and NaN rules as for lkg_topk_select_f32.     */
+ *     The n_q x n_cand logits are never stored.  Filter, cand_ids, tie and NaN rules as for lkg_topk_select_f32.
+ *
+ * Filtered ranking under the head (higher logit is better), the counterpart of lkg_rank_prepare_f32 / lkg_rank_count_f32:
+ * lkg_pair_mlp_prepare_f32: thr[i] = z(i, truth[i]) (truth[i] a row of v) and, with a filter, better[i] / equal[i] = MINUS
+ *     the number of filtered candidates c != truth[i] with z(i, c) > thr[i] / == thr[i] (else 0).  The filter is a
+ *     structure of lkg_csr_build_device over n_rows entity ids (rowptr int32[n_rows+1], col, eptr, rel): query i drops
+ *     every col[e] of row filter_row[i] that has a raw edge with relation filter_rel[i] (filter_rel[i] < 0: any
+ *     relation).  cand_slot int32[n_rows] maps an entity id to its row of v, -1 = not a candidate (such entries are
+ *     skipped); cand_slot NULL = the identity, n_rows == n_cand.  rowptr NULL = no filter.  An entry counts once
+ *     however many raw edges it has; an entry that names the truth is skipped.
+ * lkg_pair_mlp_count_f32  : better[i] += #{c != truth[i] : z(i, c) > thr[i]}, equal[i] += #{c != truth[i] : z == thr[i]}
+ *     over the n_cand rows of v (int32 atomics, one per row, count and workgroup: the result does not depend on the
+ *     order of arrival or the launch shape; the n_q x n_cand logits are never stored).  After prepare + count, better /
+ *     equal are the filtered counts.  Every logit compared -- threshold, counted, filtered -- has the bits
+ *     lkg_pair_mlp_scores_f32 stores for that pair.  A NaN logit counts nowhere; a NaN threshold gives 0 / 0.  64-bit
+ *     addressing throughout, n_cand < INT32_MAX.                                                                  */
 int lkg_pair_mlp_scores_f32(int64_t n_q, int64_t n_cand, const float *uq, int64_t ldu, const float *v, int64_t ldv,
                             const float *w2, const float *b2, const float *w3, const float *b3, float *out, int64_t ldo,
                             void *stream);
@@ -688,6 +703,14 @@ int lkg_pair_mlp_select_f32(int64_t n_q, int64_t n_cand, const float *uq, int64_
                             const int64_t *filter_row, const int64_t *filter_rel, const int32_t *rowptr,
                             const int32_t *col, const int32_t *eptr, const int32_t *rel, int32_t top_k, int32_t splits,
                             float *ws_s, int32_t *ws_i, void *stream);
+int lkg_pair_mlp_prepare_f32(int64_t n_q, int64_t n_cand, const float *uq, int64_t ldu, const float *v, int64_t ldv,
+                             const float *w2, const float *b2, const float *w3, const float *b3, const int64_t *truth,
+                             int64_t n_rows, const int32_t *cand_slot, const int64_t *filter_row,
+                             const int64_t *filter_rel, const int32_t *rowptr, const int32_t *col, const int32_t *eptr,
+                             const int32_t *rel, float *thr, int32_t *better, int32_t *equal, void *stream);
+int lkg_pair_mlp_count_f32(int64_t n_q, int64_t n_cand, const float *uq, int64_t ldu, const float *v, int64_t ldv,
+                           const float *w2, const float *b2, const float *w3, const float *b3, const float *thr,
+                           const int64_t *truth, int32_t *better, int32_t *equal, void *stream);
 
 #ifdef __cplusplus
 }

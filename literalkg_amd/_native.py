@@ -104,6 +104,9 @@ PROTOTYPES = {
     "lkg_pair_mlp_splits": [i64, i64, i32],
     "lkg_pair_mlp_select_f32": [i64, i64, vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp,
                                 vp],
+    "lkg_pair_mlp_prepare_f32": [i64, i64, vp, i64, vp, i64, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                 vp, vp],
+    "lkg_pair_mlp_count_f32": [i64, i64, vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp],
 }
 _RESTYPE = {"lkg_last_error": C.c_char_p, "lkg_csr_build_device_workspace": C.c_int64,
             "lkg_gemm_tall_workspace": C.c_int64, "lkg_gemm_workspace": C.c_int64,

@@ -1,5 +1,6 @@
 // The MLP pair head at inference (literalkg_amd/pairmlp.py): logits of every (query, candidate) pair, and the filtered
-// top-k of them per query, from the two PROJECTED tables of the head's first layer.
+// top-k of them per query, from the two PROJECTED tables of the head's first layer; and, further down, the filtered rank
+// counts of held-out pairs (prepare + count), which compare those logits instead of storing them.
 //
 // With BatchNorm in inference form folded forward the head is
 //     x1 = relu(u_q + v_c)                      u = Uq row (128, bias included), v = V row (128)
@@ -208,6 +209,161 @@ __global__ __launch_bounds__(PM_THREADS) void pair_mlp_select_kernel(
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Filtered ranking under the head (rank_pairs_mlp): the store kernel's loop with compares in place of the store, and the
+// "subtract, do not mask" filter correction of lkg_rank.hip (DESIGN.md sections 3.6a, 3.6d).
+
+constexpr int PM_PREP_WAVES = PM_THREADS / 64;   // queries per workgroup pass of the prepare kernel
+constexpr long PM_PREP_GRID = 1024;              // its workgroups at most: a wave keeps the weights for several queries
+constexpr long PM_COUNT_WGS = 4096;              // workgroups the count kernel aims for (16 per CU: a smooth tail) ...
+constexpr long PM_COUNT_MIN_TILES = 8;           // ... while each owns at least this many candidate tiles
+
+// One wave per query: thr[i] = z(i, truth[i]); better[i] / equal[i] = minus the filtered candidates (other than the truth,
+// inside the candidate set) that pair_mlp_count_kernel will count -- 0 without a filter.  Filter entries are entity ids;
+// slot maps them to rows of vt (NULL: the identity), -1 = not a candidate.
+__global__ __launch_bounds__(PM_THREADS) void pair_mlp_prepare_kernel(
+    long n_q, long n_c, const float *__restrict__ uq, long ldu, const float *__restrict__ vt, long ldv,
+    const float *__restrict__ w2, const float *__restrict__ b2, const float *__restrict__ w3,
+    const float *__restrict__ b3, const long *__restrict__ truth, long n_rows, const int *__restrict__ slot,
+    const long *__restrict__ frow, const long *__restrict__ frel, const int *__restrict__ rowptr,
+    const int *__restrict__ col, const int *__restrict__ eptr, const int *__restrict__ rel, float *__restrict__ thr,
+    int *__restrict__ better, int *__restrict__ equal) {
+    __shared__ __attribute__((aligned(16))) float su[PM_PREP_WAVES * PM_H1];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int r = lane & 15, s = lane >> 4;
+    PairWeights w;
+    pm_load_weights(w, w2, b2, w3, b3, r, s);
+    float *urow = su + wave * PM_H1;
+    for (long base = (long)blockIdx.x * PM_PREP_WAVES; base < n_q; base += (long)gridDim.x * PM_PREP_WAVES) {
+        const long i = base + wave;
+        const bool active = i < n_q;                      // (uniform in the wave; `base` is uniform in the workgroup)
+        __syncthreads();                                  // the previous pass has read its u rows
+        if (active && lane < PM_H1 / 4)
+            *reinterpret_cast<float4 *>(urow + 4 * lane) = *reinterpret_cast<const float4 *>(uq + i * ldu + 4 * lane);
+        __syncthreads();
+        if (!active) continue;
+        const long tr = min(max(truth[i], 0L), n_c - 1);
+        float4 vf[PM_H1 / 16];
+        float z[4];
+        pm_load_v(vf, vt + tr * ldv, s);                  // all 16 candidates are the truth
+        pm_pair_logits(z, urow, vf, w, s);
+        const float st = z[0];
+        int nb = 0, ne = 0;
+        if (rowptr) {
+            const long f = min(max(frow[i], 0L), n_rows - 1);
+            const int want = (int)frel[i];
+            const int e0 = rowptr[f], e1 = rowptr[f + 1];
+            for (int eb = e0; eb < e1; eb += 16) {        // 16 filter entries per pass (uniform trip count in the wave)
+                const int e = eb + r;
+                long c = tr;
+                bool keep = false;
+                if (e < e1) {
+                    const int id = col[e];
+                    long cs = -1;
+                    if (id >= 0 && id < n_rows) cs = slot ? slot[id] : id;
+                    if (cs >= 0 && cs < n_c && cs != tr) {
+                        c = cs;
+                        keep = want < 0;
+                        for (int x = eptr[e]; x < eptr[e + 1] && !keep; ++x) keep = rel[x] == want;
+                    }
+                }
+                pm_load_v(vf, vt + c * ldv, s);
+                pm_pair_logits(z, urow, vf, w, s);
+                const unsigned long long kept = __ballot(keep);          // bit r (of the lanes s = 0): candidate r is kept
+                const float zc = pm_pick(z, r);
+                const bool on = r < 4 && ((kept >> (4 * s + r)) & 1ull);
+                nb += __popcll(__ballot(on && zc > st));
+                ne += __popcll(__ballot(on && zc == st));
+            }
+        }
+        if (lane == 0) {
+            thr[i] = st;
+            better[i] = -nb;
+            equal[i] = -ne;
+        }
+    }
+}
+
+// better[i] += #{c != truth[i] : z(i, c) > thr[i]}, equal[i] += #{c != truth[i] : z(i, c) == thr[i]}: a workgroup owns 64
+// query rows and the candidate tiles of its split.  Lane qi of every wave keeps query qi's two counts over the wave's
+// candidates in registers; they meet in LDS and leave with one atomic per row, count and workgroup.
+__global__ __launch_bounds__(PM_THREADS) void pair_mlp_count_kernel(
+    long n_q, long n_c, const float *__restrict__ uq, long ldu, const float *__restrict__ vt, long ldv,
+    const float *__restrict__ w2, const float *__restrict__ b2, const float *__restrict__ w3,
+    const float *__restrict__ b3, const float *__restrict__ thr, const long *__restrict__ truth,
+    int *__restrict__ better, int *__restrict__ equal, long splits, long tiles_q, long tiles_c) {
+    __shared__ __attribute__((aligned(16))) float su[PM_ROWS * PM_H1];
+    __shared__ float sthr[PM_ROWS];
+    __shared__ int struth[PM_ROWS];
+    __shared__ int cnt[2][PM_ROWS];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int r = lane & 15, s = lane >> 4;
+    const long bid = blockIdx.x;
+    const long q0 = (bid % tiles_q) * PM_ROWS;
+    const long split = bid / tiles_q;
+    const long t_lo = split * tiles_c / splits, t_hi = (split + 1) * tiles_c / splits;
+    const int nq = (int)(n_q - q0 < PM_ROWS ? n_q - q0 : PM_ROWS);
+    if (tid < PM_ROWS) {
+        const bool in = tid < nq;
+        sthr[tid] = in ? thr[q0 + tid] : __builtin_nanf("");
+        struth[tid] = in ? (int)min(max(truth[q0 + tid], -1L), (long)INT_MAX) : -1;
+        cnt[0][tid] = 0;
+        cnt[1][tid] = 0;
+    }
+    pm_stage_u(su, uq, ldu, q0, nq);
+    PairWeights w;
+    pm_load_weights(w, w2, b2, w3, b3, r, s);
+    __syncthreads();
+    // the epilogue is kept free of branches and LDS traffic: lane qi holds query qi's threshold and truth (read with
+    // v_readlane, qi being uniform), and lane (r < 4, s) takes its candidate's logit z[r] through bit masks -- a lane that
+    // speaks for no candidate (r >= 4, or past the end) takes a NaN, which compares false both ways
+    const int my_thr = __float_as_int(sthr[lane]), my_truth = struth[lane];
+    int pick[4];
+#pragma unroll
+    for (int x = 0; x < 4; ++x) pick[x] = r == x ? -1 : 0;
+    int nb = 0, ne = 0;
+    for (long t = t_lo; t < t_hi; ++t) {
+        const long c0 = t * PM_COLS + wave * 16;
+        const long crow = c0 + r < n_c ? c0 + r : n_c - 1;        // rows past the end: computed, never counted
+        float4 vf[PM_H1 / 16];
+        pm_load_v(vf, vt + crow * ldv, s);
+        const long cw = c0 + 4 * s + (r & 3);
+        const int cwi = (int)cw;
+        const int none = (r < 4 && cw < n_c) ? 0 : 0x7fc00000;
+        for (int qi = 0; qi < nq; ++qi) {
+            float z[4];
+            pm_pair_logits(z, su + qi * PM_H1, vf, w, s);
+            const float tq = __int_as_float(__builtin_amdgcn_readlane(my_thr, qi));
+            const int tr = __builtin_amdgcn_readlane(my_truth, qi);
+            const float zc = __int_as_float((__float_as_int(z[0]) & pick[0]) | (__float_as_int(z[1]) & pick[1]) |
+                                            (__float_as_int(z[2]) & pick[2]) | (__float_as_int(z[3]) & pick[3]) | none);
+            const bool ok = cwi != tr;
+            const int b = __popcll(__ballot(ok && zc > tq)), e = __popcll(__ballot(ok && zc == tq));
+            nb += lane == qi ? b : 0;
+            ne += lane == qi ? e : 0;
+        }
+    }
+    if (lane < nq) {
+        if (nb) atomicAdd(&cnt[0][lane], nb);
+        if (ne) atomicAdd(&cnt[1][lane], ne);
+    }
+    __syncthreads();
+    if (tid < nq) {
+        if (cnt[0][tid]) atomicAdd(better + q0 + tid, cnt[0][tid]);
+        if (cnt[1][tid]) atomicAdd(equal + q0 + tid, cnt[1][tid]);
+    }
+}
+
+// candidate splits of the count kernel: enough workgroups for a smooth tail, each with a long run of tiles, and never
+// fewer than two workgroups per CU while there are tiles to hand out
+long pm_count_splits(long tiles_q, long tiles_c) {
+    const long fill = (2 * 256 + tiles_q - 1) / tiles_q, many = (PM_COUNT_WGS + tiles_q - 1) / tiles_q;
+    long s_ = tiles_c / PM_COUNT_MIN_TILES < many ? tiles_c / PM_COUNT_MIN_TILES : many;
+    s_ = s_ > fill ? s_ : fill;
+    s_ = s_ < tiles_c ? s_ : tiles_c;
+    return s_ > 1 ? s_ : 1;
+}
+
 // query rows per workgroup of the select kernel: fewer for small batches, so that the splits (at most 64) fill the chip
 long pm_select_rows(long n_q) { return n_q >= 512 ? 64 : n_q >= 128 ? 32 : 16; }
 
@@ -278,6 +434,52 @@ extern "C" int lkg_pair_mlp_select_f32(int64_t n_q, int64_t n_cand, const float 
     else LKG_PM_LAUNCH(128);
 #undef LKG_PM_LAUNCH
     LKG_CHECK_LAUNCH("lkg_pair_mlp_select_f32");
+    return LKG_OK;
+}
+
+extern "C" int lkg_pair_mlp_prepare_f32(int64_t n_q, int64_t n_cand, const float *uq, int64_t ldu, const float *v,
+                                        int64_t ldv, const float *w2, const float *b2, const float *w3, const float *b3,
+                                        const int64_t *truth, int64_t n_rows, const int32_t *cand_slot,
+                                        const int64_t *filter_row, const int64_t *filter_rel, const int32_t *rowptr,
+                                        const int32_t *col, const int32_t *eptr, const int32_t *rel, float *thr,
+                                        int32_t *better, int32_t *equal, void *stream) {
+    LKG_REQUIRE(n_q >= 0 && n_cand > 0 && n_cand < INT32_MAX, "lkg_pair_mlp_prepare_f32: bad sizes");
+    if (n_q == 0) return LKG_OK;
+    LKG_REQUIRE(uq && v && w2 && b2 && w3 && b3 && truth && thr && better && equal,
+                "lkg_pair_mlp_prepare_f32: null pointer");
+    LKG_REQUIRE(pm_operands_ok(uq, ldu, v, ldv, w2),
+                "lkg_pair_mlp_prepare_f32: uq, v and w2 must be 16-byte aligned with row strides that are multiples of 4 "
+                "(at least 128)");
+    LKG_REQUIRE(!rowptr || (filter_row && filter_rel && col && eptr && rel), "lkg_pair_mlp_prepare_f32: incomplete filter");
+    LKG_REQUIRE(!rowptr || (n_rows > 0 && n_rows < INT32_MAX && (cand_slot || n_rows == n_cand)),
+                "lkg_pair_mlp_prepare_f32: the filter's rows must be the candidates, or come with cand_slot");
+    const long blocks = (n_q + PM_PREP_WAVES - 1) / PM_PREP_WAVES;
+    hipLaunchKernelGGL(pair_mlp_prepare_kernel, dim3((unsigned)(blocks < PM_PREP_GRID ? blocks : PM_PREP_GRID)),
+                       dim3(PM_THREADS), 0, (hipStream_t)stream, (long)n_q, (long)n_cand, uq, (long)ldu, v, (long)ldv, w2,
+                       b2, w3, b3, (const long *)truth, (long)n_rows, cand_slot, (const long *)filter_row,
+                       (const long *)filter_rel, rowptr, col, eptr, rel, thr, better, equal);
+    LKG_CHECK_LAUNCH("lkg_pair_mlp_prepare_f32");
+    return LKG_OK;
+}
+
+extern "C" int lkg_pair_mlp_count_f32(int64_t n_q, int64_t n_cand, const float *uq, int64_t ldu, const float *v,
+                                      int64_t ldv, const float *w2, const float *b2, const float *w3, const float *b3,
+                                      const float *thr, const int64_t *truth, int32_t *better, int32_t *equal,
+                                      void *stream) {
+    LKG_REQUIRE(n_q >= 0 && n_cand >= 0 && n_cand < INT32_MAX, "lkg_pair_mlp_count_f32: bad sizes");
+    if (n_q == 0 || n_cand == 0) return LKG_OK;
+    LKG_REQUIRE(uq && v && w2 && b2 && w3 && b3 && thr && truth && better && equal,
+                "lkg_pair_mlp_count_f32: null pointer");
+    LKG_REQUIRE(pm_operands_ok(uq, ldu, v, ldv, w2),
+                "lkg_pair_mlp_count_f32: uq, v and w2 must be 16-byte aligned with row strides that are multiples of 4 "
+                "(at least 128)");
+    const long tiles_q = (n_q + PM_ROWS - 1) / PM_ROWS, tiles_c = (n_cand + PM_COLS - 1) / PM_COLS;
+    const long splits = pm_count_splits(tiles_q, tiles_c);
+    LKG_REQUIRE(tiles_q * splits < INT32_MAX, "lkg_pair_mlp_count_f32: too many workgroups (split the queries)");
+    hipLaunchKernelGGL(pair_mlp_count_kernel, dim3((unsigned)(tiles_q * splits)), dim3(PM_THREADS), 0,
+                       (hipStream_t)stream, (long)n_q, (long)n_cand, uq, (long)ldu, v, (long)ldv, w2, b2, w3, b3, thr,
+                       (const long *)truth, better, equal, splits, tiles_q, tiles_c);
+    LKG_CHECK_LAUNCH("lkg_pair_mlp_count_f32");
     return LKG_OK;
 }
 

@@ -711,6 +711,14 @@ class LiteralKG(nn.Module):
         from .pairmlp import mlp_scores
         return mlp_scores(self, head_ids, tail_ids, logits=logits)
 
+    def rank_pairs(self, h, t, r=None, side: str = "tail", known=None, candidates=None,
+                   batch_size: Optional[int] = None):
+        """Filtered ranks of the pairs (h, t) under the MLP pair head on the inference table (literalkg_amd/pairmlp.py,
+        rank_pairs_mlp): side 'tail' / 'head' / 'both', r the pairs' relations for the filter (None: any relation), known
+        a ranking.KnownTriples filter, candidates an optional subset of entity ids.  Returns a ranking.RankResult."""
+        from .pairmlp import rank_pairs_mlp
+        return rank_pairs_mlp(self, h, t, r=r, side=side, known=known, candidates=candidates, batch_size=batch_size)
+
     def initialize_MLP(self):
         """The pair-classification head of model.py:499-504 (same module names, so checkpoints interchange)."""
         self.fc1 = nn.Linear(self.scale_gat_dim * 2, 128)

@@ -2383,3 +2383,62 @@ def pair_mlp_topk(uq: torch.Tensor, v: torch.Tensor, w2: torch.Tensor, b2: torch
         N.call("lkg_topk_merge_f32", m, k, s_, N.ptr(ws_s), N.ptr(ws_i), None, N.ptr(ids[lo:hi]), N.ptr(scores[lo:hi]),
                N.ptr(logits[lo:hi]), _stream())
     return ids, logits
+
+
+def pair_mlp_cand_slot(n_rows: int, cand_ids: torch.Tensor) -> torch.Tensor:
+    """int32[n_rows]: the candidate row of every entity id, -1 for an id that is not among cand_ids (ids outside [0, n_rows)
+    are in no known triple and get no slot)."""
+    _need_gpu(cand_ids)
+    cand_ids = _i64(cand_ids.reshape(-1))
+    slot = torch.full((int(n_rows),), -1, dtype=torch.int32, device=cand_ids.device)
+    inside = (cand_ids >= 0) & (cand_ids < n_rows)
+    slot[cand_ids[inside]] = torch.arange(cand_ids.numel(), dtype=torch.int32, device=cand_ids.device)[inside]
+    return slot
+
+
+def pair_mlp_rank_count(uq: torch.Tensor, v: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor, w3: torch.Tensor,
+                        b3: torch.Tensor, truth_rows: torch.Tensor, filt=None, filter_row: Optional[torch.Tensor] = None,
+                        filter_rel: Optional[torch.Tensor] = None, cand_ids: Optional[torch.Tensor] = None,
+                        cand_slot: Optional[torch.Tensor] = None):
+    """(better, equal, thr) int32 / int32 / f32 per query row of uq against every candidate row of v under the logit of
+    pair_mlp_scores -- the same bits, higher is better: thr[i] = z(i, truth_rows[i]), better / equal the candidates other
+    than the truth strictly above / exactly at it; the n_q x n_c logits are never stored (lkg_pair_mlp_prepare_f32, then
+    lkg_pair_mlp_count_f32).  truth_rows are rows of v.  filt = (rowptr, col, eptr, rel) of csr_build_device over entity
+    ids; query i leaves out the cols of row filter_row[i] under relation filter_rel[i] (-1: under any).  cand_ids: the
+    (unique) entity id of every row of v (None: the row number); filter entries outside them are not candidates.  cand_slot: pair_mlp_cand_slot of
+    cand_ids, for a caller that counts batch after batch against the same candidates."""
+    _need_gpu(truth_rows, filter_row, filter_rel, cand_ids, cand_slot)
+    uq, v, w2, b2, w3, b3 = _pair_mlp_operands("pair_mlp_rank_count", uq, v, w2, b2, w3, b3)
+    n_q, n_c = uq.shape[0], v.shape[0]
+    truth_rows = _i64(truth_rows.reshape(-1))
+    if truth_rows.numel() != n_q:
+        raise ValueError(f"pair_mlp_rank_count: {truth_rows.numel()} truths for {n_q} queries")
+    if cand_ids is not None and cand_ids.numel() != n_c:
+        raise ValueError(f"pair_mlp_rank_count: {cand_ids.numel()} candidate ids for {n_c} candidate rows")
+    if n_q > 0 and n_c == 0:
+        raise ValueError("pair_mlp_rank_count: no candidates")
+    dev = uq.device
+    better = torch.zeros(n_q, dtype=torch.int32, device=dev)
+    equal = torch.zeros(n_q, dtype=torch.int32, device=dev)
+    thr = torch.empty(n_q, dtype=torch.float32, device=dev)
+    if n_q == 0:
+        return better, equal, thr
+    n_rows, slot, fargs = n_c, None, [None] * 6
+    if filt is not None:
+        rowptr, col, eptr, rel = filt
+        n_rows = rowptr.numel() - 1
+        if cand_ids is None and n_rows != n_c:
+            raise ValueError(f"pair_mlp_rank_count: the filter covers {n_rows} rows, the candidates {n_c}")
+        filter_row, filter_rel = _i64(filter_row.reshape(-1)), _i64(filter_rel.reshape(-1))
+        if filter_row.numel() != n_q or filter_rel.numel() != n_q:
+            raise ValueError(f"pair_mlp_rank_count: {filter_row.numel()} filter rows for {n_q} queries")
+        if cand_ids is not None:
+            slot = cand_slot if cand_slot is not None else pair_mlp_cand_slot(n_rows, cand_ids)
+            if slot.numel() != n_rows or slot.dtype != torch.int32 or not slot.is_contiguous():
+                raise ValueError(f"pair_mlp_rank_count: cand_slot must be a contiguous int32[{n_rows}]")
+        fargs = [N.ptr(filter_row), N.ptr(filter_rel), N.ptr(rowptr), N.ptr(col), N.ptr(eptr), N.ptr(rel)]
+    N.call("lkg_pair_mlp_prepare_f32", n_q, n_c, N.ptr(uq), _ld(uq), N.ptr(v), _ld(v), N.ptr(w2), N.ptr(b2), N.ptr(w3),
+           N.ptr(b3), N.ptr(truth_rows), n_rows, N.ptr(slot), *fargs, N.ptr(thr), N.ptr(better), N.ptr(equal), _stream())
+    N.call("lkg_pair_mlp_count_f32", n_q, n_c, N.ptr(uq), _ld(uq), N.ptr(v), _ld(v), N.ptr(w2), N.ptr(b2), N.ptr(w3),
+           N.ptr(b3), N.ptr(thr), N.ptr(truth_rows), N.ptr(better), N.ptr(equal), _stream())
+    return better, equal, thr

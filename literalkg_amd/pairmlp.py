@@ -1,5 +1,6 @@
-"""The MLP pair head at inference: all-pairs logits (``mlp_scores``, the MLP counterpart of ``calc_score``) and the
-backend of ``predict_topk(scoring="mlp")``.
+"""The MLP pair head at inference: all-pairs logits (``mlp_scores``, the MLP counterpart of ``calc_score``), the backend
+of ``predict_topk(scoring="mlp")``, and filtered ranking of held-out pairs under the head (``rank_pairs_mlp``,
+``evaluate_mlp_ranking``).
 
 The head of mode='mlp' is sigmoid(fc3(bn2(relu(fc2(bn1(relu(fc1([e_h | e_t])))))))).  At inference BatchNorm is affine per
 feature, bn(x) = a x + c with a = gamma / sqrt(running_var + eps), c = beta - running_mean a, and since ReLU comes
@@ -23,11 +24,12 @@ buffers and caches are left as they are.
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import Optional
+from typing import Dict, Optional, Sequence
 
 import torch
 
 from . import ops
+from .ranking import KnownTriples, RankResult, _check_ks, _check_side, metrics_from_counts, realistic_rank
 
 _SIGMOID_CHUNK = 1 << 24      # elements per float64 temporary of _sigmoid_
 
@@ -165,3 +167,108 @@ def predict_topk_mlp(model, head: FoldedMLPHead, ids, r, side, k, filt, cand, ba
             out_ids[lo:hi] = ii
             out_z[lo:hi] = zz
         return out_ids, _sigmoid_(out_z.clone()), out_z
+
+
+def rank_pairs_mlp(model, h: torch.Tensor, t: torch.Tensor, r: Optional[torch.Tensor] = None, side: str = "tail",
+                   known: Optional[KnownTriples] = None, candidates: Optional[torch.Tensor] = None,
+                   batch_size: Optional[int] = None) -> RankResult:
+    """Filtered ranks of the pairs (h, t) under the MLP pair head on the model's inference table (see the module
+    docstring): side 'tail' / 'head' / 'both' (2 x B: row 0 the tail side, row 1 the head side).  r: the relation of every
+    pair for the filter (None: a pair known under any relation is dropped).  candidates: optional 1-D tensor of unique
+    entity ids to rank among -- every truth must be one of them; one side only.  batch_size: queries per launch (None:
+    all); it does not change the result.  The model's mode, parameters, buffers and caches are left as they are."""
+    side = _check_side(side)
+    _check_ids("h", h)
+    _check_ids("t", t)
+    if h.numel() != t.numel():
+        raise ValueError(f"h and t have different lengths ({h.numel()}, {t.numel()})")
+    if r is not None:
+        _check_ids("r", r)
+        if r.numel() != h.numel():
+            raise ValueError(f"h and r have different lengths ({h.numel()}, {r.numel()})")
+    if candidates is not None:
+        _check_ids("candidates", candidates)
+        if side == "both":
+            raise ValueError("candidates go with side='tail' or side='head': the two sides of 'both' would need two sets")
+        if torch.unique(candidates).numel() != candidates.numel():
+            raise ValueError("candidates must be unique entity ids")
+        truth = t if side == "tail" else h
+        missing = int((~torch.isin(truth.to(candidates.device), candidates)).sum())
+        if missing:
+            raise ValueError(f"{missing} of the {truth.numel()} true {'tails' if side == 'tail' else 'heads'} are not among "
+                             "the candidates")
+    if batch_size is not None and (isinstance(batch_size, bool) or int(batch_size) != batch_size or batch_size <= 0):
+        raise ValueError(f"batch_size must be a positive integer, got {batch_size!r}")
+    if known is not None and known.n_entities != model.n_entities:
+        raise ValueError(f"known triples over {known.n_entities} entities, the model has {model.n_entities}")
+    head = fold_mlp_head(model)                          # (AttributeError without initialize_MLP)
+    dev = model.entity_embed.weight.device
+    if known is not None and known.device != dev:
+        raise ValueError(f"known triples live on {known.device}, the model on {dev}")
+    sides = ("tail", "head") if side == "both" else (side,)
+    b = h.numel()
+    if b == 0:
+        z = torch.zeros((len(sides), 0) if side == "both" else (0,), dtype=torch.int64, device=dev)
+        return RankResult(z, z.clone(), z.double(), side)
+    h, t = ops.checked_ids(model.n_entities, h.to(dev), t.to(dev))
+    if r is not None:
+        (r,) = ops.checked_ids(model.n_relations, r.to(dev), what="relation")
+    cand = None
+    if candidates is not None:
+        (cand,) = ops.checked_ids(model.n_entities, candidates.to(dev), what="candidate entity")
+    ops.check_deferred_errors()
+    model.device = dev
+    with torch.no_grad():
+        table = model._table_for_inference().detach()
+        _table_width_ok(head, table)
+        crows = table if cand is None else ops.gather_rows(table, cand)
+        slot = ops.pair_mlp_cand_slot(model.n_entities, cand) if cand is not None else None
+        frel = r if r is not None else torch.full((b,), -1, dtype=torch.int64, device=dev)
+        better = torch.empty((len(sides), b), dtype=torch.int32, device=dev)
+        equal = torch.empty((len(sides), b), dtype=torch.int32, device=dev)
+        step = b if batch_size is None else int(batch_size)
+        for j, s_ in enumerate(sides):
+            q_ids, truth = (h, t) if s_ == "tail" else (t, h)
+            qrows = ops.gather_rows(table, q_ids)
+            if s_ == "tail":                 # pairs (query, c): the query in fc1's head half, with the bias
+                uq, v = _project(qrows, head.w1h, head.b1), _project(crows, head.w1t)
+            else:                            # pairs (c, query): the candidates in the head half, with the bias
+                uq, v = _project(qrows, head.w1t), _project(crows, head.w1h, head.b1)
+            del qrows
+            filt = known.for_side(s_) if known is not None else None
+            truth_rows = truth if slot is None else slot[truth].long()
+            for lo in range(0, b, step):
+                hi = min(lo + step, b)
+                bb, ee, _ = ops.pair_mlp_rank_count(uq[lo:hi], v, head.w2, head.b2, head.w3, head.b3, truth_rows[lo:hi],
+                                                    filt, q_ids[lo:hi], frel[lo:hi], cand, slot)
+                better[j, lo:hi] = bb
+                equal[j, lo:hi] = ee
+            del uq, v
+    better, equal = better.long(), equal.long()
+    if side != "both":
+        better, equal = better[0], equal[0]
+    return RankResult(better, equal, realistic_rank(better, equal), side)
+
+
+def evaluate_mlp_ranking(model, h: torch.Tensor, t: torch.Tensor, r: Optional[torch.Tensor] = None,
+                         known: Optional[KnownTriples] = None, ks: Sequence[int] = (1, 3, 10), side: str = "both",
+                         candidates: Optional[torch.Tensor] = None, batch_size: Optional[int] = None) -> Dict:
+    """{'mr', 'mrr', 'hits@k'..., 'n', 'tail': {...}, 'head': {...}}: filtered ranking metrics of the pairs under the MLP
+    pair head (rank_pairs_mlp, ranking.metrics_from_counts); the top level is over every rank computed (2B for
+    side='both').  Runs in eval mode, as evaluate_ranking does, and restores the model's previous mode."""
+    ks = _check_ks(ks)
+    side = _check_side(side)
+    was_training = model.training
+    model.eval()
+    try:
+        res = rank_pairs_mlp(model, h, t, r=r, side=side, known=known, candidates=candidates, batch_size=batch_size)
+    finally:
+        model.train(was_training)
+    better, equal = res.better.cpu(), res.equal.cpu()
+    out = metrics_from_counts(better, equal, ks)
+    if side == "both":
+        out["tail"] = metrics_from_counts(better[0], equal[0], ks)
+        out["head"] = metrics_from_counts(better[1], equal[1], ks)
+    else:
+        out[side] = metrics_from_counts(better, equal, ks)
+    return out
