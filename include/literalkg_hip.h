@@ -159,7 +159,8 @@ int lkg_spmm_csr_f32(int64_t n_rows, int32_t d, const int32_t *rowptr, const int
  *   rowmax_out         float[n_rows] (cleared here): max |out[i,:]| -- the row scale the tall GEMM of the layer's
  *                      Linear needs of its input (lkg_gemm_tall_f32), produced while the row is in registers;
  *   x_rows, self_rows  (nullable, uint8 per row of x / of self) a zero byte promises that the row is all zero: its
- *                      entries are skipped without touching x (16-byte path; otherwise ignored).  The backward of the
+ *                      entries are skipped without touching x (on the scalar path too: an unflagged row may hold
+ *                      anything, it is not read).  The backward of the
  *                      LAST aggregation layer: the loss's gradient reaches <= 3B of the N rows, so all but a fraction
  *                      of a percent of the transpose SpMM's gathers would fetch zeros;
  *   out_rows           (nullable, uint8[n_rows], cleared here; needs x_rows and the 16-byte path, d <= 1024) receives 1

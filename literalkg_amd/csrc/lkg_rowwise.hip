@@ -1052,11 +1052,16 @@ extern "C" int lkg_adam_step_f32(int64_t n, float *param, const float *grad, flo
 // A workgroup owns 64 columns; its four waves stride over the rows (coalesced 256-B row segments) and meet in
 // LDS for the column statistics.  Training mode uses batch statistics (biased variance for the output, unbiased
 // for the running estimate, like nn.BatchNorm1d) and updates the running buffers; eval mode uses the buffers.
+// The column sums (mean, variance, g_gamma, g_beta) are ACCUMULATED IN FLOAT64 and rounded to float32 once: each of the four
+// waves walks n / 4 rows of its column in one chain, and a float32 chain of 2 000 same-sign terms (n = 8 195, a column with
+// a common offset) lost 5e-7 .. 8e-7 of the mean and 2e-6 of 1 / std -- several times torch's blocked sums
+// (tests/test_rowwise_conditioning_gpu.py::test_relu_batchnorm).  The kernel is bound by its one workgroup per 64 columns
+// reading n rows; the float64 adds do not show.
 namespace {
-__device__ __forceinline__ float col_reduce4(float v, float (*sm)[64], int g, int c) {
+__device__ __forceinline__ double col_reduce4(double v, double (*sm)[64], int g, int c) {
     sm[g][c] = v;
     __syncthreads();
-    const float r = (sm[0][c] + sm[1][c]) + (sm[2][c] + sm[3][c]);
+    const double r = (sm[0][c] + sm[1][c]) + (sm[2][c] + sm[3][c]);
     __syncthreads();
     return r;
 }
@@ -1068,20 +1073,20 @@ __global__ __launch_bounds__(256) void relu_bn_fwd_kernel(long n, int d, const f
                                                            float *__restrict__ running_var, float *__restrict__ y,
                                                            long ldy, float *__restrict__ save_mean,
                                                            float *__restrict__ save_invstd) {
-    __shared__ float sm[4][64];
+    __shared__ double sm[4][64];
     const int c = blockIdx.x * 64 + (threadIdx.x & 63), g = threadIdx.x >> 6, lc = threadIdx.x & 63;
     const bool ok = c < d;
     float mean, invstd;
     if (training) {
-        float s = 0.f;
-        for (long r = g; r < n; r += 4) s += ok ? fmaxf(z[r * ldz + c], 0.f) : 0.f;
-        mean = col_reduce4(s, sm, g, lc) / (float)n;
-        float q = 0.f;
+        double s = 0.0;
+        for (long r = g; r < n; r += 4) s += ok ? (double)fmaxf(z[r * ldz + c], 0.f) : 0.0;
+        mean = (float)(col_reduce4(s, sm, g, lc) / (double)n);
+        double q = 0.0;
         for (long r = g; r < n; r += 4) {
-            const float a = ok ? fmaxf(z[r * ldz + c], 0.f) - mean : 0.f;
-            q = fmaf(a, a, q);
+            const double a = ok ? (double)(fmaxf(z[r * ldz + c], 0.f) - mean) : 0.0;
+            q = fma(a, a, q);
         }
-        const float var = col_reduce4(q, sm, g, lc) / (float)n;
+        const float var = (float)(col_reduce4(q, sm, g, lc) / (double)n);
         invstd = 1.f / sqrtf(var + eps);
         if (ok && g == 0) {
             running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * mean;
@@ -1107,19 +1112,19 @@ __global__ __launch_bounds__(256) void relu_bn_bwd_kernel(long n, int d, const f
                                                            const float *__restrict__ g_y, long ldgy,
                                                            float *__restrict__ g_z, long ldgz,
                                                            float *__restrict__ g_gamma, float *__restrict__ g_beta) {
-    __shared__ float sm[4][64];
+    __shared__ double sm[4][64];
     const int c = blockIdx.x * 64 + (threadIdx.x & 63), g = threadIdx.x >> 6, lc = threadIdx.x & 63;
     const bool ok = c < d;
     const float mean = ok ? save_mean[c] : 0.f, invstd = ok ? save_invstd[c] : 0.f, ga = ok ? gamma[c] : 0.f;
-    float s1 = 0.f, s2 = 0.f;
+    double a1 = 0.0, a2 = 0.0;
     for (long r = g; r < n; r += 4) {
         const float dy = ok ? g_y[r * ldgy + c] : 0.f;
         const float xh = ok ? (fmaxf(z[r * ldz + c], 0.f) - mean) * invstd : 0.f;
-        s1 += dy;
-        s2 = fmaf(dy, xh, s2);
+        a1 += (double)dy;
+        a2 = fma((double)dy, (double)xh, a2);
     }
-    s1 = col_reduce4(s1, sm, g, lc);
-    s2 = col_reduce4(s2, sm, g, lc);
+    const float s1 = (float)col_reduce4(a1, sm, g, lc);
+    const float s2 = (float)col_reduce4(a2, sm, g, lc);
     if (ok && g == 0) {
         g_beta[c] = s1;
         g_gamma[c] = s2;

@@ -579,14 +579,13 @@ int launch(int64_t n_rows, int nchunk, const int *rowptr, const int *col, const 
     const int64_t blocks = ((ex.row_list ? (int64_t)ex.n_list : n_rows) + 3) / 4 + n_long;
     LKG_REQUIRE(blocks * n_slabs * 256 < (int64_t)UINT32_MAX, "lkg_spmm_csr_f32: grid too large (%lld workgroups)",
                 (long long)(blocks * n_slabs));
-    if constexpr (std::is_same<V, float4>::value) {
-        if (ex.x_rows) {
-            hipLaunchKernelGGL((spmm_csr_kernel<V, LPE, CPL, U, FULL, true>), dim3((unsigned)(blocks * n_slabs)), dim3(256), 0,
-                               s, (int)n_rows, nchunk, rowptr, col, val, x, (long)ldx, out, (long)ldo, self,
-                               (long)ld_self, long_rows, n_long, long_thresh, (int)blocks, slab_cols, ex);
-            LKG_CHECK_LAUNCH("lkg_spmm_csr_f32");
-            return LKG_OK;
-        }
+    // (the scalar path too: x_rows promises that the unflagged rows of x are not READ -- they may hold anything)
+    if (ex.x_rows) {
+        hipLaunchKernelGGL((spmm_csr_kernel<V, LPE, CPL, U, FULL, true>), dim3((unsigned)(blocks * n_slabs)), dim3(256), 0,
+                           s, (int)n_rows, nchunk, rowptr, col, val, x, (long)ldx, out, (long)ldo, self,
+                           (long)ld_self, long_rows, n_long, long_thresh, (int)blocks, slab_cols, ex);
+        LKG_CHECK_LAUNCH("lkg_spmm_csr_f32");
+        return LKG_OK;
     }
     hipLaunchKernelGGL((spmm_csr_kernel<V, LPE, CPL, U, FULL, false>), dim3((unsigned)(blocks * n_slabs)), dim3(256), 0, s,
                        (int)n_rows, nchunk, rowptr, col, val, x, (long)ldx, out, (long)ldo, self, (long)ld_self,

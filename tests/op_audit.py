@@ -66,6 +66,419 @@ def bound_for(engine: str, r_torch32: float, k: int = 0) -> float:
     return max(f * r_torch32, floor, chain_term(engine, k))
 
 
+# ------------------------------------------------------------------------------- row-wise, sparse and grouped families
+# Plain references of the kernels outside the GEMM engines (test_rowwise_conditioning_gpu.py on the device,
+# test_rowwise_measures_host.py for the measures themselves).  Each is a function of the float32 inputs only, works on CPU
+# and GPU tensors alike, and comes as  X_eval(..., dtype)  -- the expression evaluated in ``dtype`` (torch.float64: the
+# reference; torch.float32: torch's own float32 evaluation, the r_torch32 of the bound) -- and  X_scale(...)  -- the sum of
+# the absolute values of the terms of the float64 expression, per output element.
+def f32(x: float) -> float:
+    """the float32 a kernel receives when it is handed the Python float x"""
+    return float(torch.tensor(x, dtype=torch.float32))
+
+
+def leaky(x: torch.Tensor, slope: float) -> torch.Tensor:
+    return torch.where(x > 0, x, x * slope)
+
+
+def units(n: int) -> float:
+    """n roundings of float32, each at most 2^-24 of the scale, with their second-order product"""
+    return n * U * (1.0 + n * U)
+
+
+def within_units(got, want64, scale64, n_units: float, extra=None):
+    """(worst |err| / allowance, flat index) with allowance = n_units 2^-24 scale (+ extra, an absolute per-element term)"""
+    allow = units(n_units) * scale64 + (extra if extra is not None else 0.0) + TINY
+    q = (got.double() - want64).abs() / allow
+    q = torch.nan_to_num(q, nan=math.inf)
+    i = int(q.argmax()) if q.numel() else 0
+    return (float(q.reshape(-1)[i]) if q.numel() else 0.0), i
+
+
+# allowances of the kept activations (the gate epilogue's, above): absolute error of tanh_fast / sigmoid_fast
+def tanh_allow(t64):
+    return 4e-7 * (1 + t64.abs())
+
+
+def sigmoid_allow(s64):
+    return 2e-6 * (1 + s64.abs())
+
+
+# ---- grouped GEMM (lkg_grouped_gemm_f32)
+def grouped_blocks(mode, seg, a, b, trans_b, b_period):
+    """[(group, row slice, A operand [m, k], B operand [k, n])] in math layout, float32 views"""
+    sg = [int(v) for v in seg.tolist()]
+    out = []
+    for g in range(len(sg) - 1):
+        lo_, hi_ = sg[g], sg[g + 1]
+        if mode == 1:
+            blk = b[g % b_period if b_period > 0 else g] if b.dim() == 3 else b
+            out.append((g, slice(lo_, hi_), a[lo_:hi_], blk.t() if trans_b else blk))
+        else:
+            out.append((g, slice(lo_, hi_), a[lo_:hi_].t(), b[lo_:hi_]))
+    return out
+
+
+def grouped_eval(mode, seg, a, b, c0, beta, trans_b, b_period, dtype):
+    """rows mode: {group: C rows of the segment}; k mode: {group: C block}.  c0: C before the call (rows mode: the whole
+    [M, n] view; k mode: [G, m, n]) or None with beta = 0."""
+    res = {}
+    for g, rows, am, bm in grouped_blocks(mode, seg, a, b, trans_b, b_period):
+        v = am.to(dtype) @ bm.to(dtype)
+        if beta != 0.0:
+            v = v + beta * (c0[rows] if mode == 1 else c0[g]).to(dtype)
+        res[g] = v
+    return res
+
+
+def grouped_scale(mode, seg, a, b, c0, beta, trans_b, b_period):
+    res = {}
+    for g, rows, am, bm in grouped_blocks(mode, seg, a, b, trans_b, b_period):
+        v = am.double().abs() @ bm.double().abs()
+        if beta != 0.0:
+            v = v + abs(beta) * (c0[rows] if mode == 1 else c0[g]).double().abs()
+        res[g] = v
+    return res
+
+
+# ---- LeakyReLU + LayerNorm + normalised copy (lkg_act_layernorm_*), BatchNorm(ReLU) (lkg_relu_batchnorm_*)
+def layernorm_fwd_eval(z, gamma, beta, slope, eps, norm_eps, dtype, mean_over=None):
+    """{mean, rstd, y, yn}.  mean_over: a planted fault for the host test (the row mean taken over that many elements)."""
+    a = leaky(z.to(dtype), slope)
+    d = a.shape[1]
+    mean = a.sum(1) / (mean_over or d)
+    c = a - mean[:, None]
+    rstd = 1.0 / torch.sqrt((c * c).sum(1) / d + eps)
+    y = c * rstd[:, None] * gamma.to(dtype) + beta.to(dtype)
+    nrm = torch.sqrt((y * y).sum(1))
+    yn = y / nrm.clamp_min(norm_eps)[:, None]
+    return dict(mean=mean, rstd=rstd, y=y, yn=yn)
+
+
+def layernorm_fwd_scale(z, gamma, beta, slope, eps, norm_eps):
+    w = layernorm_fwd_eval(z, gamma, beta, slope, eps, norm_eps, torch.float64)
+    a = leaky(z.double(), slope).abs()
+    ma = a.mean(1)
+    sy = (a + ma[:, None]) * w["rstd"][:, None] * gamma.double().abs() + beta.double().abs()
+    nrm = torch.sqrt((w["y"] * w["y"]).sum(1)).clamp_min(norm_eps)
+    return dict(mean=ma, rstd=w["rstd"], y=sy, yn=sy / nrm[:, None])
+
+
+def _ln_upstream(y, gy, gyn, norm_eps, dtype):
+    """G = g_y + d(yn)/dy applied to g_yn, and the |.|-sum of its terms"""
+    g = torch.zeros_like(y, dtype=dtype) if gy is None else gy.to(dtype)
+    ag = g.abs()
+    if gyn is not None:
+        yy, gn = y.to(dtype), gyn.to(dtype)
+        nrm = torch.sqrt((yy * yy).sum(1, keepdim=True))
+        big = nrm > norm_eps
+        inv = 1.0 / torch.where(big, nrm, torch.full_like(nrm, norm_eps))
+        dot = (yy * gn).sum(1, keepdim=True)
+        adot = (yy * gn).abs().sum(1, keepdim=True)
+        g = g + gn * inv - torch.where(big, yy * dot * inv ** 3, torch.zeros_like(yy))
+        ag = ag + gn.abs() * inv + torch.where(big, yy.abs() * adot * inv ** 3, torch.zeros_like(yy))
+    return g, ag
+
+
+def layernorm_bwd_eval(z, gamma, mean, rstd, y, gy, gyn, slope, norm_eps, dtype):
+    """{gz, g_gamma, g_beta} from the backward kernel's own float32 inputs (z, gamma, the saved mean / rstd / y, g_y, g_yn)"""
+    zz = z.to(dtype)
+    xh = (leaky(zz, slope) - mean.to(dtype)[:, None]) * rstd.to(dtype)[:, None]
+    g, _ = _ln_upstream(y, gy, gyn, norm_eps, dtype)
+    dxh = g * gamma.to(dtype)
+    da = rstd.to(dtype)[:, None] * (dxh - dxh.mean(1, keepdim=True) - xh * (dxh * xh).mean(1, keepdim=True))
+    gz = da * torch.where(zz > 0, torch.ones_like(zz), torch.full_like(zz, slope))
+    return dict(gz=gz, g_gamma=(g * xh).sum(0), g_beta=g.sum(0))
+
+
+def layernorm_bwd_scale(z, gamma, mean, rstd, y, gy, gyn, slope, norm_eps):
+    zz = z.double()
+    xh = ((leaky(zz, slope) - mean.double()[:, None]) * rstd.double()[:, None]).abs()
+    _, ag = _ln_upstream(y, gy, gyn, norm_eps, torch.float64)
+    adx = ag * gamma.double().abs()
+    gz = rstd.double()[:, None] * (adx + adx.mean(1, keepdim=True) + xh * (adx * xh).mean(1, keepdim=True))
+    gz = gz * torch.where(zz > 0, torch.ones_like(zz), torch.full_like(zz, slope))
+    return dict(gz=gz, g_gamma=(ag * xh).sum(0), g_beta=ag.sum(0))
+
+
+def batchnorm_fwd_eval(z, gamma, beta, run_mean, run_var, training, momentum, eps, dtype, mean_over=None):
+    """{mean, invstd, y, run_mean, run_var} of BatchNorm1d(relu(z)) (the running buffers after the step; unbiased variance)"""
+    a = torch.relu(z.to(dtype))
+    n = a.shape[0]
+    if training:
+        mean = a.sum(0) / (mean_over or n)
+        var = ((a - mean) ** 2).sum(0) / n
+        new_mean = (1 - momentum) * run_mean.to(dtype) + momentum * mean
+        new_var = (1 - momentum) * run_var.to(dtype) + momentum * var * (n / max(n - 1, 1))
+    else:
+        mean, var = run_mean.to(dtype), run_var.to(dtype)
+        new_mean, new_var = mean, var
+    invstd = 1.0 / torch.sqrt(var + eps)
+    y = (a - mean) * invstd * gamma.to(dtype) + beta.to(dtype)
+    return dict(mean=mean, invstd=invstd, y=y, run_mean=new_mean, run_var=new_var)
+
+
+def batchnorm_fwd_scale(z, gamma, beta, run_mean, run_var, training, momentum, eps):
+    w = batchnorm_fwd_eval(z, gamma, beta, run_mean, run_var, training, momentum, eps, torch.float64)
+    a = torch.relu(z.double())
+    n = a.shape[0]
+    ma = a.mean(0) if training else run_mean.double().abs()
+    sy = (a + ma) * w["invstd"] * gamma.double().abs() + beta.double().abs()
+    if training:
+        var = ((a - w["mean"]) ** 2).sum(0) / n
+        s_rm = (1 - momentum) * run_mean.double().abs() + momentum * ma
+        s_rv = (1 - momentum) * run_var.double().abs() + momentum * var * (n / max(n - 1, 1))
+    else:
+        s_rm, s_rv = run_mean.double().abs(), run_var.double().abs()
+    return dict(mean=ma, invstd=w["invstd"], y=sy, run_mean=s_rm, run_var=s_rv)
+
+
+def batchnorm_bwd_eval(z, gamma, mean, invstd, gy, training, dtype):
+    """{gz, g_gamma, g_beta} from the backward kernel's own float32 inputs (z, gamma, the saved mean / invstd, g_y)"""
+    zz, dy = z.to(dtype), gy.to(dtype)
+    xh = (torch.relu(zz) - mean.to(dtype)) * invstd.to(dtype)
+    s1, s2 = dy.sum(0), (dy * xh).sum(0)
+    n = zz.shape[0]
+    da = gamma.to(dtype) * invstd.to(dtype) * ((dy - s1 / n - xh * s2 / n) if training else dy)
+    return dict(gz=torch.where(zz > 0, da, torch.zeros_like(da)), g_gamma=s2, g_beta=s1)
+
+
+def batchnorm_bwd_scale(z, gamma, mean, invstd, gy, training):
+    zz, dy = z.double(), gy.double().abs()
+    xh = ((torch.relu(zz) - mean.double()) * invstd.double()).abs()
+    s1, s2 = dy.sum(0), (dy * xh).sum(0)
+    n = zz.shape[0]
+    da = gamma.double().abs() * invstd.double() * ((dy + s1 / n + xh * s2 / n) if training else dy)
+    return dict(gz=torch.where(zz > 0, da, torch.zeros_like(da)), g_gamma=s2, g_beta=s1)
+
+
+# ---- SpMM (lkg_spmm_csr_fused_f32)
+def spmm_eval(rowptr, col, val, x, n_rows, dtype, add_self=None, add2=None, bias=None, absolute=False, drop_last_of=None):
+    """out[i] = sum_j val[j] x[col[j]] (+ add_self[i] + add2[i] | bias).  absolute: every term by its absolute value (the
+    scale).  drop_last_of: a planted fault for the host test (the last entry of that row left out)."""
+    rp = rowptr.long()
+    cnt = rp[1:n_rows + 1] - rp[:n_rows]
+    rows = torch.repeat_interleave(torch.arange(n_rows, device=x.device), cnt)
+    lo_, hi_ = int(rp[0]), int(rp[n_rows])
+    cc, vv = col.long()[lo_:hi_], val.to(dtype)[lo_:hi_]
+    terms = vv[:, None] * x.to(dtype)[cc]
+    if drop_last_of is not None:
+        terms[int(rp[drop_last_of + 1]) - 1 - lo_] = 0
+    if absolute:
+        terms = terms.abs()
+    out = torch.zeros(n_rows, x.shape[1], dtype=dtype, device=x.device).index_add_(0, rows, terms)
+    for t in (add_self, add2, bias):
+        if t is not None:
+            out = out + (t.to(dtype).abs() if absolute else t.to(dtype))
+    return out
+
+
+# ---- element-wise row walkers (lkg_eltwise_f32, lkg_bi_mix_*, lkg_gate_blend_*): (want64, scale64, roundings)
+def eltwise_ref(op, a, b, alpha, beta):
+    """lkg_eltwise_f32's four ops; the rounding count is that of the kernel's expression (lkg_rowwise.hip)"""
+    x, al, be = a.double(), f32(alpha), f32(beta)
+    y = b.double() if b is not None else None
+    if op == 0:
+        if y is None:
+            return al * x + be, (al * x).abs() + abs(be), 1                 # fmaf(alpha, x, beta)
+        return al * x + be * y, (al * x).abs() + (be * y).abs(), 2          # fmaf(alpha, x, beta * y)
+    if op == 1:
+        return x * y, (x * y).abs(), 1                                      # x * y
+    if op == 2:
+        lx = leaky(x, al)
+        if y is None:
+            return lx, lx.abs(), 1                                          # alpha * x (+ 0)
+        ly = leaky(y, al)
+        return lx + ly, lx.abs() + ly.abs(), 3                              # alpha * x, alpha * y, the sum
+    w = x * torch.where(y > 0, torch.ones_like(y), torch.full_like(y, al))
+    return w, w.abs(), 1                                                    # x * (1 | alpha)
+
+
+def bi_mix_fwd_ref(ego, side, h0p, alpha):
+    """{sum, prod} -> (want64, scale64, roundings): fmaf(c, e + s, alpha * h) with c = 1 - alpha is c, e + s, alpha * h and
+    the fma: 4; the product form likewise (e * s in place of e + s); without h0p c = 1 and the added term is 0: 1"""
+    e, s = ego.double(), side.double()
+    if h0p is None:
+        return dict(sum=(e + s, e.abs() + s.abs(), 1), prod=(e * s, (e * s).abs(), 1))
+    al = f32(alpha)
+    c, hh = 1.0 - al, al * h0p.double()
+    return dict(sum=(c * (e + s) + hh, c * (e.abs() + s.abs()) + hh.abs(), 4),
+                prod=(c * e * s + hh, c * (e * s).abs() + hh.abs(), 4))
+
+
+def bi_mix_bwd_ref(ego, side, g_sum, g_prod, has_h0, alpha):
+    """{g_ego, g_side, g_h0p}: c * fmaf(gp, s, gs) is c, the fma and the product: 3 (1 without h0p: c = 1);
+    alpha * (gs + gp): 2"""
+    e, s, gs, gp = ego.double(), side.double(), g_sum.double(), g_prod.double()
+    al = f32(alpha)
+    c = 1.0 - al if has_h0 else 1.0
+    n_r = 3 if has_h0 else 1
+    res = dict(g_ego=(c * (gp * s + gs), c * ((gp * s).abs() + gs.abs()), n_r),
+               g_side=(c * (gp * e + gs), c * ((gp * e).abs() + gs.abs()), n_r))
+    if has_h0:
+        res["g_h0p"] = (al * (gs + gp), al * (gs.abs() + gp.abs()), 2)
+    return res
+
+
+def gate_blend_fwd_ref(x, gpre, zpre):
+    """(want64, scale64, roundings, extra): out = (1 - s) x + s t with s = sigmoid(z), t = tanh(g): 1 - s, its product,
+    s * t and the sum: 4; the activations' allowances through the derivative: s dt + |t - x| ds"""
+    xx = x.double()
+    s, t = torch.sigmoid(zpre.double()), torch.tanh(gpre.double())
+    want = (1 - s) * xx + s * t
+    scale = (1 + s) * xx.abs() + s * t.abs()          # (1 - s is itself a difference: |1| + |s|)
+    return want, scale, 4, s * tanh_allow(t) + (t - xx).abs() * sigmoid_allow(s)
+
+
+def gate_blend_bwd_ref(x, gpre, zpre, go):
+    """{g_x, g_gpre, g_zpre} -> (want64, scale64, roundings, extra) of lkg_gate_blend_bwd_f32 (activated = 0):
+    g_x = go (1 - s): 2;  g_gpre = go s (1 - t t): 4;  g_zpre = go (t - x) s (1 - s): 5"""
+    xx, g = x.double(), go.double()
+    s, t = torch.sigmoid(zpre.double()), torch.tanh(gpre.double())
+    ds, dt = sigmoid_allow(s), tanh_allow(t)
+    ag = g.abs()
+    return dict(
+        g_x=(g * (1 - s), ag * (1 + s), 2, ag * ds),
+        g_gpre=(g * s * (1 - t * t), ag * s * (1 + t * t), 4, ag * ((1 - t * t) * ds + s * 2 * t.abs() * dt + s * dt * dt)),
+        g_zpre=(g * (t - xx) * s * (1 - s), ag * (t.abs() + xx.abs()) * s * (1 + s), 5,
+                ag * (s * (1 - s) * dt + (t - xx).abs() * ((1 - 2 * s).abs() * ds + ds * ds) + dt * ds * (1 + 2 * ds))))
+
+
+# ---- attention refresh (lkg_edge_softmax_f32)
+def _entry_edges(rowptr, col, eptr, n_rows):
+    """(head row of every raw edge, stored entry of every raw edge, entry offsets)"""
+    dev = col.device
+    nnz = col.numel()
+    rp = rowptr.long()
+    rows = torch.repeat_interleave(torch.arange(n_rows, device=dev), rp[1:n_rows + 1] - rp[:n_rows])
+    ep = eptr.long() if eptr is not None else torch.arange(nnz + 1, device=dev)
+    entry = torch.repeat_interleave(torch.arange(nnz, device=dev), ep[1:] - ep[:-1])
+    return rows[entry], entry, ep
+
+
+def attention_logits_eval(rowptr, col, eptr, rel, ent, relemb, dtype, tanh=torch.tanh):
+    """(logits, scale, allowance) per stored entry:  sum over the entry's raw edges of  sum_d t_d tanh(h_d + r_d);
+    scale  sum |t_d| |tanh|;  allowance (float64 only): tanh_fast's 4e-7 (1 + |tanh|) and the rounding of h + r through
+    tanh' = 1 - tanh^2, each times |t_d|.  tanh: a planted fault for the host test."""
+    head, entry, _ = _entry_edges(rowptr, col, eptr, ent.shape[0])
+    e_, r_ = ent.to(dtype), relemb.to(dtype)
+    h, t, r = e_[head], e_[col.long()[entry]], r_[rel.long()[:entry.numel()]]
+    th = tanh(h + r)
+    nnz = col.numel()
+    z = lambda: torch.zeros(nnz, dtype=dtype, device=ent.device)
+    logits = z().index_add_(0, entry, (t * th).sum(1))
+    scale = z().index_add_(0, entry, (t * th).abs().sum(1))
+    allow = z().index_add_(0, entry, (t.abs() * (tanh_allow(th) + (1 - th * th) * U * (h.abs() + r.abs()))).sum(1))
+    return logits, scale, allow
+
+
+# roundings of one logit (lkg_attention.hip): the product, the lane's own chain (at most 4 chunks of 4 on the 16-byte path, 4
+# elements on the scalar one), the 6 butterfly steps, and the merge of up to 3 raw edges with the pre-pass' own wave sum
+def attention_logit_units(vec: bool) -> int:
+    return 1 + (16 if vec else 4) + 6 + 3
+
+
+def row_softmax_eval(rowptr, logits, n_rows, dtype, subtract_max=True):
+    """softmax of the stored logits over each row's entries.  subtract_max=False: a planted fault for the host test."""
+    rp = rowptr.long()
+    rows = torch.repeat_interleave(torch.arange(n_rows, device=logits.device), rp[1:n_rows + 1] - rp[:n_rows])
+    lo_, hi_ = int(rp[0]), int(rp[n_rows])
+    l = logits.to(dtype)[lo_:hi_]
+    mx = torch.full((n_rows,), -math.inf, dtype=dtype, device=l.device).scatter_reduce_(0, rows, l, "amax")
+    sh = l - mx[rows] if subtract_max else l
+    e = torch.exp(sh)
+    s = torch.zeros(n_rows, dtype=dtype, device=l.device).index_add_(0, rows, e)
+    return e / s[rows], (l - mx[rows]).abs()
+
+
+def softmax_excess(got, want64, ref32, spread):
+    """worst  |got - want| / allowed  with the allowed relative error  max(3 r_torch32, 2^-24 (4 + |l - max l|))  per entry
+    (one rounding of the exponent's argument carried through exp, plus exp, the sum and the division), and float32's
+    subnormal spacing 2^-149 as the absolute floor"""
+    rel32 = (ref32.double() - want64).abs() / (want64 + TINY)
+    allow = want64 * torch.maximum(3.0 * rel32, U * (4.0 + spread)) + 2.0 ** -149
+    q = torch.nan_to_num((got.double() - want64).abs() / allow, nan=math.inf)
+    i = int(q.argmax()) if q.numel() else 0
+    return (float(q[i]) if q.numel() else 0.0), i
+
+
+# ---- triple scores and losses (lkg_score.hip)
+def softplus_neg(x):
+    """-logsigmoid(x) = softplus(-x), stable in both tails"""
+    return torch.clamp(-x, min=0) + torch.log1p(torch.exp(-x.abs()))
+
+
+def trans_scores_eval(eh, er, ep, en, dtype):
+    """rows of h, r, t+, t- (one per triple) -> {pos, neg, reg} and their scales: sum (|h| + |r| + |t|)^2, reg"""
+    h, r, p, n = (t.to(dtype) for t in (eh, er, ep, en))
+    pos, neg = ((h + r - p) ** 2).sum(1), ((h + r - n) ** 2).sum(1)
+    reg = 0.5 * ((h * h).sum(1) + (r * r).sum(1) + (p * p).sum(1) + (n * n).sum(1))
+    scale = dict(pos=((h.abs() + r.abs() + p.abs()) ** 2).sum(1), neg=((h.abs() + r.abs() + n.abs()) ** 2).sum(1), reg=reg)
+    return dict(pos=pos, neg=neg, reg=reg), scale
+
+
+def dot_scores_eval(eh, ep, en, dtype):
+    h, p, n = (t.to(dtype) for t in (eh, ep, en))
+    reg = 0.5 * ((h * h).sum(1) + (p * p).sum(1) + (n * n).sum(1))
+    return (dict(pos=(h * p).sum(1), neg=(h * n).sum(1), reg=reg),
+            dict(pos=(h * p).abs().sum(1), neg=(h * n).abs().sum(1), reg=reg))
+
+
+def rank_eval(margin, dtype):
+    """(rank, scale) of -logsigmoid(margin): |margin| + log 2"""
+    m = margin.to(dtype)
+    return softplus_neg(m), m.abs() + math.log(2.0)
+
+
+def loss_eval(rank, reg, lam, dtype):
+    a, b = rank.to(dtype).mean(), reg.to(dtype).mean()
+    return a + lam * b, a.abs() + abs(lam) * b.abs()
+
+
+def trans_grads_eval(eh, er, ep, en, pos, neg, lam, g, dtype, sigmoid=torch.sigmoid):
+    """Per-triple gradient rows {h, r, p, n} of the TransE / TransR score loss from the backward kernel's own inputs (the
+    rows and the float32 pos / neg it kept), with the |.|-sums of their terms and the allowance for sigmoidf_'s
+    2e-6 (1 + |sigmoid|) through the terms it multiplies:
+        dp = g sigmoid(pos - neg) / B,  u = h + r - p,  w = h + r - n
+        g_h = g_r' = 2 (u - w) dp + lr h | r ;  g_p = -2 u dp + lr p ;  g_n = 2 w dp + lr n ;  lr = g lam / B"""
+    h, r, p, n = (t.to(dtype) for t in (eh, er, ep, en))
+    b = h.shape[0]
+    sg = sigmoid((pos.to(dtype) - neg.to(dtype)))[:, None]
+    dp, lr = g * sg / b, g * lam / b
+    u, w = h + r - p, h + r - n
+    su, sw = h.abs() + r.abs() + p.abs(), h.abs() + r.abs() + n.abs()
+    common, s_common = 2 * (u * dp - w * dp), 2 * (su + sw) * dp.abs()
+    val = dict(h=common + lr * h, r=common + lr * r, p=-2 * u * dp + lr * p, n=2 * w * dp + lr * n)
+    scale = dict(h=s_common + (lr * h).abs(), r=s_common + (lr * r).abs(), p=2 * su * dp.abs() + (lr * p).abs(),
+                 n=2 * sw * dp.abs() + (lr * n).abs())
+    ds = abs(g) / b * sigmoid_allow(sg)
+    allow = dict(h=2 * (u - w).abs() * ds, r=2 * (u - w).abs() * ds, p=2 * u.abs() * ds, n=2 * w.abs() * ds)
+    return val, scale, allow
+
+
+def dot_grads_eval(eh, ep, en, pos, neg, lam, g, dtype, sigmoid=torch.sigmoid):
+    """dn = g sigmoid(neg - pos) / B, dp = -dn:  g_h = dp p + dn n + lr h ;  g_p = dp h + lr p ;  g_n = dn h + lr n"""
+    h, p, n = (t.to(dtype) for t in (eh, ep, en))
+    b = h.shape[0]
+    sg = sigmoid((neg.to(dtype) - pos.to(dtype)))[:, None]
+    dn, lr = g * sg / b, g * lam / b
+    val = dict(h=dn * (n - p) + lr * h, p=-dn * h + lr * p, n=dn * h + lr * n)
+    scale = dict(h=dn.abs() * (n.abs() + p.abs()) + (lr * h).abs(), p=(dn * h).abs() + (lr * p).abs(),
+                 n=(dn * h).abs() + (lr * n).abs())
+    ds = abs(g) / b * sigmoid_allow(sg)
+    allow = dict(h=(n - p).abs() * ds, p=h.abs() * ds, n=h.abs() * ds)
+    return val, scale, allow
+
+
+def scatter_rows(n_rows, parts, dtype):
+    """sum of the per-triple rows into a table: parts = [(ids, rows)]"""
+    d = parts[0][1].shape[1]
+    out = torch.zeros(n_rows, d, dtype=dtype, device=parts[0][1].device)
+    for ids, rows in parts:
+        out.index_add_(0, ids.long(), rows.to(dtype))
+    return out
+
+
 # ----------------------------------------------------------------------------------------------------- the audit
 @dataclass
 class Record:
@@ -151,12 +564,13 @@ def _measure(audit, rec, got, want64, scale64, ref32, k=0):
 
 @contextlib.contextmanager
 def audit_ops(ops):
-    """Wrap ops.gemm, gemm_tall, gemm_wgrad, colsum, narrow_weight_grad, gemm_f64acc and linear_act_layernorm_fwd: every
-    call clones its inputs, runs the real op, and checks the result against float64 with the bound of the engine that
-    ran and every scale hint against the true maximum.  Yields the Audit."""
+    """Wrap ops.gemm, gemm_tall, gemm_wgrad, colsum, narrow_weight_grad, gemm_f64acc, linear_act_layernorm_fwd and
+    _grouped (the TransR loss's grouped products, counted as "grouped"): every call clones its inputs, runs the real op,
+    and checks the result against float64 with the bound of the engine that ran and every scale hint against the true
+    maximum.  Yields the Audit."""
     audit = Audit()
     real = {name: getattr(ops, name) for name in ("gemm", "gemm_tall", "gemm_wgrad", "colsum", "narrow_weight_grad",
-                                                   "gemm_f64acc", "linear_act_layernorm_fwd")}
+                                                   "gemm_f64acc", "linear_act_layernorm_fwd", "_grouped")}
     depth = [0]
 
     def count(name):
@@ -339,9 +753,27 @@ def audit_ops(ops):
         audit.records.append(rec)
         return res
 
+    def _grouped(mode, seg, max_len, a, b, out, m, n, k, trans_a, trans_b, beta, stride_b=0, stride_c=0, b_period=0):
+        count("grouped")
+        c0 = out.detach().clone() if beta != 0.0 else None
+        real["_grouped"](mode, seg, max_len, a, b, out, m, n, k, trans_a, trans_b, beta, stride_b, stride_c, b_period)
+        if seg.numel() < 2 or out.numel() == 0:
+            return
+        args = (mode, seg, a, b, c0, beta, trans_b, b_period)
+        want = grouped_eval(*args, torch.float64)
+        scale = grouped_scale(*args)
+        ref32 = grouped_eval(*args, torch.float32)
+        site = _ops_site()
+        for g, rows, am, bm in grouped_blocks(mode, seg, a, b, trans_b, b_period):
+            if want[g].numel() == 0:
+                continue
+            rec = Record("grouped/" + ("rows" if mode == 1 else "k"), site, "f32_mfma", (tuple(am.shape), tuple(bm.shape)),
+                         0.0, 0.0, "")
+            _measure(audit, rec, (out[rows] if mode == 1 else out[g]).detach(), want[g], scale[g], ref32[g], am.shape[1])
+
     wrappers = dict(gemm=gemm, gemm_tall=gemm_tall, gemm_wgrad=gemm_wgrad, colsum=colsum,
                     narrow_weight_grad=narrow_weight_grad, gemm_f64acc=gemm_f64acc,
-                    linear_act_layernorm_fwd=linear_act_layernorm_fwd)
+                    linear_act_layernorm_fwd=linear_act_layernorm_fwd, _grouped=_grouped)
     for name, w in wrappers.items():
         setattr(ops, name, w)
     try:

@@ -73,6 +73,8 @@ def test_every_device_op_of_a_model_step_is_within_its_bound(L, O, gpu_device, c
     assert audit.inner.get("colsum", 0) + audit.inner.get("narrow_weight_grad", 0) > 0, audit.inner
     if c["gate"] is not None:
         assert audit.inner.get("gemm_wgrad", 0) + audit.inner.get("narrow_weight_grad", 0) > 0, audit.inner
+    if c["scoring"] == "transr":        # the TransR loss's projections and gradients: lkg_grouped_gemm_f32, rows and k mode
+        assert audit.calls.get("grouped", 0) > 0, audit.calls
     assert not audit.failures, f"case {seed}:\n" + op_audit.report(audit)
     # a scale hint far above its tensor's maximum costs bits of the split: none in these steps
     assert not audit.hint_notes, audit.hint_notes
