@@ -301,7 +301,21 @@ int lkg_gather_i64(int64_t n, const int64_t *src, const int32_t *perm, int64_t *
  * random.choice(training_tails), rejecting (tail, relation) positives of the head and repeats inside the
  * group; h / r / pos_t are repeated neg_rate times.  Outputs are int64[n_groups * neg_rate].  A head outside
  * [0, n_entities) or without a triple (kg_dict[h] raises KeyError in the reference) yields a sentinel group:
- * r = pos_t = neg_t = -1, nothing is drawn.  Counter-based RNG: the batch is a pure function of (seed, heads).  */
+ * r = pos_t = neg_t = -1, nothing is drawn.  Counter-based RNG: the batch is a pure function of (seed, heads).
+ *
+ * The stream (all arithmetic on unsigned 64-bit integers, wrapping):
+ *   mix(z):  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;  z = (z ^ (z >> 27)) * 0x94D049BB133111EB;  return z ^ (z >> 31)
+ *   group g (0-based position in `heads`) has the key  mix(seed ^ (0xD1B54A32D192ED03 * (g + 1)))  and a counter that
+ *   starts at 0; every draw increments the counter first and has the value  mix(key + 0x9E3779B97F4A7C15 * counter);
+ *   "a number below n" is  value % n.
+ * The raw triples are taken in the structure's sorted order (by head, then tail; lkg_csr_build's `order`), so those of a
+ * head are consecutive.  Order of the draws of a group: FIRST the positive -- a number below the head's triple count picks
+ * the head's triple at that offset (its relation and tail) -- THEN the candidates, one draw each: a number below n_raw
+ * picks a raw triple, whose tail is the candidate.  A candidate is rejected when (head, candidate, the positive's
+ * relation) is a triple or when it equals an earlier negative of the group; the next draw replaces it.  The 256th
+ * candidate of one negative is kept whether or not it would be rejected (the reference would draw for ever: this happens
+ * only when the head's triples and the group's negatives leave fewer free tails than neg_rate).  Negatives are drawn
+ * one after the other, k = 0 .. neg_rate - 1, from the same stream.  */
 int lkg_sample_kg_batch(int64_t n_groups, int32_t neg_rate, uint64_t seed, const int64_t *heads,
                         int64_t n_entities, const int32_t *rowptr, const int32_t *col, const int32_t *eptr, const int32_t *rel,
                         int64_t nnz, int64_t n_raw, int64_t *out_h, int64_t *out_r, int64_t *out_pos_t,

@@ -228,7 +228,25 @@ extern "C" int lkg_group_by_key_i64(int64_t n, int32_t n_keys, const int64_t *ke
     LKG_REQUIRE(n >= 0 && n < INT32_MAX && n_keys >= 1, "lkg_group_by_key_i64: bad sizes");
     LKG_REQUIRE(n_keys <= 1024, "lkg_group_by_key_i64: at most 1024 distinct keys supported (got %d)", n_keys);
     LKG_REQUIRE(seg && (n == 0 || (keys && perm)), "lkg_group_by_key_i64: null pointer");
-    hipLaunchKernelGGL(group_by_key_kernel, dim3(1), dim3(1024), sizeof(int) * (n_keys * GB_WAVES + 1),
+    const int lds = (int)sizeof(int) * (n_keys * GB_WAVES + 1);
+    // n_keys = 1024 asks for 65 540 bytes, four over the 64 KiB a kernel may take as dynamic LDS unless its limit is raised
+    // (the limit belongs to the kernel on ONE device: one flag per device of the process)
+    static bool raised_on[64] = {};
+    int dev = 0;
+    if (lds > 64 * 1024 && (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64)) {
+        lkg_set_error("lkg_group_by_key_i64: cannot tell the current device");
+        return LKG_ERR_HIP;
+    }
+    bool &raised = raised_on[dev];
+    if (!raised && lds > 64 * 1024) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void *>(group_by_key_kernel),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, sizeof(int) * (1024 * GB_WAVES + 1)) != hipSuccess) {
+            lkg_set_error("lkg_group_by_key_i64: cannot raise the dynamic LDS limit");
+            return LKG_ERR_HIP;
+        }
+        raised = true;
+    }
+    hipLaunchKernelGGL(group_by_key_kernel, dim3(1), dim3(1024), lds,
                        (hipStream_t)stream, (long)n, n_keys, (const long *)keys, perm, seg, n_bad);
     LKG_CHECK_LAUNCH("lkg_group_by_key_i64");
     return LKG_OK;
