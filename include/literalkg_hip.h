@@ -727,6 +727,36 @@ int lkg_pair_mlp_count_f32(int64_t n_q, int64_t n_cand, const float *uq, int64_t
                            const float *w2, const float *b2, const float *w3, const float *b3, const float *thr,
                            const int64_t *truth, int32_t *better, int32_t *equal, void *stream);
 
+/* Explicit pairs under the head (lkg_pairmlp.hip; score_pairs_mlp, evaluate_mlp_classification).  Pair i is (row u_idx[i]
+ * of u, row v_idx[i] of v) of the two projected tables (as uq / v above: f32, 128 columns, row strides multiples of 4,
+ * 16-byte aligned); a NULL index list means "pair i uses row i".  Row indices are trusted.
+ *
+ * lkg_pair_mlp_pairs_f32: out[i] = z(u_idx[i], v_idx[i]), the bits lkg_pair_mlp_scores_f32 stores for that pair, and / or
+ *     counts[0..4] += tp, fp, tn, fn, nan against labels (uint8[n_pairs], 0 or 1) and the logit threshold thr: a pair is
+ *     predicted positive iff z > thr (an f32 compare); a NaN logit is counted in nan and in none of the other four.
+ *     out and counts are each nullable, at least one is given; counts needs labels.  The counts are ACCUMULATED (64-bit
+ *     integer atomics, at most five per workgroup: the order of arrival does not enter), so batches add up; the caller
+ *     zeroes them.  64-bit addressing, n_pairs <= INT32_MAX - 1; n_pairs == 0 launches nothing.                      */
+int lkg_pair_mlp_pairs_f32(int64_t n_pairs, const float *u, int64_t ldu, const float *v, int64_t ldv,
+                           const int64_t *u_idx, const int64_t *v_idx, const float *w2, const float *b2, const float *w3,
+                           const float *b3, const uint8_t *labels, float thr, float *out, int64_t *counts, void *stream);
+
+/* Exact tie-aware ROC AUC and average precision of n (score, label) pairs (lkg_csr_device.hip): scores f32[n], labels
+ * uint8[n] (0 or 1).  out_counts int64[5] = n_pos, n_neg, n_nan, n_groups, auc2; out_ap double[1].
+ *   ties      by float equality: -0.0 and +0.0 tie; +-inf are ordinary values
+ *   NaN       scores are counted in n_nan and take part in nothing else (n_pos + n_neg + n_nan = n)
+ *   n_groups  the number of distinct non-NaN scores
+ *   auc2      sum over positives i of (2 #{negatives j: s_j < s_i} + #{negatives j: s_j == s_i}), an exact integer;
+ *             ROC AUC = auc2 / (2 n_pos n_neg), formed by the caller
+ *   ap        sum over the distinct scores in descending order of (TP_g - TP_(g-1)) / n_pos * TP_g / (TP_g + FP_g), the
+ *             cumulative counts taken at the end of each tie group (average precision as a step function, not the
+ *             trapezoid); float64, three roundings per term, summed in an order that is a fixed function of the sorted
+ *             scores: the same bits from run to run and for any permutation of the input.  0.0 when n_pos == 0.
+ * n <= INT32_MAX - 1; n == 0 gives all-zero outputs.  workspace: lkg_binary_curve_workspace(n) bytes of device memory. */
+int64_t lkg_binary_curve_workspace(int64_t n);
+int lkg_binary_curve_f32(int64_t n, const float *scores, const uint8_t *labels, int64_t *out_counts, double *out_ap,
+                         void *workspace, int64_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

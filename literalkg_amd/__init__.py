@@ -12,9 +12,9 @@ from .model import Aggregator, LiteralKG  # noqa: F401
 from .graph import KGStructure           # noqa: F401
 from .ranking import KnownTriples, RankResult, evaluate_ranking   # noqa: F401
 from .topk import TopKResult, predict_topk   # noqa: F401
-from .pairmlp import (FoldedMLPHead, evaluate_mlp_ranking, fold_mlp_head, mlp_scores,   # noqa: F401
-                      rank_pairs_mlp)
+from .pairmlp import (FoldedMLPHead, evaluate_mlp_classification, evaluate_mlp_ranking,   # noqa: F401
+                      fold_mlp_head, mlp_scores, rank_pairs_mlp, score_pairs_mlp)
 
 __all__ = ["LiteralKG", "Aggregator", "Gate", "GateMul", "KGStructure", "KnownTriples", "RankResult", "evaluate_ranking",
            "TopKResult", "predict_topk", "FoldedMLPHead", "fold_mlp_head", "mlp_scores", "rank_pairs_mlp",
-           "evaluate_mlp_ranking"]
+           "evaluate_mlp_ranking", "score_pairs_mlp", "evaluate_mlp_classification"]

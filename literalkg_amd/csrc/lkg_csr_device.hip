@@ -507,3 +507,171 @@ int lkg_internal_preload_csr_device() {
     hipFuncAttributes attr;
     return hipFuncGetAttributes(&attr, reinterpret_cast<const void *>(&scan_totals_kernel)) == hipSuccess ? 0 : 1;
 }
+
+// ---------------------------------------------------------------------------------------------------
+// Exact tie-aware ROC AUC and average precision of (score, label) lists (evaluate_mlp_classification), on the radix sort
+// and the scan above.  Scores are put in DESCENDING order by the key
+//     ((~ascending key of s) << 1) | label          ascending key: sign flipped for s >= 0, all bits for s < 0
+// with -0.0 canonicalised to +0.0 first (float equality is the tie rule) and NaN scores keyed past every number
+// (bit 33), so the non-NaN scores are the first n - n_nan sorted keys and a tie group is a run of equal key >> 1.  Then
+//   bc_mark     pos[k] = the key's label, end[k] = 1 where a tie group ends               (both 0 for NaN keys)
+//   scans       pos -> positives before k (total n_pos), end -> the group's index g (total n_groups)
+//   bc_compact  at every group end: tp[g] = positives up to and including k, cum[g] = k + 1 = TP_g + FP_g
+//   bc_groups   per group dTP = TP_g - TP_(g-1), dFP likewise:  auc2 += dTP (2 (n_neg - FP_g) + dFP)  (64-bit integers:
+//               the negatives below the group count twice, those inside it once), and the float64 term
+//               (dTP / n_pos) * (TP_g / (TP_g + FP_g)) of the average precision, three roundings; a workgroup adds its
+//               1024 terms in a fixed tree and stores one partial
+//   bc_finish   n_neg, and ap = the partials added in a fixed order by one workgroup
+// The sorted keys are the same for any order of the input, and every float64 sum is a fixed function of them: the same
+// bits from run to run and for any permutation.
+namespace {
+
+constexpr int BC_THREADS = 256, BC_ITEMS = 4, BC_TILE = BC_THREADS * BC_ITEMS;
+constexpr u64 BC_NAN_KEY = 1ull << 33;
+
+__global__ void bc_keys_kernel(long n, const float *__restrict__ scores, const unsigned char *__restrict__ labels,
+                               u64 *__restrict__ keys, u64 *__restrict__ n_nan) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    bool nan = false;
+    if (i < n) {
+        u32 b = __float_as_uint(scores[i]);
+        nan = (b & 0x7fffffffu) > 0x7f800000u;
+        b = (b << 1) ? b : 0u;                                    // -0.0 ties with +0.0 (subnormals stay themselves)
+        const u32 asc = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+        keys[i] = nan ? BC_NAN_KEY : (((u64)(~asc)) << 1) | (u64)(labels[i] != 0);
+    }
+    const u64 m = __ballot(nan);
+    if (m && (threadIdx.x & 63) == 0) atomicAdd(n_nan, (u64)__popcll(m));
+}
+
+__global__ void bc_mark_kernel(long n, const u64 *__restrict__ keys, int *__restrict__ pos, int *__restrict__ end) {
+    const long k = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    const u64 key = keys[k];
+    const bool valid = key < BC_NAN_KEY;
+    pos[k] = valid ? (int)(key & 1ull) : 0;
+    end[k] = (valid && (k == n - 1 || (keys[k + 1] >> 1) != (key >> 1))) ? 1 : 0;
+}
+
+// pos / grp: the exclusive scans of the marks
+__global__ void bc_compact_kernel(long n, const u64 *__restrict__ keys, const int *__restrict__ pos,
+                                  const int *__restrict__ grp, int *__restrict__ tp, int *__restrict__ cum) {
+    const long k = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    const u64 key = keys[k];
+    if (key >= BC_NAN_KEY || (k != n - 1 && (keys[k + 1] >> 1) == (key >> 1))) return;
+    const int g = grp[k];
+    tp[g] = pos[k] + (int)(key & 1ull);
+    cum[g] = (int)(k + 1);
+}
+
+// out: n_pos, n_neg, n_nan, n_groups, auc2 (n_pos, n_nan and n_groups are final here)
+__global__ __launch_bounds__(BC_THREADS) void bc_groups_kernel(long n, const int *__restrict__ tp,
+                                                               const int *__restrict__ cum, long *__restrict__ out,
+                                                               double *__restrict__ partial) {
+    __shared__ double sd[BC_THREADS / 64];
+    __shared__ u64 si[BC_THREADS / 64];
+    const long n_pos = out[0], n_groups = out[3], n_neg = n - out[2] - n_pos;
+    const long g0 = (long)blockIdx.x * BC_TILE + (long)threadIdx.x * BC_ITEMS;
+    double ap = 0.0;
+    u64 auc2 = 0;
+#pragma unroll
+    for (int j = 0; j < BC_ITEMS; ++j) {
+        const long g = g0 + j;
+        if (g < n_groups) {
+            const long t1 = tp[g], c1 = cum[g], t0 = g ? tp[g - 1] : 0, c0 = g ? cum[g - 1] : 0;
+            const long d_tp = t1 - t0, d_fp = (c1 - t1) - (c0 - t0);
+            auc2 += (u64)d_tp * (u64)(2 * (n_neg - (c1 - t1)) + d_fp);
+            if (d_tp) ap += ((double)d_tp / (double)n_pos) * ((double)t1 / (double)c1);
+        }
+    }
+#pragma unroll
+    for (int o = 32; o; o >>= 1) {
+        ap += __shfl_down(ap, o, 64);
+        auc2 += __shfl_down(auc2, o, 64);
+    }
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    if (lane == 0) {
+        sd[w] = ap;
+        si[w] = auc2;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double a = sd[0];
+        u64 b = si[0];
+        for (int i = 1; i < BC_THREADS / 64; ++i) {
+            a += sd[i];
+            b += si[i];
+        }
+        partial[blockIdx.x] = a;
+        if (b) atomicAdd((u64 *)out + 4, b);
+    }
+}
+
+__global__ __launch_bounds__(1024) void bc_finish_kernel(long n, long n_partial, const double *__restrict__ partial,
+                                                         long *__restrict__ out, double *__restrict__ ap_out) {
+    __shared__ double sd[1024];
+    double a = 0.0;
+    for (long i = threadIdx.x; i < n_partial; i += 1024) a += partial[i];
+    sd[threadIdx.x] = a;
+    __syncthreads();
+    for (int o = 512; o; o >>= 1) {
+        if ((int)threadIdx.x < o) sd[threadIdx.x] += sd[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        out[1] = n - out[2] - out[0];
+        *ap_out = sd[0];
+    }
+}
+
+long bc_ws_bytes(long n) {
+    const long e = std::max<long>(n, 1);
+    return sort_ws_bytes(e) + 4 * align_up(4 * e, 256) + align_up(8 * ceil_div(e, BC_TILE), 256) + 256;
+}
+
+}  // namespace
+
+extern "C" int64_t lkg_binary_curve_workspace(int64_t n) { return n < 0 ? 0 : bc_ws_bytes(n); }
+
+extern "C" int lkg_binary_curve_f32(int64_t n, const float *scores, const uint8_t *labels, int64_t *out_counts,
+                                    double *out_ap, void *workspace, int64_t workspace_bytes, void *stream) {
+    LKG_REQUIRE(n >= 0 && n <= (int64_t)INT32_MAX - 1, "lkg_binary_curve_f32: n %lld out of range", (long long)n);
+    LKG_REQUIRE(out_counts && out_ap, "lkg_binary_curve_f32: null pointer");
+    hipStream_t s = (hipStream_t)stream;
+    if (hipMemsetAsync(out_counts, 0, 5 * sizeof(int64_t), s) != hipSuccess ||
+        hipMemsetAsync(out_ap, 0, sizeof(double), s) != hipSuccess) {
+        lkg_set_error("lkg_binary_curve_f32: hipMemsetAsync failed");
+        return LKG_ERR_HIP;
+    }
+    if (n == 0) return LKG_OK;
+    LKG_REQUIRE(scores && labels && workspace, "lkg_binary_curve_f32: null pointer");
+    LKG_REQUIRE(workspace_bytes >= bc_ws_bytes(n),
+                "lkg_binary_curve_f32: workspace of %lld bytes is smaller than the %lld required",
+                (long long)workspace_bytes, (long long)bc_ws_bytes(n));
+    char *ws = (char *)workspace;
+    const SortWs w = carve(ws, n);
+    const long stride = align_up(4 * n, 256);
+    int *pos = (int *)(ws + sort_ws_bytes(n));
+    int *grp = (int *)((char *)pos + stride), *tp = (int *)((char *)pos + 2 * stride);
+    int *cum = (int *)((char *)pos + 3 * stride);
+    double *partial = (double *)((char *)pos + 4 * stride);
+    long *out = (long *)out_counts;
+    hipLaunchKernelGGL(bc_keys_kernel, grid1d(n), dim3(256), 0, s, (long)n, scores, labels, w.k0, (u64 *)(out + 2));
+    u64 *keys;
+    u32 *perm;
+    int rc = radix_sort(w, n, 34, &keys, &perm, s);
+    if (rc != LKG_OK) return rc;
+    hipLaunchKernelGGL(bc_mark_kernel, grid1d(n), dim3(256), 0, s, (long)n, keys, pos, grp);
+    rc = exclusive_scan(pos, pos, n, w.sums, out + 0, s);
+    if (rc != LKG_OK) return rc;
+    rc = exclusive_scan(grp, grp, n, w.sums, out + 3, s);
+    if (rc != LKG_OK) return rc;
+    hipLaunchKernelGGL(bc_compact_kernel, grid1d(n), dim3(256), 0, s, (long)n, keys, pos, grp, tp, cum);
+    const long n_partial = ceil_div(n, BC_TILE);
+    hipLaunchKernelGGL(bc_groups_kernel, dim3((unsigned)n_partial), dim3(BC_THREADS), 0, s, (long)n, tp, cum, out,
+                       partial);
+    hipLaunchKernelGGL(bc_finish_kernel, dim3(1), dim3(1024), 0, s, (long)n, n_partial, partial, out, out_ap);
+    LKG_CHECK_LAUNCH("lkg_binary_curve_f32");
+    return LKG_OK;
+}

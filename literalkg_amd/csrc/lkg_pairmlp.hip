@@ -1,6 +1,7 @@
 // The MLP pair head at inference (literalkg_amd/pairmlp.py): logits of every (query, candidate) pair, and the filtered
 // top-k of them per query, from the two PROJECTED tables of the head's first layer; and, further down, the filtered rank
-// counts of held-out pairs (prepare + count), which compare those logits instead of storing them.
+// counts of held-out pairs (prepare + count), which compare those logits instead of storing them; and the logits and
+// confusion counts of an explicit list of pairs (pairs), every row of the A operand a pair of its own.
 //
 // With BatchNorm in inference form folded forward the head is
 //     x1 = relu(u_q + v_c)                      u = Uq row (128, bias included), v = V row (128)
@@ -16,7 +17,8 @@
 // Position independence: a pair's logit is a fixed sequence of f32 operations on (u row, v row, folded weights) --
 // k order 16 t + {0, 4, 8, 12} + e for e = 0..3, t = 0..7 (the order of lkg_rank_common.h); the epilogue's in-lane fma
 // chain over the 4 column blocks, then the xor butterfly over the 16 lanes of a row -- whatever tile, wave, row, split
-// or launch computes it, and the same in the store and the select epilogue (both call pm_pair_logits).
+// or launch computes it, and the same in every epilogue and for either source of the A rows (all go through
+// pm_logits_of).
 //
 // Selection: the state and the merge of lkg_topk_common.h, fed s = -2 z (exact), so ascending s is descending logit and
 // lkg_topk_merge_f32 reports -s / 2 = z.  After the lane reduction one lane holds a pair's logit; it is pushed when it
@@ -65,18 +67,34 @@ __device__ __forceinline__ void pm_load_v(float4 (&vf)[PM_H1 / 16], const float 
     for (int t = 0; t < PM_H1 / 16; ++t) vf[t] = *reinterpret_cast<const float4 *>(vrow + 16 * t + 4 * s);
 }
 
-// z[v] = the logit of (the query whose u row is at `urow` in LDS, the wave's candidate 4 s + v), the same bits in all
-// 16 lanes r of the row group.  Call with all lanes active.
-__device__ __forceinline__ void pm_pair_logits(float (&z)[4], const float *urow, const float4 (&vf)[PM_H1 / 16],
-                                               const PairWeights &w, int s) {
+// Where row r of the A operand comes from: x1(t) = elements 16 t + 4 s .. + 3 of relu(u + v) for the lane's row.
+// PmBroadcastU: one u row in LDS for all 16 candidates (the query of the store / select / count / prepare kernels).
+// PmOwnX: every row a pair of its own, its relu(u + v) already formed from the lane's own u and v fragments.
+struct PmBroadcastU {
+    const float *urow;
+    const float4 (&vf)[PM_H1 / 16];
+    int s;
+    __device__ __forceinline__ float4 x1(int t) const {
+        const float4 u = *reinterpret_cast<const float4 *>(urow + 16 * t + 4 * s);
+        return make_float4(pm_relu(u.x + vf[t].x), pm_relu(u.y + vf[t].y), pm_relu(u.z + vf[t].z),
+                           pm_relu(u.w + vf[t].w));
+    }
+};
+struct PmOwnX {
+    const float4 (&xf)[PM_H1 / 16];
+    __device__ __forceinline__ float4 x1(int t) const { return xf[t]; }
+};
+
+// z[v] = the logit of row 4 s + v of the wave's 16 A rows, the same bits in all 16 lanes r of the row group: the one
+// operation sequence of a logit, whatever feeds the rows.  Call with all lanes active.
+template <typename ROWS>
+__device__ __forceinline__ void pm_logits_of(float (&z)[4], const ROWS &rows, const PairWeights &w) {
     f32x4 acc[PM_H2 / 16];
 #pragma unroll
     for (int j = 0; j < PM_H2 / 16; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int t = 0; t < PM_H1 / 16; ++t) {
-        const float4 u = *reinterpret_cast<const float4 *>(urow + 16 * t + 4 * s);
-        const float4 x = make_float4(pm_relu(u.x + vf[t].x), pm_relu(u.y + vf[t].y), pm_relu(u.z + vf[t].z),
-                                     pm_relu(u.w + vf[t].w));
+        const float4 x = rows.x1(t);
 #pragma unroll
         for (int j = 0; j < PM_H2 / 16; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(x.x, w.b[t][j].x, acc[j], 0, 0, 0);
 #pragma unroll
@@ -86,7 +104,7 @@ __device__ __forceinline__ void pm_pair_logits(float (&z)[4], const float *urow,
 #pragma unroll
         for (int j = 0; j < PM_H2 / 16; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(x.w, w.b[t][j].w, acc[j], 0, 0, 0);
     }
-    // acc[j][v]: candidate 4 s + v, fc2 output 16 j + r
+    // acc[j][v]: row 4 s + v, fc2 output 16 j + r
 #pragma unroll
     for (int v = 0; v < 4; ++v) {
         float p = 0.f;
@@ -94,6 +112,17 @@ __device__ __forceinline__ void pm_pair_logits(float (&z)[4], const float *urow,
         for (int j = 0; j < PM_H2 / 16; ++j) p = __builtin_fmaf(w.w3[j], pm_relu(acc[j][v] + w.b2[j]), p);
         z[v] = group_sum<16>(p) + w.b3;
     }
+}
+
+// z[v] = the logit of (the query whose u row is at `urow` in LDS, the wave's candidate 4 s + v)
+__device__ __forceinline__ void pm_pair_logits(float (&z)[4], const float *urow, const float4 (&vf)[PM_H1 / 16],
+                                               const PairWeights &w, int s) {
+    pm_logits_of(z, PmBroadcastU{urow, vf, s}, w);
+}
+
+// z[v] = the logit of the wave's pair 4 s + v, xf the lane's fragments of relu(u + v) of ITS pair r
+__device__ __forceinline__ void pm_own_pair_logits(float (&z)[4], const float4 (&xf)[PM_H1 / 16], const PairWeights &w) {
+    pm_logits_of(z, PmOwnX{xf}, w);
 }
 
 // lane r < 4 of a row group speaks for candidate 4 s + r
@@ -354,6 +383,69 @@ __global__ __launch_bounds__(PM_THREADS) void pair_mlp_count_kernel(
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Explicit pairs (score_pairs_mlp, evaluate_mlp_classification): pair i = (row u_idx[i] of u, row v_idx[i] of v).  A wave
+// owns 16 pairs per step and lane (r, s) forms relu(u + v) of ITS pair r from the two gathered rows, so the A operand has
+// a pair of its own in every row; the rest is pm_logits_of, the operation sequence of every other logit in this file.
+// The grid is capped so that a wave keeps the weights for many steps.  Pairs past the end are clamped to the last one:
+// computed, never stored or counted.
+constexpr long PM_PAIRS_GRID = 1024;             // workgroups at most: 64 pairs per workgroup and trip
+
+// counts[0..4] += tp, fp, tn, fn, nan of the pairs against labels and the logit threshold thr: per lane in registers,
+// per workgroup in LDS, then one 64-bit atomic per non-zero count and workgroup (integers: no order enters).
+__global__ __launch_bounds__(PM_THREADS) void pair_mlp_pairs_kernel(
+    long n_pairs, const float *__restrict__ u, long ldu, const float *__restrict__ v, long ldv,
+    const long *__restrict__ u_idx, const long *__restrict__ v_idx, const float *__restrict__ w2,
+    const float *__restrict__ b2, const float *__restrict__ w3, const float *__restrict__ b3,
+    const unsigned char *__restrict__ labels, float thr, float *__restrict__ out,
+    unsigned long long *__restrict__ counts) {
+    __shared__ int cnt[5];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int r = lane & 15, s = lane >> 4;
+    if (tid < 5) cnt[tid] = 0;
+    PairWeights w;
+    pm_load_weights(w, w2, b2, w3, b3, r, s);
+    int n_tp = 0, n_fp = 0, n_tn = 0, n_fn = 0, n_nan = 0;
+    // (the trip count is uniform in the workgroup: a wave whose 16 pairs all lie past the end computes the last pair)
+    for (long base = (long)blockIdx.x * PM_COLS; base < n_pairs; base += (long)gridDim.x * PM_COLS) {
+        const long p0 = base + wave * 16;
+        const long pr = p0 + r < n_pairs ? p0 + r : n_pairs - 1;
+        const float *urow = u + (u_idx ? u_idx[pr] : pr) * ldu;
+        const float *vrow = v + (v_idx ? v_idx[pr] : pr) * ldv;
+        float4 xf[PM_H1 / 16];
+#pragma unroll
+        for (int t = 0; t < PM_H1 / 16; ++t) {
+            const float4 a = *reinterpret_cast<const float4 *>(urow + 16 * t + 4 * s);
+            const float4 b = *reinterpret_cast<const float4 *>(vrow + 16 * t + 4 * s);
+            xf[t] = make_float4(pm_relu(a.x + b.x), pm_relu(a.y + b.y), pm_relu(a.z + b.z), pm_relu(a.w + b.w));
+        }
+        float z[4];
+        pm_own_pair_logits(z, xf, w);
+        const long pw = p0 + 4 * s + (r & 3);
+        if (r < 4 && pw < n_pairs) {
+            const float zp = pm_pick(z, r);
+            if (out) out[pw] = zp;
+            if (counts) {
+                const bool one = labels[pw] != 0, nan = zp != zp, pos = zp > thr;
+                n_nan += nan;
+                n_tp += !nan && pos && one;
+                n_fp += !nan && pos && !one;
+                n_tn += !nan && !pos && !one;
+                n_fn += !nan && !pos && one;
+            }
+        }
+    }
+    if (!counts) return;                                          // (uniform: a kernel argument)
+    __syncthreads();
+    if (n_tp) atomicAdd(&cnt[0], n_tp);
+    if (n_fp) atomicAdd(&cnt[1], n_fp);
+    if (n_tn) atomicAdd(&cnt[2], n_tn);
+    if (n_fn) atomicAdd(&cnt[3], n_fn);
+    if (n_nan) atomicAdd(&cnt[4], n_nan);
+    __syncthreads();
+    if (tid < 5 && cnt[tid]) atomicAdd(counts + tid, (unsigned long long)cnt[tid]);
+}
+
 // candidate splits of the count kernel: enough workgroups for a smooth tail, each with a long run of tiles, and never
 // fewer than two workgroups per CU while there are tiles to hand out
 long pm_count_splits(long tiles_q, long tiles_c) {
@@ -480,6 +572,27 @@ extern "C" int lkg_pair_mlp_count_f32(int64_t n_q, int64_t n_cand, const float *
                        (hipStream_t)stream, (long)n_q, (long)n_cand, uq, (long)ldu, v, (long)ldv, w2, b2, w3, b3, thr,
                        (const long *)truth, better, equal, splits, tiles_q, tiles_c);
     LKG_CHECK_LAUNCH("lkg_pair_mlp_count_f32");
+    return LKG_OK;
+}
+
+extern "C" int lkg_pair_mlp_pairs_f32(int64_t n_pairs, const float *u, int64_t ldu, const float *v, int64_t ldv,
+                                      const int64_t *u_idx, const int64_t *v_idx, const float *w2, const float *b2,
+                                      const float *w3, const float *b3, const uint8_t *labels, float thr, float *out,
+                                      int64_t *counts, void *stream) {
+    LKG_REQUIRE(n_pairs >= 0 && n_pairs <= (int64_t)INT32_MAX - 1, "lkg_pair_mlp_pairs_f32: bad sizes");
+    LKG_REQUIRE(out || counts, "lkg_pair_mlp_pairs_f32: nothing to write (out and counts are both null)");
+    LKG_REQUIRE(!counts || labels, "lkg_pair_mlp_pairs_f32: counts need labels (null pointer)");
+    if (n_pairs == 0) return LKG_OK;
+    LKG_REQUIRE(u && v && w2 && b2 && w3 && b3, "lkg_pair_mlp_pairs_f32: null pointer");
+    LKG_REQUIRE(pm_operands_ok(u, ldu, v, ldv, w2),
+                "lkg_pair_mlp_pairs_f32: u, v and w2 must be 16-byte aligned with row strides that are multiples of 4 "
+                "(at least 128)");
+    const long blocks = (n_pairs + PM_COLS - 1) / PM_COLS;
+    hipLaunchKernelGGL(pair_mlp_pairs_kernel, dim3((unsigned)(blocks < PM_PAIRS_GRID ? blocks : PM_PAIRS_GRID)),
+                       dim3(PM_THREADS), 0, (hipStream_t)stream, (long)n_pairs, u, (long)ldu, v, (long)ldv,
+                       (const long *)u_idx, (const long *)v_idx, w2, b2, w3, b3, labels, thr, out,
+                       (unsigned long long *)counts);
+    LKG_CHECK_LAUNCH("lkg_pair_mlp_pairs_f32");
     return LKG_OK;
 }
 

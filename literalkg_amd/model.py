@@ -719,6 +719,12 @@ class LiteralKG(nn.Module):
         from .pairmlp import rank_pairs_mlp
         return rank_pairs_mlp(self, h, t, r=r, side=side, known=known, candidates=candidates, batch_size=batch_size)
 
+    def score_pairs(self, h, t, logits: bool = False, batch_size: Optional[int] = None):
+        """float32[P]: the MLP pair head's probability (or logit) of every pair (h_i, t_i) on the inference table, each
+        logit with the bits mlp_scores gives that pair (literalkg_amd/pairmlp.py, score_pairs_mlp)."""
+        from .pairmlp import score_pairs_mlp
+        return score_pairs_mlp(self, h, t, logits=logits, batch_size=batch_size)
+
     def initialize_MLP(self):
         """The pair-classification head of model.py:499-504 (same module names, so checkpoints interchange)."""
         self.fc1 = nn.Linear(self.scale_gat_dim * 2, 128)

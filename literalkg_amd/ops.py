@@ -2442,3 +2442,91 @@ def pair_mlp_rank_count(uq: torch.Tensor, v: torch.Tensor, w2: torch.Tensor, b2:
     N.call("lkg_pair_mlp_count_f32", n_q, n_c, N.ptr(uq), _ld(uq), N.ptr(v), _ld(v), N.ptr(w2), N.ptr(b2), N.ptr(w3),
            N.ptr(b3), N.ptr(thr), N.ptr(truth_rows), N.ptr(better), N.ptr(equal), _stream())
     return better, equal, thr
+
+
+def pair_mlp_pairs(u: torch.Tensor, v: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor, w3: torch.Tensor,
+                   b3: torch.Tensor, u_idx: Optional[torch.Tensor] = None, v_idx: Optional[torch.Tensor] = None,
+                   labels: Optional[torch.Tensor] = None, thr: Optional[float] = None, want_logits: bool = True,
+                   out: Optional[torch.Tensor] = None, counts: Optional[torch.Tensor] = None):
+    """(logits, counts) of an explicit list of pairs under the folded head (lkg_pair_mlp_pairs_f32): pair i is (row
+    u_idx[i] of u, row v_idx[i] of v) of the two projected tables (n x 128 each; an index list of None means "pair i uses
+    row i"), its logit the bits pair_mlp_scores gives that pair.  The row indices must lie inside the tables.
+
+    logits: float32[P], or None with want_logits=False (out: an optional contiguous float32[P] to write them to).
+    counts: with labels (uint8 / bool [P], 0 or 1) and thr (a logit), an int64[5] device tensor tp, fp, tn, fn, nan -- a
+    pair is positive iff its logit > thr in float32, a NaN logit is counted in nan alone -- else None.  Passing counts (a
+    contiguous int64[5] on the device) ADDS to it, so batches accumulate; otherwise a zeroed one is made."""
+    _need_gpu(u_idx, v_idx, labels, out, counts)
+    u, v, w2, b2, w3, b3 = _pair_mlp_operands("pair_mlp_pairs", u, v, w2, b2, w3, b3)
+    dev = u.device
+    u_idx = _i64(u_idx.reshape(-1)) if u_idx is not None else None
+    v_idx = _i64(v_idx.reshape(-1)) if v_idx is not None else None
+    n_u = u_idx.numel() if u_idx is not None else u.shape[0]
+    n_v = v_idx.numel() if v_idx is not None else v.shape[0]
+    if n_u != n_v:
+        raise ValueError(f"pair_mlp_pairs: {n_u} rows of u against {n_v} rows of v: not a list of pairs")
+    n_pairs = n_u
+    if n_pairs > 2 ** 31 - 2:
+        raise ValueError(f"pair_mlp_pairs: {n_pairs} pairs in one launch (at most 2^31 - 2): use batches")
+    if n_pairs and ((u_idx is not None and u.shape[0] == 0) or (v_idx is not None and v.shape[0] == 0)):
+        raise ValueError("pair_mlp_pairs: row indices into an empty table")
+    want_counts = labels is not None or counts is not None
+    if want_counts:
+        if labels is None or thr is None:
+            raise ValueError("pair_mlp_pairs: the counts need labels and thr")
+        thr = float(thr)
+        if thr != thr:
+            raise ValueError("pair_mlp_pairs: thr is NaN")
+        if labels.dtype == torch.bool:
+            labels = labels.view(torch.uint8) if labels.is_contiguous() else labels.to(torch.uint8)
+        if labels.dtype != torch.uint8 or labels.dim() != 1 or labels.numel() != n_pairs:
+            raise ValueError(f"pair_mlp_pairs: labels must be a uint8 or bool tensor of {n_pairs} elements")
+        labels = labels.contiguous()
+        if counts is None:
+            counts = torch.zeros(5, dtype=torch.int64, device=dev)
+        elif counts.dtype != torch.int64 or counts.numel() != 5 or not counts.is_contiguous() or counts.device != dev:
+            raise ValueError(f"pair_mlp_pairs: counts must be a contiguous int64[5] on {dev}")
+    elif not want_logits:
+        raise ValueError("pair_mlp_pairs: nothing to compute (no logits wanted, no labels given)")
+    if want_logits:
+        if out is None:
+            out = torch.empty(n_pairs, dtype=torch.float32, device=dev)
+        elif out.dtype != torch.float32 or out.dim() != 1 or out.numel() != n_pairs or not out.is_contiguous() or \
+                out.device != dev:
+            raise ValueError(f"pair_mlp_pairs: out must be a contiguous float32[{n_pairs}] on {dev}")
+    else:
+        out = None
+    if n_pairs:
+        N.call("lkg_pair_mlp_pairs_f32", n_pairs, N.ptr(u), _ld(u), N.ptr(v), _ld(v), N.ptr(u_idx), N.ptr(v_idx),
+               N.ptr(w2), N.ptr(b2), N.ptr(w3), N.ptr(b3), N.ptr(labels) if want_counts else None,
+               thr if want_counts else 0.0, N.ptr(out), N.ptr(counts) if want_counts else None, _stream())
+    return out, (counts if want_counts else None)
+
+
+def binary_curve(scores: torch.Tensor, labels: torch.Tensor):
+    """(n_pos, n_neg, n_nan, n_groups, auc2, ap) of float32 scores and uint8 / bool labels (0 or 1), exact and tie-aware
+    (lkg_binary_curve_f32): NaN scores are counted in n_nan and take part in nothing else; ties are by float equality
+    (-0.0 == +0.0); n_groups is the number of distinct non-NaN scores; auc2 = sum over positives of (2 #{negatives
+    below} + #{negatives tied}), so ROC AUC = auc2 / (2 n_pos n_neg); ap is the average precision, the sum over the
+    distinct scores in descending order of (TP_g - TP_(g-1)) / n_pos * TP_g / (TP_g + FP_g), in float64 with the same bits
+    for any order of the input (0.0 without positives).  Five Python ints and a float; the call waits for the device."""
+    _need_gpu(scores, labels)
+    if scores.dtype != torch.float32 or scores.dim() != 1:
+        raise ValueError("binary_curve: scores must be a 1-D float32 tensor")
+    if labels.dtype == torch.bool:
+        labels = labels.view(torch.uint8) if labels.is_contiguous() else labels.to(torch.uint8)
+    if labels.dtype != torch.uint8 or labels.dim() != 1 or labels.numel() != scores.numel():
+        raise ValueError(f"binary_curve: labels must be a uint8 or bool tensor of {scores.numel()} elements")
+    n = scores.numel()
+    if n > 2 ** 31 - 2:
+        raise ValueError(f"binary_curve: {n} scores (at most 2^31 - 2)")
+    scores, labels = scores.contiguous(), labels.contiguous()
+    dev = scores.device
+    counts = torch.empty(5, dtype=torch.int64, device=dev)
+    ap = torch.empty(1, dtype=torch.float64, device=dev)
+    ws_bytes = int(N.load().lkg_binary_curve_workspace(n))
+    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+    N.call("lkg_binary_curve_f32", n, N.ptr(scores), N.ptr(labels), N.ptr(counts), N.ptr(ap), N.ptr(ws), ws_bytes,
+           _stream())
+    n_pos, n_neg, n_nan, n_groups, auc2 = (int(x) for x in counts.tolist())
+    return n_pos, n_neg, n_nan, n_groups, auc2, float(ap.item())

@@ -1,6 +1,7 @@
 """The MLP pair head at inference: all-pairs logits (``mlp_scores``, the MLP counterpart of ``calc_score``), the backend
-of ``predict_topk(scoring="mlp")``, and filtered ranking of held-out pairs under the head (``rank_pairs_mlp``,
-``evaluate_mlp_ranking``).
+of ``predict_topk(scoring="mlp")``, filtered ranking of held-out pairs under the head (``rank_pairs_mlp``,
+``evaluate_mlp_ranking``), and the head's downstream task itself: scores of an explicit list of pairs
+(``score_pairs_mlp``) and their binary-classification metrics against labels (``evaluate_mlp_classification``).
 
 The head of mode='mlp' is sigmoid(fc3(bn2(relu(fc2(bn1(relu(fc1([e_h | e_t])))))))).  At inference BatchNorm is affine per
 feature, bn(x) = a x + c with a = gamma / sqrt(running_var + eps), c = beta - running_mean a, and since ReLU comes
@@ -16,13 +17,14 @@ fc1 separates over the two entities, so every entity is projected once (the tall
 exact-f32 MFMA, fc3 in its epilogue -- runs in lkg_pairmlp.hip, which stores the logits or keeps a running filtered
 top-k per query without storing them.  Everything orders by the logit z: the sigmoid is
 monotone but saturates in f32.  A pair's logit has the same bits wherever it is computed: in ``mlp_scores``, in
-``predict_topk`` on either side, in any batch, split or candidate order.
+``predict_topk`` on either side, in ``rank_pairs_mlp``, in ``score_pairs_mlp``, in any batch, split or candidate order.
 
 BatchNorm always uses its running statistics here, whatever ``model.training`` says; the model's mode, parameters,
 buffers and caches are left as they are.
 """
 from __future__ import annotations
 
+import math
 from dataclasses import dataclass
 from typing import Dict, Optional, Sequence
 
@@ -272,3 +274,156 @@ def evaluate_mlp_ranking(model, h: torch.Tensor, t: torch.Tensor, r: Optional[to
     else:
         out[side] = metrics_from_counts(better, equal, ks)
     return out
+
+
+# ----------------------------------------------------------------------------- explicit pairs and their classification
+def _check_batch_size(batch_size):
+    if batch_size is not None and (isinstance(batch_size, bool) or int(batch_size) != batch_size or batch_size <= 0):
+        raise ValueError(f"batch_size must be a positive integer, got {batch_size!r}")
+
+
+def _check_pairs(h, t):
+    _check_ids("h", h)
+    _check_ids("t", t)
+    if h.numel() != t.numel():
+        raise ValueError(f"h and t have different lengths ({h.numel()}, {t.numel()})")
+
+
+def _pair_side(table: torch.Tensor, ids: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor],
+               unique: Optional[bool] = None):
+    """(rows, idx): one half of fc1 for a list of checked entity ids -- projected over the unique ids, idx the row of
+    every pair, when those are fewer than the pairs; else over the gathered rows, idx None ("pair i uses row i").  A
+    projected row does not depend on which rows are projected with it, so the choice (unique: None = by the counts,
+    True / False force a route) does not change a bit."""
+    uniq, inv = (None, None) if unique is False else torch.unique(ids, return_inverse=True)
+    if unique is None:
+        unique = uniq.numel() < ids.numel()
+    if unique:
+        return _project(ops.gather_rows(table, uniq), w, bias), inv
+    return _project(ops.gather_rows(table, ids), w, bias), None
+
+
+def _pair_logits(model, head: FoldedMLPHead, h, t, batch_size, labels=None, thr=None):
+    """(logits float32[P], counts int64[5] or None) of the checked-for-shape, non-empty pair list on the model's device"""
+    dev = model.entity_embed.weight.device
+    hid, tid = ops.checked_ids(model.n_entities, h.to(dev), t.to(dev))
+    ops.check_deferred_errors()
+    model.device = dev
+    p = hid.numel()
+    with torch.no_grad():
+        table = model._table_for_inference().detach()
+        _table_width_ok(head, table)
+        u, u_idx = _pair_side(table, hid, head.w1h, head.b1)
+        v, v_idx = _pair_side(table, tid, head.w1t, None)
+        z = torch.empty(p, dtype=torch.float32, device=dev)
+        counts = torch.zeros(5, dtype=torch.int64, device=dev) if labels is not None else None
+        step = p if batch_size is None else int(batch_size)
+        for lo in range(0, p, step):
+            hi = min(lo + step, p)
+            ops.pair_mlp_pairs(u if u_idx is not None else u[lo:hi], v if v_idx is not None else v[lo:hi], head.w2,
+                               head.b2, head.w3, head.b3, u_idx[lo:hi] if u_idx is not None else None,
+                               v_idx[lo:hi] if v_idx is not None else None,
+                               labels[lo:hi] if labels is not None else None, thr, True, z[lo:hi], counts)
+    return z, counts
+
+
+def score_pairs_mlp(model, h: torch.Tensor, t: torch.Tensor, logits: bool = False,
+                    batch_size: Optional[int] = None) -> torch.Tensor:
+    """float32[P]: the head's probability -- or logit -- of every pair (h_i, t_i) on the model's inference table: what
+    model(h, t, mode='mlp') gives in eval mode, through the folded head (see the module docstring), each logit with the
+    bits mlp_scores gives that pair.  Every distinct entity is projected once.  batch_size: pairs per launch (None: all);
+    it does not change the result.  BatchNorm is in inference form whatever model.training says; the model's mode,
+    parameters, buffers and caches are left as they are."""
+    _check_pairs(h, t)
+    _check_batch_size(batch_size)
+    head = fold_mlp_head(model)                          # (AttributeError without initialize_MLP)
+    if h.numel() == 0:
+        return torch.empty(0, dtype=torch.float32, device=model.entity_embed.weight.device)
+    z, _ = _pair_logits(model, head, h, t, batch_size)
+    return z if logits else _sigmoid_(z)
+
+
+def logit_of_probability(p: float) -> float:
+    """float32(log(p / (1 - p))) formed in float64, as a Python float: the logit threshold of a probability threshold
+    strictly inside (0, 1).  0.5 is the logit 0.0 exactly."""
+    p = float(p)
+    if not 0.0 < p < 1.0:
+        raise ValueError(f"threshold must be a probability strictly inside (0, 1), got {p!r}")
+    return float(torch.tensor(math.log(p / (1.0 - p)), dtype=torch.float64).to(torch.float32))
+
+
+def classification_metrics(tp: int, fp: int, tn: int, fn: int, nan: int, n_pos: int, n_neg: int,
+                           curve=None) -> Dict:
+    """The dict of evaluate_mlp_classification from the confusion counts, the label counts and binary_curve's six
+    values (None: no pair was scored).  accuracy, precision, recall and f1 follow the reference's utils/metric_utils.py:
+    accuracy over ALL pairs (a NaN prediction is wrong), precision / recall 0 with an empty denominator, f1 0 when both
+    are 0."""
+    n = tp + fp + tn + fn + nan
+    precision = tp / (tp + fp) if tp + fp else 0.0
+    recall = tp / (tp + fn) if tp + fn else 0.0
+    f1 = (2.0 * precision * recall) / (precision + recall) if precision + recall > 0 else 0.0
+    roc_auc = average_precision = float("nan")
+    if curve is not None:
+        c_pos, c_neg, _, _, auc2, ap = curve
+        if c_pos > 0 and c_neg > 0:
+            roc_auc, average_precision = auc2 / (2 * c_pos * c_neg), ap
+    return {"accuracy": (tp + tn) / n if n else 0.0, "precision": precision, "recall": recall, "f1": f1,
+            "tp": tp, "fp": fp, "tn": tn, "fn": fn, "nan": nan, "n": n, "n_pos": n_pos, "n_neg": n_neg,
+            "roc_auc": roc_auc, "average_precision": average_precision}
+
+
+def _check_labels(labels, n):
+    if not isinstance(labels, torch.Tensor) or labels.dim() != 1 or labels.is_complex():
+        raise ValueError("labels must be a 1-D bool, integer or float tensor of 0 / 1")
+    if labels.numel() != n:
+        raise ValueError(f"h and labels have different lengths ({n}, {labels.numel()})")
+    if labels.dtype != torch.bool and not bool(((labels == 0) | (labels == 1)).all()):
+        raise ValueError("labels must be 0 or 1")
+
+
+def evaluate_mlp_classification(model, h: torch.Tensor, t: torch.Tensor, labels: torch.Tensor, threshold: float = 0.5,
+                                logit_threshold: Optional[float] = None, batch_size: Optional[int] = None) -> Dict:
+    """Binary classification of the labelled pairs (h_i, t_i) under the MLP pair head, the reference's downstream
+    evaluation (utils/model_utils.py:133-158) with its baselines' curve metrics:
+
+        accuracy, precision, recall, f1        the formulas and zero conventions of utils/metric_utils.py; accuracy is
+                                               over all pairs, so a NaN prediction is wrong
+        tp, fp, tn, fn, nan, n, n_pos, n_neg   the counts behind them (nan: pairs whose logit is NaN; n_pos / n_neg: the
+                                               labels, n = n_pos + n_neg = tp + fp + tn + fn + nan)
+        roc_auc, average_precision             exact and tie-aware over the pairs whose logit is not NaN (tied scores
+                                               count as halves; average precision is the step-function sum, not the
+                                               trapezoid); NaN when either class is empty among them
+
+    labels: a 1-D bool, integer or float tensor of 0 / 1.  threshold: a probability strictly inside (0, 1), applied on
+    the logit as float32(log(p / (1 - p))) formed in float64 (0.5 is the logit 0.0 exactly); logit_threshold overrides
+    it (any float but NaN).  A pair is positive iff its logit > that threshold.  The logits are those of
+    score_pairs_mlp, computed once for the counts (taken in the scoring kernel) and the curve (lkg_binary_curve_f32).
+    batch_size: pairs per launch; it changes nothing.  Runs in eval mode and restores the model's previous mode.
+
+    One deliberate difference from the reference: decisions are taken on the logit, where the reference rounds the float32
+    probability.  sigmoid(z) rounds to exactly 0.5 in float32 for 0 < z < ~6e-8, which .round() sends to 0; here such a
+    pair is positive."""
+    _check_pairs(h, t)
+    _check_labels(labels, h.numel())
+    _check_batch_size(batch_size)
+    if logit_threshold is None:
+        thr = logit_of_probability(threshold)
+    else:
+        thr = float(logit_threshold)
+        if thr != thr:
+            raise ValueError("logit_threshold is NaN")
+    head = fold_mlp_head(model)                          # (AttributeError without initialize_MLP)
+    was_training = model.training
+    model.eval()
+    try:
+        if h.numel() == 0:
+            return classification_metrics(0, 0, 0, 0, 0, 0, 0)
+        dev = model.entity_embed.weight.device
+        lab = (labels != 0).to(dev).view(torch.uint8)
+        z, counts = _pair_logits(model, head, h, t, batch_size, lab, thr)
+        curve = ops.binary_curve(z, lab)
+        tp, fp, tn, fn, nan = (int(x) for x in counts.tolist())
+        n_pos = int(lab.sum())
+    finally:
+        model.train(was_training)
+    return classification_metrics(tp, fp, tn, fn, nan, n_pos, h.numel() - n_pos, curve)
