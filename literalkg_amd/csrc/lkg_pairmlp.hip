@@ -67,6 +67,17 @@ __device__ __forceinline__ void pm_load_v(float4 (&vf)[PM_H1 / 16], const float 
     for (int t = 0; t < PM_H1 / 16; ++t) vf[t] = *reinterpret_cast<const float4 *>(vrow + 16 * t + 4 * s);
 }
 
+// Opens candidate tile t for the wave: vf = its 16 V rows (rows past the end repeat the last one: computed, never
+// used), cw = the candidate that lane (r < 4, s) speaks for; true when the lane speaks for one
+__device__ __forceinline__ bool pm_open_tile(float4 (&vf)[PM_H1 / 16], long &cw, long t, int wave, int r, int s,
+                                             const float *__restrict__ vt, long ldv, long n_c) {
+    const long c0 = t * PM_COLS + wave * 16;
+    const long crow = c0 + r < n_c ? c0 + r : n_c - 1;
+    pm_load_v(vf, vt + crow * ldv, s);
+    cw = c0 + 4 * s + (r & 3);
+    return r < 4 && cw < n_c;
+}
+
 // Where row r of the A operand comes from: x1(t) = elements 16 t + 4 s .. + 3 of relu(u + v) for the lane's row.
 // PmBroadcastU: one u row in LDS for all 16 candidates (the query of the store / select / count / prepare kernels).
 // PmOwnX: every row a pair of its own, its relu(u + v) already formed from the lane's own u and v fragments.
@@ -157,12 +168,9 @@ __global__ __launch_bounds__(PM_THREADS) void pair_mlp_store_kernel(
     pm_load_weights(w, w2, b2, w3, b3, r, s);
     __syncthreads();
     for (long t = t_lo; t < t_hi; ++t) {
-        const long c0 = t * PM_COLS + wave * 16;
-        const long crow = c0 + r < n_c ? c0 + r : n_c - 1;        // rows past the end: computed, never stored
         float4 vf[PM_H1 / 16];
-        pm_load_v(vf, vt + crow * ldv, s);
-        const long cw = c0 + 4 * s + (r & 3);
-        const bool mine = r < 4 && cw < n_c;
+        long cw;
+        const bool mine = pm_open_tile(vf, cw, t, wave, r, s, vt, ldv, n_c);
         for (int qi = 0; qi < nq; ++qi) {
             float z[4];
             pm_pair_logits(z, su + qi * PM_H1, vf, w, s);
@@ -205,6 +213,7 @@ __global__ __launch_bounds__(PM_THREADS) void pair_mlp_select_kernel(
     pm_load_weights(w, w2, b2, w3, b3, r, s);
     __syncthreads();
     for (long t = t_lo; t < t_hi; ++t) {
+        // (pm_open_tile by hand: through the helper this kernel's registers are allocated differently)
         const long c0 = t * PM_COLS + wave * 16;
         const long crow = c0 + r < n_c ? c0 + r : n_c - 1;        // rows past the end: computed, never pushed
         float4 vf[PM_H1 / 16];
@@ -352,13 +361,10 @@ __global__ __launch_bounds__(PM_THREADS) void pair_mlp_count_kernel(
     for (int x = 0; x < 4; ++x) pick[x] = r == x ? -1 : 0;
     int nb = 0, ne = 0;
     for (long t = t_lo; t < t_hi; ++t) {
-        const long c0 = t * PM_COLS + wave * 16;
-        const long crow = c0 + r < n_c ? c0 + r : n_c - 1;        // rows past the end: computed, never counted
         float4 vf[PM_H1 / 16];
-        pm_load_v(vf, vt + crow * ldv, s);
-        const long cw = c0 + 4 * s + (r & 3);
+        long cw;
+        const int none = pm_open_tile(vf, cw, t, wave, r, s, vt, ldv, n_c) ? 0 : 0x7fc00000;
         const int cwi = (int)cw;
-        const int none = (r < 4 && cw < n_c) ? 0 : 0x7fc00000;
         for (int qi = 0; qi < nq; ++qi) {
             float z[4];
             pm_pair_logits(z, su + qi * PM_H1, vf, w, s);
@@ -464,6 +470,15 @@ bool pm_operands_ok(const float *uq, long ldu, const float *v, long ldv, const f
            ldv >= PM_H1;
 }
 
+// What an entry point asks of its operands (`a`: its first table, `rest`: its other pointers that may not be null) and filter.
+// Statements of the entry point's body, which read its parameters v, w2, b2, w3, b3, ldu, ldv (and the filter's six) by name.
+#define PM_REQUIRE_OPERANDS(name, a, rest)                                                                             \
+    LKG_REQUIRE(a && v && w2 && b2 && w3 && b3 && rest, name ": null pointer");                                        \
+    LKG_REQUIRE(pm_operands_ok(a, ldu, v, ldv, w2),                                                                    \
+                name ": " #a ", v and w2 must be 16-byte aligned with row strides that are multiples of 4 (at least 128)")
+#define PM_REQUIRE_FILTER(name) \
+    LKG_REQUIRE(!rowptr || (filter_row && filter_rel && col && eptr && rel), name ": incomplete filter")
+
 }  // namespace
 
 extern "C" int32_t lkg_pair_mlp_splits(int64_t n_q, int64_t n_cand, int32_t requested) {
@@ -481,10 +496,7 @@ extern "C" int lkg_pair_mlp_scores_f32(int64_t n_q, int64_t n_cand, const float 
                                        float *out, int64_t ldo, void *stream) {
     LKG_REQUIRE(n_q >= 0 && n_cand >= 0 && ldo >= n_cand, "lkg_pair_mlp_scores_f32: bad sizes");
     if (n_q == 0 || n_cand == 0) return LKG_OK;
-    LKG_REQUIRE(uq && v && w2 && b2 && w3 && b3 && out, "lkg_pair_mlp_scores_f32: null pointer");
-    LKG_REQUIRE(pm_operands_ok(uq, ldu, v, ldv, w2),
-                "lkg_pair_mlp_scores_f32: uq, v and w2 must be 16-byte aligned with row strides that are multiples of 4 "
-                "(at least 128)");
+    PM_REQUIRE_OPERANDS("lkg_pair_mlp_scores_f32", uq, out);
     const long tiles_q = (n_q + PM_ROWS - 1) / PM_ROWS, tiles_c = (n_cand + PM_COLS - 1) / PM_COLS;
     const long chunks = (tiles_c + PM_STORE_TILES - 1) / PM_STORE_TILES;
     LKG_REQUIRE(tiles_q * chunks < INT32_MAX, "lkg_pair_mlp_scores_f32: too many workgroups (split the queries)");
@@ -505,11 +517,8 @@ extern "C" int lkg_pair_mlp_select_f32(int64_t n_q, int64_t n_cand, const float 
     if (n_q == 0) return LKG_OK;
     LKG_REQUIRE(splits >= 1 && splits == lkg_pair_mlp_splits(n_q, n_cand, splits),
                 "lkg_pair_mlp_select_f32: splits must come from lkg_pair_mlp_splits");
-    LKG_REQUIRE(uq && v && w2 && b2 && w3 && b3 && ws_s && ws_i, "lkg_pair_mlp_select_f32: null pointer");
-    LKG_REQUIRE(pm_operands_ok(uq, ldu, v, ldv, w2),
-                "lkg_pair_mlp_select_f32: uq, v and w2 must be 16-byte aligned with row strides that are multiples of 4 "
-                "(at least 128)");
-    LKG_REQUIRE(!rowptr || (filter_row && filter_rel && col && eptr && rel), "lkg_pair_mlp_select_f32: incomplete filter");
+    PM_REQUIRE_OPERANDS("lkg_pair_mlp_select_f32", uq, ws_s && ws_i);
+    PM_REQUIRE_FILTER("lkg_pair_mlp_select_f32");
     const long qr = pm_select_rows(n_q);
     const long tiles_q = (n_q + qr - 1) / qr, tiles_c = (n_cand + PM_COLS - 1) / PM_COLS;
     LKG_REQUIRE(tiles_q * splits < INT32_MAX, "lkg_pair_mlp_select_f32: too many workgroups (split the queries)");
@@ -537,12 +546,8 @@ extern "C" int lkg_pair_mlp_prepare_f32(int64_t n_q, int64_t n_cand, const float
                                         int32_t *better, int32_t *equal, void *stream) {
     LKG_REQUIRE(n_q >= 0 && n_cand > 0 && n_cand < INT32_MAX, "lkg_pair_mlp_prepare_f32: bad sizes");
     if (n_q == 0) return LKG_OK;
-    LKG_REQUIRE(uq && v && w2 && b2 && w3 && b3 && truth && thr && better && equal,
-                "lkg_pair_mlp_prepare_f32: null pointer");
-    LKG_REQUIRE(pm_operands_ok(uq, ldu, v, ldv, w2),
-                "lkg_pair_mlp_prepare_f32: uq, v and w2 must be 16-byte aligned with row strides that are multiples of 4 "
-                "(at least 128)");
-    LKG_REQUIRE(!rowptr || (filter_row && filter_rel && col && eptr && rel), "lkg_pair_mlp_prepare_f32: incomplete filter");
+    PM_REQUIRE_OPERANDS("lkg_pair_mlp_prepare_f32", uq, truth && thr && better && equal);
+    PM_REQUIRE_FILTER("lkg_pair_mlp_prepare_f32");
     LKG_REQUIRE(!rowptr || (n_rows > 0 && n_rows < INT32_MAX && (cand_slot || n_rows == n_cand)),
                 "lkg_pair_mlp_prepare_f32: the filter's rows must be the candidates, or come with cand_slot");
     const long blocks = (n_q + PM_PREP_WAVES - 1) / PM_PREP_WAVES;
@@ -560,11 +565,7 @@ extern "C" int lkg_pair_mlp_count_f32(int64_t n_q, int64_t n_cand, const float *
                                       void *stream) {
     LKG_REQUIRE(n_q >= 0 && n_cand >= 0 && n_cand < INT32_MAX, "lkg_pair_mlp_count_f32: bad sizes");
     if (n_q == 0 || n_cand == 0) return LKG_OK;
-    LKG_REQUIRE(uq && v && w2 && b2 && w3 && b3 && thr && truth && better && equal,
-                "lkg_pair_mlp_count_f32: null pointer");
-    LKG_REQUIRE(pm_operands_ok(uq, ldu, v, ldv, w2),
-                "lkg_pair_mlp_count_f32: uq, v and w2 must be 16-byte aligned with row strides that are multiples of 4 "
-                "(at least 128)");
+    PM_REQUIRE_OPERANDS("lkg_pair_mlp_count_f32", uq, thr && truth && better && equal);
     const long tiles_q = (n_q + PM_ROWS - 1) / PM_ROWS, tiles_c = (n_cand + PM_COLS - 1) / PM_COLS;
     const long splits = pm_count_splits(tiles_q, tiles_c);
     LKG_REQUIRE(tiles_q * splits < INT32_MAX, "lkg_pair_mlp_count_f32: too many workgroups (split the queries)");
@@ -583,10 +584,7 @@ extern "C" int lkg_pair_mlp_pairs_f32(int64_t n_pairs, const float *u, int64_t l
     LKG_REQUIRE(out || counts, "lkg_pair_mlp_pairs_f32: nothing to write (out and counts are both null)");
     LKG_REQUIRE(!counts || labels, "lkg_pair_mlp_pairs_f32: counts need labels (null pointer)");
     if (n_pairs == 0) return LKG_OK;
-    LKG_REQUIRE(u && v && w2 && b2 && w3 && b3, "lkg_pair_mlp_pairs_f32: null pointer");
-    LKG_REQUIRE(pm_operands_ok(u, ldu, v, ldv, w2),
-                "lkg_pair_mlp_pairs_f32: u, v and w2 must be 16-byte aligned with row strides that are multiples of 4 "
-                "(at least 128)");
+    PM_REQUIRE_OPERANDS("lkg_pair_mlp_pairs_f32", u, true);
     const long blocks = (n_pairs + PM_COLS - 1) / PM_COLS;
     hipLaunchKernelGGL(pair_mlp_pairs_kernel, dim3((unsigned)(blocks < PM_PAIRS_GRID ? blocks : PM_PAIRS_GRID)),
                        dim3(PM_THREADS), 0, (hipStream_t)stream, (long)n_pairs, u, (long)ldu, v, (long)ldv,

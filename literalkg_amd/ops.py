@@ -2201,6 +2201,18 @@ def rank_queries(p: torch.Tensor, ids: torch.Tensor, e: Optional[torch.Tensor] =
     return q
 
 
+def _filter_args(what: str, filt, filter_row: Optional[torch.Tensor], filter_rel: Optional[torch.Tensor], n_q: int):
+    """fargs(lo, hi): the six filter arguments (filter_row, filter_rel, rowptr, col, eptr, rel) of a launch over the
+    queries lo .. hi of n_q (default: all) -- six None without a filter.  The kernels index filter_row / filter_rel by
+    query, so each needs n_q entries.  fargs holds the converted lists: keep it while launches use the pointers."""
+    if filt is None:
+        return lambda lo=None, hi=None: [None] * 6
+    row, rel = _i64(filter_row.reshape(-1)), _i64(filter_rel.reshape(-1))
+    if row.numel() != n_q or rel.numel() != n_q:
+        raise ValueError(f"{what}: {row.numel()} filter rows and {rel.numel()} filter relations for {n_q} queries")
+    return lambda lo=None, hi=None: [N.ptr(row[lo:hi]), N.ptr(rel[lo:hi]), *map(N.ptr, filt)]
+
+
 def rank_count(q: torch.Tensor, p: torch.Tensor, pn: Optional[torch.Tensor], truth: torch.Tensor,
                filt=None, filter_row: Optional[torch.Tensor] = None, filter_rel: Optional[torch.Tensor] = None):
     """(better, equal, thr) int32 / int32 / f32 per query row of q against every row of p: lkg_rank_prepare_f32 (the
@@ -2215,16 +2227,11 @@ def rank_count(q: torch.Tensor, p: torch.Tensor, pn: Optional[torch.Tensor], tru
     better = torch.empty(n_q, dtype=torch.int32, device=dev)
     equal = torch.empty(n_q, dtype=torch.int32, device=dev)
     thr = torch.empty(n_q, dtype=torch.float32, device=dev)
-    if filt is not None:
-        rowptr, col, eptr, rel = filt
-        if rowptr.numel() != p.shape[0] + 1:
-            raise ValueError(f"rank_count: the filter covers {rowptr.numel() - 1} rows, the candidates {p.shape[0]}")
-        filter_row, filter_rel = _i64(filter_row.reshape(-1)), _i64(filter_rel.reshape(-1))
-        fargs = [N.ptr(filter_row), N.ptr(filter_rel), N.ptr(rowptr), N.ptr(col), N.ptr(eptr), N.ptr(rel)]
-    else:
-        fargs = [None] * 6
+    if filt is not None and filt[0].numel() != p.shape[0] + 1:
+        raise ValueError(f"rank_count: the filter covers {filt[0].numel() - 1} rows, the candidates {p.shape[0]}")
+    fargs = _filter_args("rank_count", filt, filter_row, filter_rel, n_q)
     N.call("lkg_rank_prepare_f32", n_q, p.shape[0], k, N.ptr(q), _ld(q), N.ptr(p), _ld(p), N.ptr(pn), N.ptr(truth),
-           *fargs, N.ptr(thr), N.ptr(better), N.ptr(equal), _stream())
+           *fargs(), N.ptr(thr), N.ptr(better), N.ptr(equal), _stream())
     N.call("lkg_rank_count_f32", n_q, p.shape[0], k, N.ptr(q), _ld(q), N.ptr(p), _ld(p), N.ptr(pn), N.ptr(thr),
            N.ptr(truth), N.ptr(better), N.ptr(equal), _stream())
     return better, equal, thr
@@ -2234,6 +2241,33 @@ def rank_count(q: torch.Tensor, p: torch.Tensor, pn: Optional[torch.Tensor], tru
 TOPK_MAX = 128
 TOPK_MAX_SPLITS = 64
 TOPK_WORKSPACE_BYTES = 256 << 20
+
+
+def _check_k_splits(what: str, k, splits):
+    k, splits = int(k), int(splits)
+    if not 1 <= k <= TOPK_MAX:
+        raise ValueError(f"{what}: k must lie in [1, {TOPK_MAX}], got {k}")
+    if not 0 <= splits <= TOPK_MAX_SPLITS:
+        raise ValueError(f"{what}: splits must lie in [0, {TOPK_MAX_SPLITS}], got {splits}")
+    return k, splits
+
+
+def _split_launches(splits_symbol: str, select, n_c: int, splits: int, fargs, *, qn, ids, scores, values):
+    """A top-k in launches over query rows lo .. hi whose workspace (S x rows x k x 8 bytes) stays within
+    TOPK_WORKSPACE_BYTES: S = splits_symbol(rows, n_c, splits); select(lo, hi, tail), the caller's select entry point, its
+    arguments ending in tail (fargs(lo, hi), k, S, the workspaces, the stream); lkg_topk_merge_f32 into [lo:hi] of the
+    results (qn: the queries' squared norms for values, or None)."""
+    lib, dev, (n_q, k) = N.load(), ids.device, ids.shape
+    step = max(64, TOPK_WORKSPACE_BYTES // (TOPK_MAX_SPLITS * k * 8) // 64 * 64)     # rows per launch (worst-case S)
+    for lo in range(0, n_q, step):
+        hi = min(n_q, lo + step)
+        m = hi - lo
+        s_ = int(getattr(lib, splits_symbol)(m, n_c, splits))
+        ws_s = torch.empty(s_ * m * k, dtype=torch.float32, device=dev)
+        ws_i = torch.empty(s_ * m * k, dtype=torch.int32, device=dev)
+        select(lo, hi, (*fargs(lo, hi), k, s_, N.ptr(ws_s), N.ptr(ws_i), _stream()))
+        N.call("lkg_topk_merge_f32", m, k, s_, N.ptr(ws_s), N.ptr(ws_i), N.ptr(qn[lo:hi]) if qn is not None else None,
+               N.ptr(ids[lo:hi]), N.ptr(scores[lo:hi]), N.ptr(values[lo:hi]), _stream())
 
 
 def topk_select(q: torch.Tensor, p: torch.Tensor, pn: Optional[torch.Tensor], k: int, filt=None,
@@ -2247,11 +2281,7 @@ def topk_select(q: torch.Tensor, p: torch.Tensor, pn: Optional[torch.Tensor], k:
     splits: candidate splits per launch (0 = automatic, at most TOPK_MAX_SPLITS); the result does not depend on it.
     The queries run in launches whose workspace (S x rows x k x 8 bytes) stays within TOPK_WORKSPACE_BYTES."""
     _need_gpu(q, p, pn, cand_ids, filter_row, filter_rel)
-    k, splits = int(k), int(splits)
-    if not 1 <= k <= TOPK_MAX:
-        raise ValueError(f"topk_select: k must lie in [1, {TOPK_MAX}], got {k}")
-    if not 0 <= splits <= TOPK_MAX_SPLITS:
-        raise ValueError(f"topk_select: splits must lie in [0, {TOPK_MAX_SPLITS}], got {splits}")
+    k, splits = _check_k_splits("topk_select", k, splits)
     q, p = _f32_rows(q), _f32_rows(p)
     n_q, kd = q.shape
     n_c = p.shape[0]
@@ -2265,29 +2295,13 @@ def topk_select(q: torch.Tensor, p: torch.Tensor, pn: Optional[torch.Tensor], k:
         return ids, scores, values
     qn = rank_sqnorm(q) if pn is not None else None
     cand_ids = _i64(cand_ids.reshape(-1)) if cand_ids is not None else None
-    if filt is not None:
-        rowptr, col, eptr, rel = filt
-        filter_row = _i64(filter_row.reshape(-1))
-        filter_rel = _i64(filter_rel.reshape(-1))
-        if filter_row.numel() != n_q or filter_rel.numel() != n_q:
-            raise ValueError(f"topk_select: {filter_row.numel()} filter rows for {n_q} queries")
-    lib = N.load()
-    step = max(64, TOPK_WORKSPACE_BYTES // (TOPK_MAX_SPLITS * k * 8) // 64 * 64)     # rows per launch (worst-case S)
-    for lo in range(0, n_q, step):
-        hi = min(n_q, lo + step)
-        m = hi - lo
-        s_ = int(lib.lkg_topk_splits(m, n_c, splits))
-        ws_s = torch.empty(s_ * m * k, dtype=torch.float32, device=dev)
-        ws_i = torch.empty(s_ * m * k, dtype=torch.int32, device=dev)
+    fargs = _filter_args("topk_select", filt, filter_row, filter_rel, n_q)
+
+    def select(lo, hi, tail):
         qq = q[lo:hi]
-        fargs = [None] * 6
-        if filt is not None:
-            fargs = [N.ptr(filter_row[lo:hi]), N.ptr(filter_rel[lo:hi]), N.ptr(rowptr), N.ptr(col), N.ptr(eptr),
-                     N.ptr(rel)]
-        N.call("lkg_topk_select_f32", m, n_c, kd, N.ptr(qq), _ld(qq), N.ptr(p), _ld(p), N.ptr(pn), N.ptr(cand_ids),
-               *fargs, k, s_, N.ptr(ws_s), N.ptr(ws_i), _stream())
-        N.call("lkg_topk_merge_f32", m, k, s_, N.ptr(ws_s), N.ptr(ws_i), N.ptr(qn[lo:hi]) if qn is not None else None,
-               N.ptr(ids[lo:hi]), N.ptr(scores[lo:hi]), N.ptr(values[lo:hi]), _stream())
+        N.call("lkg_topk_select_f32", hi - lo, n_c, kd, N.ptr(qq), _ld(qq), N.ptr(p), _ld(p), N.ptr(pn), N.ptr(cand_ids),
+               *tail)
+    _split_launches("lkg_topk_splits", select, n_c, splits, fargs, qn=qn, ids=ids, scores=scores, values=values)
     return ids, scores, values
 
 
@@ -2342,11 +2356,7 @@ def pair_mlp_topk(uq: torch.Tensor, v: torch.Tensor, w2: torch.Tensor, b2: torch
     pair_mlp_scores -- the same bits -- ties by the smaller id, NaN never selected; the n_q x n_c logits are never stored
     (lkg_pair_mlp_select_f32, lkg_topk_merge_f32).  ids, filt / filter_row / filter_rel, cand_ids, splits, the padding
     (-1 / NaN) and the workspace bound are those of topk_select."""
-    k, splits = int(k), int(splits)
-    if not 1 <= k <= TOPK_MAX:
-        raise ValueError(f"pair_mlp_topk: k must lie in [1, {TOPK_MAX}], got {k}")
-    if not 0 <= splits <= TOPK_MAX_SPLITS:
-        raise ValueError(f"pair_mlp_topk: splits must lie in [0, {TOPK_MAX_SPLITS}], got {splits}")
+    k, splits = _check_k_splits("pair_mlp_topk", k, splits)
     _need_gpu(cand_ids, filter_row, filter_rel)
     uq, v, w2, b2, w3, b3 = _pair_mlp_operands("pair_mlp_topk", uq, v, w2, b2, w3, b3)
     n_q, n_c = uq.shape[0], v.shape[0]
@@ -2359,29 +2369,13 @@ def pair_mlp_topk(uq: torch.Tensor, v: torch.Tensor, w2: torch.Tensor, b2: torch
         return ids, logits
     scores = torch.empty((n_q, k), dtype=torch.float32, device=dev)          # s = -2 z, the order's key
     cand_ids = _i64(cand_ids.reshape(-1)) if cand_ids is not None else None
-    if filt is not None:
-        rowptr, col, eptr, rel = filt
-        filter_row = _i64(filter_row.reshape(-1))
-        filter_rel = _i64(filter_rel.reshape(-1))
-        if filter_row.numel() != n_q or filter_rel.numel() != n_q:
-            raise ValueError(f"pair_mlp_topk: {filter_row.numel()} filter rows for {n_q} queries")
-    lib = N.load()
-    step = max(64, TOPK_WORKSPACE_BYTES // (TOPK_MAX_SPLITS * k * 8) // 64 * 64)     # rows per launch (worst-case S)
-    for lo in range(0, n_q, step):
-        hi = min(n_q, lo + step)
-        m = hi - lo
-        s_ = int(lib.lkg_pair_mlp_splits(m, n_c, splits))
-        ws_s = torch.empty(s_ * m * k, dtype=torch.float32, device=dev)
-        ws_i = torch.empty(s_ * m * k, dtype=torch.int32, device=dev)
+    fargs = _filter_args("pair_mlp_topk", filt, filter_row, filter_rel, n_q)
+
+    def select(lo, hi, tail):
         qq = uq[lo:hi]
-        fargs = [None] * 6
-        if filt is not None:
-            fargs = [N.ptr(filter_row[lo:hi]), N.ptr(filter_rel[lo:hi]), N.ptr(rowptr), N.ptr(col), N.ptr(eptr),
-                     N.ptr(rel)]
-        N.call("lkg_pair_mlp_select_f32", m, n_c, N.ptr(qq), _ld(qq), N.ptr(v), _ld(v), N.ptr(w2), N.ptr(b2), N.ptr(w3),
-               N.ptr(b3), N.ptr(cand_ids), *fargs, k, s_, N.ptr(ws_s), N.ptr(ws_i), _stream())
-        N.call("lkg_topk_merge_f32", m, k, s_, N.ptr(ws_s), N.ptr(ws_i), None, N.ptr(ids[lo:hi]), N.ptr(scores[lo:hi]),
-               N.ptr(logits[lo:hi]), _stream())
+        N.call("lkg_pair_mlp_select_f32", hi - lo, n_c, N.ptr(qq), _ld(qq), N.ptr(v), _ld(v), N.ptr(w2), N.ptr(b2),
+               N.ptr(w3), N.ptr(b3), N.ptr(cand_ids), *tail)
+    _split_launches("lkg_pair_mlp_splits", select, n_c, splits, fargs, qn=None, ids=ids, scores=scores, values=logits)
     return ids, logits
 
 
@@ -2405,8 +2399,8 @@ def pair_mlp_rank_count(uq: torch.Tensor, v: torch.Tensor, w2: torch.Tensor, b2:
     than the truth strictly above / exactly at it; the n_q x n_c logits are never stored (lkg_pair_mlp_prepare_f32, then
     lkg_pair_mlp_count_f32).  truth_rows are rows of v.  filt = (rowptr, col, eptr, rel) of csr_build_device over entity
     ids; query i leaves out the cols of row filter_row[i] under relation filter_rel[i] (-1: under any).  cand_ids: the
-    (unique) entity id of every row of v (None: the row number); filter entries outside them are not candidates.  cand_slot: pair_mlp_cand_slot of
-    cand_ids, for a caller that counts batch after batch against the same candidates."""
+    (unique) entity id of every row of v (None: the row number); filter entries outside them are not candidates.
+    cand_slot: pair_mlp_cand_slot of cand_ids, for a caller that counts batch after batch against the same candidates."""
     _need_gpu(truth_rows, filter_row, filter_rel, cand_ids, cand_slot)
     uq, v, w2, b2, w3, b3 = _pair_mlp_operands("pair_mlp_rank_count", uq, v, w2, b2, w3, b3)
     n_q, n_c = uq.shape[0], v.shape[0]
@@ -2423,25 +2417,31 @@ def pair_mlp_rank_count(uq: torch.Tensor, v: torch.Tensor, w2: torch.Tensor, b2:
     thr = torch.empty(n_q, dtype=torch.float32, device=dev)
     if n_q == 0:
         return better, equal, thr
-    n_rows, slot, fargs = n_c, None, [None] * 6
+    n_rows, slot = n_c, None
     if filt is not None:
-        rowptr, col, eptr, rel = filt
-        n_rows = rowptr.numel() - 1
+        n_rows = filt[0].numel() - 1
         if cand_ids is None and n_rows != n_c:
             raise ValueError(f"pair_mlp_rank_count: the filter covers {n_rows} rows, the candidates {n_c}")
-        filter_row, filter_rel = _i64(filter_row.reshape(-1)), _i64(filter_rel.reshape(-1))
-        if filter_row.numel() != n_q or filter_rel.numel() != n_q:
-            raise ValueError(f"pair_mlp_rank_count: {filter_row.numel()} filter rows for {n_q} queries")
-        if cand_ids is not None:
-            slot = cand_slot if cand_slot is not None else pair_mlp_cand_slot(n_rows, cand_ids)
-            if slot.numel() != n_rows or slot.dtype != torch.int32 or not slot.is_contiguous():
-                raise ValueError(f"pair_mlp_rank_count: cand_slot must be a contiguous int32[{n_rows}]")
-        fargs = [N.ptr(filter_row), N.ptr(filter_rel), N.ptr(rowptr), N.ptr(col), N.ptr(eptr), N.ptr(rel)]
+    fargs = _filter_args("pair_mlp_rank_count", filt, filter_row, filter_rel, n_q)
+    if filt is not None and cand_ids is not None:
+        slot = cand_slot if cand_slot is not None else pair_mlp_cand_slot(n_rows, cand_ids)
+        if slot.numel() != n_rows or slot.dtype != torch.int32 or not slot.is_contiguous():
+            raise ValueError(f"pair_mlp_rank_count: cand_slot must be a contiguous int32[{n_rows}]")
     N.call("lkg_pair_mlp_prepare_f32", n_q, n_c, N.ptr(uq), _ld(uq), N.ptr(v), _ld(v), N.ptr(w2), N.ptr(b2), N.ptr(w3),
-           N.ptr(b3), N.ptr(truth_rows), n_rows, N.ptr(slot), *fargs, N.ptr(thr), N.ptr(better), N.ptr(equal), _stream())
+           N.ptr(b3), N.ptr(truth_rows), n_rows, N.ptr(slot), *fargs(), N.ptr(thr), N.ptr(better), N.ptr(equal),
+           _stream())
     N.call("lkg_pair_mlp_count_f32", n_q, n_c, N.ptr(uq), _ld(uq), N.ptr(v), _ld(v), N.ptr(w2), N.ptr(b2), N.ptr(w3),
            N.ptr(b3), N.ptr(thr), N.ptr(truth_rows), N.ptr(better), N.ptr(equal), _stream())
     return better, equal, thr
+
+
+def _u8_labels(what: str, labels: torch.Tensor, n: int) -> torch.Tensor:
+    """uint8 / bool labels, one per score, as the contiguous uint8 the kernels read."""
+    if labels.dtype == torch.bool:
+        labels = labels.view(torch.uint8) if labels.is_contiguous() else labels.to(torch.uint8)
+    if labels.dtype != torch.uint8 or labels.dim() != 1 or labels.numel() != n:
+        raise ValueError(f"{what}: labels must be a uint8 or bool tensor of {n} elements")
+    return labels.contiguous()
 
 
 def pair_mlp_pairs(u: torch.Tensor, v: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor, w3: torch.Tensor,
@@ -2477,11 +2477,7 @@ def pair_mlp_pairs(u: torch.Tensor, v: torch.Tensor, w2: torch.Tensor, b2: torch
         thr = float(thr)
         if thr != thr:
             raise ValueError("pair_mlp_pairs: thr is NaN")
-        if labels.dtype == torch.bool:
-            labels = labels.view(torch.uint8) if labels.is_contiguous() else labels.to(torch.uint8)
-        if labels.dtype != torch.uint8 or labels.dim() != 1 or labels.numel() != n_pairs:
-            raise ValueError(f"pair_mlp_pairs: labels must be a uint8 or bool tensor of {n_pairs} elements")
-        labels = labels.contiguous()
+        labels = _u8_labels("pair_mlp_pairs", labels, n_pairs)
         if counts is None:
             counts = torch.zeros(5, dtype=torch.int64, device=dev)
         elif counts.dtype != torch.int64 or counts.numel() != 5 or not counts.is_contiguous() or counts.device != dev:
@@ -2513,14 +2509,11 @@ def binary_curve(scores: torch.Tensor, labels: torch.Tensor):
     _need_gpu(scores, labels)
     if scores.dtype != torch.float32 or scores.dim() != 1:
         raise ValueError("binary_curve: scores must be a 1-D float32 tensor")
-    if labels.dtype == torch.bool:
-        labels = labels.view(torch.uint8) if labels.is_contiguous() else labels.to(torch.uint8)
-    if labels.dtype != torch.uint8 or labels.dim() != 1 or labels.numel() != scores.numel():
-        raise ValueError(f"binary_curve: labels must be a uint8 or bool tensor of {scores.numel()} elements")
     n = scores.numel()
+    labels = _u8_labels("binary_curve", labels, n)
     if n > 2 ** 31 - 2:
         raise ValueError(f"binary_curve: {n} scores (at most 2^31 - 2)")
-    scores, labels = scores.contiguous(), labels.contiguous()
+    scores = scores.contiguous()
     dev = scores.device
     counts = torch.empty(5, dtype=torch.int64, device=dev)
     ap = torch.empty(1, dtype=torch.float64, device=dev)

@@ -30,8 +30,9 @@ from typing import Dict, Optional, Sequence
 
 import torch
 
+from . import _queries as Q
 from . import ops
-from .ranking import KnownTriples, RankResult, _check_ks, _check_side, metrics_from_counts, realistic_rank
+from .ranking import KnownTriples, RankResult
 
 _SIGMOID_CHUNK = 1 << 24      # elements per float64 temporary of _sigmoid_
 
@@ -100,15 +101,10 @@ def _sigmoid_(z: torch.Tensor) -> torch.Tensor:
         for row in z:
             _sigmoid_(row)
         return z
-    for lo in range(0, flat.numel(), _SIGMOID_CHUNK):
-        part = flat[lo:lo + _SIGMOID_CHUNK]
+    for lo, hi in Q.batches(flat.numel(), _SIGMOID_CHUNK):
+        part = flat[lo:hi]
         part.copy_(torch.sigmoid(part.double()))
     return z
-
-
-def _check_ids(name, x):
-    if not isinstance(x, torch.Tensor) or x.dim() != 1 or x.dtype.is_floating_point or x.dtype == torch.bool:
-        raise ValueError(f"{name} must be a 1-D tensor of integer ids")
 
 
 def _table_width_ok(head: FoldedMLPHead, table: torch.Tensor):
@@ -123,17 +119,22 @@ def _project(rows: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] =
     return ops.gemm_tall([rows], [[w]], trans_b=True, bias=bias)
 
 
+def _project_sides(head: FoldedMLPHead, side: str, qrows: torch.Tensor, crows: torch.Tensor):
+    """(uq, v) of the query rows and the candidate rows for a side.  'tail': the pairs are (query, c), so the queries take
+    fc1's head half and its bias; 'head': the pairs are (c, query), so the candidates do."""
+    if side == "tail":
+        return _project(qrows, head.w1h, head.b1), _project(crows, head.w1t)
+    return _project(qrows, head.w1t), _project(crows, head.w1h, head.b1)
+
+
 def mlp_scores(model, head_ids: torch.Tensor, tail_ids: torch.Tensor, logits: bool = False) -> torch.Tensor:
     """The len(head_ids) x len(tail_ids) matrix of the head's probabilities p(h_i, t_j) -- or logits -- on the model's
     inference table: what model(h, t, mode='mlp') gives in eval mode for every pair, without forming the pairs.  Only
     the rows named are projected.  The result is one float32 tensor of the caller's choosing (rows x cols x 4 bytes)."""
-    _check_ids("head_ids", head_ids)
-    _check_ids("tail_ids", tail_ids)
+    Q.check_ids("head_ids", head_ids)
+    Q.check_ids("tail_ids", tail_ids)
     head = fold_mlp_head(model)
-    dev = model.entity_embed.weight.device
-    hid, tid = ops.checked_ids(model.n_entities, head_ids.to(dev), tail_ids.to(dev))
-    ops.check_deferred_errors()
-    model.device = dev
+    (hid, tid), _, _ = Q.ids_to_device(model, model.entity_embed.weight.device, (head_ids, tail_ids))
     with torch.no_grad():
         table = model._table_for_inference().detach()
         _table_width_ok(head, table)
@@ -153,17 +154,12 @@ def predict_topk_mlp(model, head: FoldedMLPHead, ids, r, side, k, filt, cand, ba
         _table_width_ok(head, table)
         qrows = ops.gather_rows(table, ids)
         crows = table if cand is None else ops.gather_rows(table, cand)
-        if side == "tail":                   # pairs (query, c): the query in fc1's head half, with the bias
-            uq, v = _project(qrows, head.w1h, head.b1), _project(crows, head.w1t)
-        else:                                # pairs (c, query): the candidates in the head half, with the bias
-            uq, v = _project(qrows, head.w1t), _project(crows, head.w1h, head.b1)
+        uq, v = _project_sides(head, side, qrows, crows)
         del qrows, crows
-        frel = r if r is not None else torch.full((b,), -1, dtype=torch.int64, device=dev)
+        frel = Q.filter_relations(r, b, dev)
         out_ids = torch.empty((b, k), dtype=torch.int64, device=dev)
         out_z = torch.empty((b, k), dtype=torch.float32, device=dev)
-        step = b if batch_size is None else int(batch_size)
-        for lo in range(0, b, step):
-            hi = min(lo + step, b)
+        for lo, hi in Q.batches(b, batch_size):
             ii, zz = ops.pair_mlp_topk(uq[lo:hi], v, head.w2, head.b2, head.w3, head.b3, k, filt, ids[lo:hi], frel[lo:hi],
                                        cand, splits)
             out_ids[lo:hi] = ii
@@ -179,77 +175,50 @@ def rank_pairs_mlp(model, h: torch.Tensor, t: torch.Tensor, r: Optional[torch.Te
     pair for the filter (None: a pair known under any relation is dropped).  candidates: optional 1-D tensor of unique
     entity ids to rank among -- every truth must be one of them; one side only.  batch_size: queries per launch (None:
     all); it does not change the result.  The model's mode, parameters, buffers and caches are left as they are."""
-    side = _check_side(side)
-    _check_ids("h", h)
-    _check_ids("t", t)
-    if h.numel() != t.numel():
-        raise ValueError(f"h and t have different lengths ({h.numel()}, {t.numel()})")
+    side = Q.check_side(side)
+    _check_pairs(h, t)
     if r is not None:
-        _check_ids("r", r)
+        Q.check_ids("r", r)
         if r.numel() != h.numel():
             raise ValueError(f"h and r have different lengths ({h.numel()}, {r.numel()})")
     if candidates is not None:
-        _check_ids("candidates", candidates)
+        Q.check_ids("candidates", candidates)
         if side == "both":
             raise ValueError("candidates go with side='tail' or side='head': the two sides of 'both' would need two sets")
-        if torch.unique(candidates).numel() != candidates.numel():
-            raise ValueError("candidates must be unique entity ids")
+        Q.check_unique(candidates)
         truth = t if side == "tail" else h
         missing = int((~torch.isin(truth.to(candidates.device), candidates)).sum())
         if missing:
             raise ValueError(f"{missing} of the {truth.numel()} true {'tails' if side == 'tail' else 'heads'} are not among "
                              "the candidates")
-    if batch_size is not None and (isinstance(batch_size, bool) or int(batch_size) != batch_size or batch_size <= 0):
-        raise ValueError(f"batch_size must be a positive integer, got {batch_size!r}")
-    if known is not None and known.n_entities != model.n_entities:
-        raise ValueError(f"known triples over {known.n_entities} entities, the model has {model.n_entities}")
+    Q.check_batch_size(batch_size)
+    Q.check_known_entities(known, model)
     head = fold_mlp_head(model)                          # (AttributeError without initialize_MLP)
     dev = model.entity_embed.weight.device
-    if known is not None and known.device != dev:
-        raise ValueError(f"known triples live on {known.device}, the model on {dev}")
-    sides = ("tail", "head") if side == "both" else (side,)
+    Q.check_known_device(known, dev)
     b = h.numel()
+    better, equal = Q.count_buffers(side, b, dev)
     if b == 0:
-        z = torch.zeros((len(sides), 0) if side == "both" else (0,), dtype=torch.int64, device=dev)
-        return RankResult(z, z.clone(), z.double(), side)
-    h, t = ops.checked_ids(model.n_entities, h.to(dev), t.to(dev))
-    if r is not None:
-        (r,) = ops.checked_ids(model.n_relations, r.to(dev), what="relation")
-    cand = None
-    if candidates is not None:
-        (cand,) = ops.checked_ids(model.n_entities, candidates.to(dev), what="candidate entity")
-    ops.check_deferred_errors()
-    model.device = dev
+        return Q.rank_result(better, equal, side)
+    (h, t), r, cand = Q.ids_to_device(model, dev, (h, t), r, candidates)
     with torch.no_grad():
         table = model._table_for_inference().detach()
         _table_width_ok(head, table)
         crows = table if cand is None else ops.gather_rows(table, cand)
         slot = ops.pair_mlp_cand_slot(model.n_entities, cand) if cand is not None else None
-        frel = r if r is not None else torch.full((b,), -1, dtype=torch.int64, device=dev)
-        better = torch.empty((len(sides), b), dtype=torch.int32, device=dev)
-        equal = torch.empty((len(sides), b), dtype=torch.int32, device=dev)
-        step = b if batch_size is None else int(batch_size)
-        for j, s_ in enumerate(sides):
+        frel = Q.filter_relations(r, b, dev)
+        for j, s_ in enumerate(Q.rank_sides(side)):
             q_ids, truth = (h, t) if s_ == "tail" else (t, h)
-            qrows = ops.gather_rows(table, q_ids)
-            if s_ == "tail":                 # pairs (query, c): the query in fc1's head half, with the bias
-                uq, v = _project(qrows, head.w1h, head.b1), _project(crows, head.w1t)
-            else:                            # pairs (c, query): the candidates in the head half, with the bias
-                uq, v = _project(qrows, head.w1t), _project(crows, head.w1h, head.b1)
-            del qrows
+            uq, v = _project_sides(head, s_, ops.gather_rows(table, q_ids), crows)
             filt = known.for_side(s_) if known is not None else None
             truth_rows = truth if slot is None else slot[truth].long()
-            for lo in range(0, b, step):
-                hi = min(lo + step, b)
+            for lo, hi in Q.batches(b, batch_size):
                 bb, ee, _ = ops.pair_mlp_rank_count(uq[lo:hi], v, head.w2, head.b2, head.w3, head.b3, truth_rows[lo:hi],
                                                     filt, q_ids[lo:hi], frel[lo:hi], cand, slot)
                 better[j, lo:hi] = bb
                 equal[j, lo:hi] = ee
             del uq, v
-    better, equal = better.long(), equal.long()
-    if side != "both":
-        better, equal = better[0], equal[0]
-    return RankResult(better, equal, realistic_rank(better, equal), side)
+    return Q.rank_result(better, equal, side)
 
 
 def evaluate_mlp_ranking(model, h: torch.Tensor, t: torch.Tensor, r: Optional[torch.Tensor] = None,
@@ -258,33 +227,17 @@ def evaluate_mlp_ranking(model, h: torch.Tensor, t: torch.Tensor, r: Optional[to
     """{'mr', 'mrr', 'hits@k'..., 'n', 'tail': {...}, 'head': {...}}: filtered ranking metrics of the pairs under the MLP
     pair head (rank_pairs_mlp, ranking.metrics_from_counts); the top level is over every rank computed (2B for
     side='both').  Runs in eval mode, as evaluate_ranking does, and restores the model's previous mode."""
-    ks = _check_ks(ks)
-    side = _check_side(side)
-    was_training = model.training
-    model.eval()
-    try:
+    ks = Q.check_ks(ks)
+    side = Q.check_side(side)
+    with Q.eval_mode(model):
         res = rank_pairs_mlp(model, h, t, r=r, side=side, known=known, candidates=candidates, batch_size=batch_size)
-    finally:
-        model.train(was_training)
-    better, equal = res.better.cpu(), res.equal.cpu()
-    out = metrics_from_counts(better, equal, ks)
-    if side == "both":
-        out["tail"] = metrics_from_counts(better[0], equal[0], ks)
-        out["head"] = metrics_from_counts(better[1], equal[1], ks)
-    else:
-        out[side] = metrics_from_counts(better, equal, ks)
-    return out
+    return Q.ranking_metrics(res, ks)
 
 
 # ----------------------------------------------------------------------------- explicit pairs and their classification
-def _check_batch_size(batch_size):
-    if batch_size is not None and (isinstance(batch_size, bool) or int(batch_size) != batch_size or batch_size <= 0):
-        raise ValueError(f"batch_size must be a positive integer, got {batch_size!r}")
-
-
 def _check_pairs(h, t):
-    _check_ids("h", h)
-    _check_ids("t", t)
+    Q.check_ids("h", h)
+    Q.check_ids("t", t)
     if h.numel() != t.numel():
         raise ValueError(f"h and t have different lengths ({h.numel()}, {t.numel()})")
 
@@ -306,9 +259,7 @@ def _pair_side(table: torch.Tensor, ids: torch.Tensor, w: torch.Tensor, bias: Op
 def _pair_logits(model, head: FoldedMLPHead, h, t, batch_size, labels=None, thr=None):
     """(logits float32[P], counts int64[5] or None) of the checked-for-shape, non-empty pair list on the model's device"""
     dev = model.entity_embed.weight.device
-    hid, tid = ops.checked_ids(model.n_entities, h.to(dev), t.to(dev))
-    ops.check_deferred_errors()
-    model.device = dev
+    (hid, tid), _, _ = Q.ids_to_device(model, dev, (h, t))
     p = hid.numel()
     with torch.no_grad():
         table = model._table_for_inference().detach()
@@ -317,9 +268,7 @@ def _pair_logits(model, head: FoldedMLPHead, h, t, batch_size, labels=None, thr=
         v, v_idx = _pair_side(table, tid, head.w1t, None)
         z = torch.empty(p, dtype=torch.float32, device=dev)
         counts = torch.zeros(5, dtype=torch.int64, device=dev) if labels is not None else None
-        step = p if batch_size is None else int(batch_size)
-        for lo in range(0, p, step):
-            hi = min(lo + step, p)
+        for lo, hi in Q.batches(p, batch_size):
             ops.pair_mlp_pairs(u if u_idx is not None else u[lo:hi], v if v_idx is not None else v[lo:hi], head.w2,
                                head.b2, head.w3, head.b3, u_idx[lo:hi] if u_idx is not None else None,
                                v_idx[lo:hi] if v_idx is not None else None,
@@ -335,7 +284,7 @@ def score_pairs_mlp(model, h: torch.Tensor, t: torch.Tensor, logits: bool = Fals
     it does not change the result.  BatchNorm is in inference form whatever model.training says; the model's mode,
     parameters, buffers and caches are left as they are."""
     _check_pairs(h, t)
-    _check_batch_size(batch_size)
+    Q.check_batch_size(batch_size)
     head = fold_mlp_head(model)                          # (AttributeError without initialize_MLP)
     if h.numel() == 0:
         return torch.empty(0, dtype=torch.float32, device=model.entity_embed.weight.device)
@@ -405,7 +354,7 @@ def evaluate_mlp_classification(model, h: torch.Tensor, t: torch.Tensor, labels:
     pair is positive."""
     _check_pairs(h, t)
     _check_labels(labels, h.numel())
-    _check_batch_size(batch_size)
+    Q.check_batch_size(batch_size)
     if logit_threshold is None:
         thr = logit_of_probability(threshold)
     else:
@@ -413,9 +362,7 @@ def evaluate_mlp_classification(model, h: torch.Tensor, t: torch.Tensor, labels:
         if thr != thr:
             raise ValueError("logit_threshold is NaN")
     head = fold_mlp_head(model)                          # (AttributeError without initialize_MLP)
-    was_training = model.training
-    model.eval()
-    try:
+    with Q.eval_mode(model):
         if h.numel() == 0:
             return classification_metrics(0, 0, 0, 0, 0, 0, 0)
         dev = model.entity_embed.weight.device
@@ -424,6 +371,4 @@ def evaluate_mlp_classification(model, h: torch.Tensor, t: torch.Tensor, labels:
         curve = ops.binary_curve(z, lab)
         tp, fp, tn, fn, nan = (int(x) for x in counts.tolist())
         n_pos = int(lab.sum())
-    finally:
-        model.train(was_training)
     return classification_metrics(tp, fp, tn, fn, nan, n_pos, h.numel() - n_pos, curve)

@@ -15,35 +15,21 @@ table once per relation present in the queries (the tall GEMM), and that project
 """
 from __future__ import annotations
 
-from dataclasses import dataclass
 from typing import Dict, Optional, Sequence
 
 import torch
 
+from . import _queries as Q
 from . import ops
+from ._queries import SIDES, RankResult, metrics_from_counts, realistic_rank  # noqa: F401  (public under this module)
 
-SIDES = ("tail", "head", "both")
 SCORINGS = ("transr", "transe", "dot")
-
-
-def _check_side(side: str) -> str:
-    if side not in SIDES:
-        raise ValueError(f"side must be one of {SIDES}, got {side!r}")
-    return side
 
 
 def _check_scoring(scoring: str) -> str:
     if scoring not in SCORINGS:
         raise ValueError(f"scoring must be one of {SCORINGS}, got {scoring!r}")
     return scoring
-
-
-def _check_ks(ks: Sequence[int]) -> tuple:
-    ks = tuple(ks)
-    for k in ks:
-        if isinstance(k, bool) or int(k) != k or k <= 0:
-            raise ValueError(f"Hits@k needs positive integers k, got {k!r}")
-    return tuple(int(k) for k in ks)
 
 
 def _check_triples(h, r, t):
@@ -77,36 +63,6 @@ class KnownTriples:
         return self.by_head if side == "tail" else self.by_tail
 
 
-@dataclass
-class RankResult:
-    """Per query: ``better`` / ``equal`` (int64) and ``rank`` = 1 + better + equal / 2 (float64).  For side='both' the
-    tensors are 2 x B: row 0 the tail side, row 1 the head side."""
-    better: torch.Tensor
-    equal: torch.Tensor
-    rank: torch.Tensor
-    side: str
-
-
-def realistic_rank(better: torch.Tensor, equal: torch.Tensor) -> torch.Tensor:
-    return 1.0 + better.double() + 0.5 * equal.double()
-
-
-def metrics_from_counts(better: torch.Tensor, equal: torch.Tensor, ks: Sequence[int] = (1, 3, 10)) -> Dict[str, float]:
-    """{'mr', 'mrr', 'hits@k'..., 'n'} of the ranks 1 + better + equal / 2 (all zero for an empty set, 'n' = 0)."""
-    ks = _check_ks(ks)
-    rank = realistic_rank(torch.as_tensor(better).reshape(-1), torch.as_tensor(equal).reshape(-1))
-    n = rank.numel()
-    out = {"n": n}
-    if n == 0:
-        out.update({"mr": 0.0, "mrr": 0.0}, **{f"hits@{k}": 0.0 for k in ks})
-        return out
-    out["mr"] = float(rank.mean())
-    out["mrr"] = float((1.0 / rank).mean())
-    for k in ks:
-        out[f"hits@{k}"] = float((rank <= k).double().mean())
-    return out
-
-
 def _count_group(model, scoring, side, p, pn, pos, h, r, t, known, batch_size, better, equal):
     """better / equal of one side for the queries at positions pos, against the candidate rows p (squared norms pn)."""
     q_ids, truth = (h, t) if side == "tail" else (t, h)
@@ -114,9 +70,7 @@ def _count_group(model, scoring, side, p, pn, pos, h, r, t, known, batch_size, b
     filt = known.for_side(side) if known is not None else None
     ids, tru, rel = q_ids[pos], truth[pos], r[pos]
     q = ops.rank_queries(p, ids, None if scoring == "dot" else model.relation_embed.weight.detach(), rel, alpha)
-    step = pos.numel() if batch_size is None else int(batch_size)
-    for lo in range(0, pos.numel(), step):
-        hi = min(lo + step, pos.numel())
+    for lo, hi in Q.batches(pos.numel(), batch_size):
         bb, ee, _ = ops.rank_count(q[lo:hi], p, pn, tru[lo:hi], filt, ids[lo:hi], rel[lo:hi])
         better[pos[lo:hi]] = bb
         equal[pos[lo:hi]] = ee
@@ -158,40 +112,26 @@ def rank_triples(model, h: torch.Tensor, r: torch.Tensor, t: torch.Tensor, side:
                  batch_size: Optional[int] = None) -> RankResult:
     """Filtered ranks of the triples (h, r, t) on the model's inference table (see the module docstring).  The model's
     mode is left as it is (evaluate_ranking switches to eval); nothing of the model is changed."""
-    side = _check_side(side)
+    side = Q.check_side(side)
     scoring = _check_scoring(scoring if scoring is not None else model.scoring)
     _check_triples(h, r, t)
-    if batch_size is not None and (int(batch_size) != batch_size or batch_size <= 0):
-        raise ValueError(f"batch_size must be a positive integer, got {batch_size!r}")
+    Q.check_batch_size(batch_size)
     if scoring == "transr" and getattr(model, "gat_trans_M", None) is None:
         raise ValueError("scoring='transr' needs a model with gat_trans_M (built with scoring='transr')")
-    if known is not None and known.n_entities != model.n_entities:
-        raise ValueError(f"known triples over {known.n_entities} entities, the model has {model.n_entities}")
-    sides = ("tail", "head") if side == "both" else (side,)
+    Q.check_known_entities(known, model)
     dev = model.entity_embed.weight.device
     b = h.numel()
+    better, equal = Q.count_buffers(side, b, dev)
     if b == 0:
-        z = torch.zeros((len(sides), 0) if side == "both" else (0,), dtype=torch.int64, device=dev)
-        return RankResult(z, z.clone(), z.double(), side)
-    h, t = ops.checked_ids(model.n_entities, h.to(dev), t.to(dev))
-    (r,) = ops.checked_ids(model.n_relations, r.to(dev), what="relation")
-    ops.check_deferred_errors()
-    if known is not None and known.device != dev:
-        raise ValueError(f"known triples live on {known.device}, the model on {dev}")
-    model.device = dev                   # (as forward(..., device=) records it: the literal tables follow it)
+        return Q.rank_result(better, equal, side)
+    (h, t), r, _ = Q.ids_to_device(model, dev, (h, t), r, known=known)
     with torch.no_grad():
         table = model._table_for_inference().detach()
-        groups = scoring_groups(model, scoring, table, r)
-        better = torch.empty((len(sides), b), dtype=torch.int32, device=dev)
-        equal = torch.empty((len(sides), b), dtype=torch.int32, device=dev)
-        for p, pn, pos in groups:
-            for j, s_ in enumerate(sides):
+        for p, pn, pos in scoring_groups(model, scoring, table, r):
+            for j, s_ in enumerate(Q.rank_sides(side)):
                 _count_group(model, scoring, s_, p, pn, pos, h, r, t, known, batch_size, better[j], equal[j])
             del p, pn
-    better, equal = better.long(), equal.long()
-    if side != "both":
-        better, equal = better[0], equal[0]
-    return RankResult(better, equal, realistic_rank(better, equal), side)
+    return Q.rank_result(better, equal, side)
 
 
 def evaluate_ranking(model, h: torch.Tensor, r: torch.Tensor, t: torch.Tensor, known: Optional[KnownTriples] = None,
@@ -200,20 +140,9 @@ def evaluate_ranking(model, h: torch.Tensor, r: torch.Tensor, t: torch.Tensor, k
     """{'mr', 'mrr', 'hits@k'..., 'n', 'tail': {...}, 'head': {...}}: filtered ranking metrics of the triples; the top
     level is over every rank computed (2B for side='both').  Runs in eval mode, as the reference's evaluate does, and
     restores the model's previous mode."""
-    ks = _check_ks(ks)
-    side = _check_side(side)
+    ks = Q.check_ks(ks)
+    side = Q.check_side(side)
     _check_scoring(scoring if scoring is not None else model.scoring)
-    was_training = model.training
-    model.eval()
-    try:
+    with Q.eval_mode(model):
         res = rank_triples(model, h, r, t, side=side, known=known, scoring=scoring, batch_size=batch_size)
-    finally:
-        model.train(was_training)
-    better, equal = res.better.cpu(), res.equal.cpu()
-    out = metrics_from_counts(better, equal, ks)
-    if side == "both":
-        out["tail"] = metrics_from_counts(better[0], equal[0], ks)
-        out["head"] = metrics_from_counts(better[1], equal[1], ks)
-    else:
-        out[side] = metrics_from_counts(better, equal, ks)
-    return out
+    return Q.ranking_metrics(res, ks)

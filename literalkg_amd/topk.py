@@ -24,6 +24,7 @@ from typing import Optional
 
 import torch
 
+from . import _queries as Q
 from . import ops
 from .ranking import KnownTriples, _check_scoring, scoring_groups
 
@@ -53,11 +54,6 @@ def _check_k(k) -> int:
     return k
 
 
-def _check_ids(name, x):
-    if not isinstance(x, torch.Tensor) or x.dim() != 1 or x.dtype.is_floating_point or x.dtype == torch.bool:
-        raise ValueError(f"{name} must be a 1-D tensor of integer ids")
-
-
 def predict_topk(model, ids: torch.Tensor, r: Optional[torch.Tensor] = None, side: str = "tail", k: int = 10,
                  known: Optional[KnownTriples] = None, scoring: Optional[str] = None,
                  candidates: Optional[torch.Tensor] = None, batch_size: Optional[int] = None,
@@ -72,54 +68,41 @@ def predict_topk(model, ids: torch.Tensor, r: Optional[torch.Tensor] = None, sid
     if not mlp:
         scoring = _check_scoring(scoring)
     k = _check_k(k)
-    _check_ids("ids", ids)
+    Q.check_ids("ids", ids)
     if r is None:
         if scoring not in ("dot", "mlp"):
             raise ValueError(f"scoring={scoring!r} needs the relations r (only 'dot' can filter without them)")
     else:
-        _check_ids("r", r)
+        Q.check_ids("r", r)
         if r.numel() != ids.numel():
             raise ValueError(f"ids and r have different lengths ({ids.numel()}, {r.numel()})")
     if candidates is not None:
-        _check_ids("candidates", candidates)
-    if batch_size is not None and (isinstance(batch_size, bool) or int(batch_size) != batch_size or batch_size <= 0):
-        raise ValueError(f"batch_size must be a positive integer, got {batch_size!r}")
+        Q.check_ids("candidates", candidates)
+    Q.check_batch_size(batch_size)
     if isinstance(splits, bool) or int(splits) != splits or not 0 <= splits <= ops.TOPK_MAX_SPLITS:
         raise ValueError(f"splits must be an integer in [0, {ops.TOPK_MAX_SPLITS}], got {splits!r}")
     if scoring == "transr" and getattr(model, "gat_trans_M", None) is None:
         raise ValueError("scoring='transr' needs a model with gat_trans_M (built with scoring='transr')")
-    if known is not None and known.n_entities != model.n_entities:
-        raise ValueError(f"known triples over {known.n_entities} entities, the model has {model.n_entities}")
+    Q.check_known_entities(known, model)
     head = None
     if mlp:
         from .pairmlp import fold_mlp_head, predict_topk_mlp
-        if candidates is not None and torch.unique(candidates).numel() != candidates.numel():
-            raise ValueError("candidates must be unique entity ids")
+        Q.check_unique(candidates)
         head = fold_mlp_head(model)                      # (AttributeError without initialize_MLP)
     dev = model.entity_embed.weight.device
-    if known is not None and known.device != dev:
-        raise ValueError(f"known triples live on {known.device}, the model on {dev}")
+    Q.check_known_device(known, dev)
     b = ids.numel()
     if b == 0:
         return TopKResult(torch.full((0, k), -1, dtype=torch.int64, device=dev),
                           torch.zeros((0, k), dtype=torch.float32, device=dev), side,
                           torch.zeros((0, k), dtype=torch.float32, device=dev))
-    (ids,) = ops.checked_ids(model.n_entities, ids.to(dev))
-    if r is not None:
-        (r,) = ops.checked_ids(model.n_relations, r.to(dev), what="relation")
-    cand = None
-    if candidates is not None:
-        (cand,) = ops.checked_ids(model.n_entities, candidates.to(dev), what="candidate entity")
-    ops.check_deferred_errors()
-    if cand is not None and torch.unique(cand).numel() != cand.numel():
-        raise ValueError("candidates must be unique entity ids")
-    model.device = dev
+    (ids,), r, cand = Q.ids_to_device(model, dev, (ids,), r, candidates, unique=True)
     filt = known.for_side(side) if known is not None else None
     if mlp:
         out_ids, out_p, out_z = predict_topk_mlp(model, head, ids, r, side, k, filt, cand, batch_size, splits)
         return TopKResult(out_ids, out_p, side, out_z)
     alpha = 1.0 if side == "tail" else -1.0             # q = P_r[h] + e_r  /  q = P_r[t] - e_r
-    frel_all = r if r is not None else torch.full((b,), -1, dtype=torch.int64, device=dev)
+    frel_all = Q.filter_relations(r, b, dev)
     out_ids = torch.empty((b, k), dtype=torch.int64, device=dev)
     out_sc = torch.empty((b, k), dtype=torch.float32, device=dev)
     out_s = torch.empty((b, k), dtype=torch.float32, device=dev)
@@ -132,9 +115,7 @@ def predict_topk(model, ids: torch.Tensor, r: Optional[torch.Tensor] = None, sid
                 p = ops.gather_rows(p, cand)
                 pn = ops.rank_sqnorm(p) if pn is not None else None
             frel = frel_all[pos]
-            step = pos.numel() if batch_size is None else int(batch_size)
-            for lo in range(0, pos.numel(), step):
-                hi = min(lo + step, pos.numel())
+            for lo, hi in Q.batches(pos.numel(), batch_size):
                 ii, ss, vv = ops.topk_select(q[lo:hi], p, pn, k, filt, qid[lo:hi], frel[lo:hi], cand, splits)
                 out_ids[pos[lo:hi]] = ii
                 out_s[pos[lo:hi]] = ss

@@ -450,6 +450,13 @@ def test_errors_and_edges(L, R, gpu_device):
     wide = random_model(gen, "transe", 300, 16, 32, 3, gpu_device)
     with pytest.raises(ValueError):
         R.rank_triples(wide, h, r, t, scoring="transe")             # width 32 != relation_dim 16
+    # one filter row and one filter relation per query: a short list is refused, not read past
+    from literalkg_amd import ops
+    filt = R.KnownTriples(h, r, t, 300, 3).by_head
+    for frow, frel in ((h[:2], r), (h, r[:2]), (h[:2], r[:2])):
+        said = f"{frow.numel()} filter rows and {frel.numel()} filter relations for 3 queries"
+        with pytest.raises(ValueError, match=said):
+            ops.rank_count(model.T[:3], model.T, None, t, filt, frow, frel)
     # the calls above leave nothing pending: a valid call works
     ok = R.rank_triples(model, h, r, t, side="both", scoring="transe")
     assert ok.better.shape == (2, 3)

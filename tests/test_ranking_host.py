@@ -71,4 +71,6 @@ def test_argument_checks_without_device(R):
         m.rank_triples(ids, ids[:1], ids)
     with pytest.raises(ValueError, match="batch_size"):
         m.rank_triples(ids, ids, ids, batch_size=0)
+    with pytest.raises(ValueError, match="batch_size"):
+        m.rank_triples(ids, ids, ids, batch_size=True)      # a bool is no batch size (as for its siblings)
     assert m.training                                   # a rejected call leaves the mode alone
