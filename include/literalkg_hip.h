@@ -757,6 +757,37 @@ int64_t lkg_binary_curve_workspace(int64_t n);
 int lkg_binary_curve_f32(int64_t n, const float *scores, const uint8_t *labels, int64_t *out_counts, double *out_ap,
                          void *workspace, int64_t workspace_bytes, void *stream);
 
+/* Explicit triples under the model's own score (lkg_triples.hip; score_triples, evaluate_triple_classification).  Triple i
+ * is (query row q_idx[i], candidate row c_idx[i]) of the n_rows x k table p (P_r for 'transr', the inference table
+ * otherwise); its query is q = p[q_idx[i]] + alpha e[rel[i]] (e NULL: the row itself; rel NULL: row 0 of e), formed with
+ * the one rounding lkg_rank_queries_f32 makes.  Row and relation indices are trusted; addressing is 64-bit.
+ *
+ * lkg_triple_scores_f32: out[i] = the kernel score s = pn[c_idx[i]] - 2 q.p_c (pn NULL: dot scoring, s = -2 q.p_c), the
+ *     bits lkg_rank_count_f32 compares and lkg_topk_merge_f32 returns as `scores` for that (query, candidate) -- or, with
+ *     flag 1, the reported score it returns as `values`: |q|^2 + s (pn given; |q|^2 with lkg_rank_sqnorm_f32's bits) or
+ *     -s / 2 (dot).  And / or counts[0..4] += tp, fp, tn, fn, nan against labels (uint8[n], 0 or 1) and thr: a triple is
+ *     predicted positive iff out[i] <= thr -- with flag 2, iff out[i] >= thr -- one f32 compare on the value out would
+ *     hold; a NaN score is counted in nan alone.  out and counts are each nullable, at least one is given; counts needs
+ *     labels and a thr that is not NaN.  The counts are ACCUMULATED (64-bit integer atomics, at most five per workgroup),
+ *     so batches add up; the caller zeroes them.  n <= INT32_MAX - 1; n == 0 launches nothing.                        */
+int lkg_triple_scores_f32(int64_t n, int32_t k, const float *p, int64_t ldp, const int64_t *q_idx, const int64_t *c_idx,
+                          const float *pn, const float *e, int64_t lde, const int64_t *rel, float alpha, int32_t flags,
+                          const uint8_t *labels, float thr, float *out, int64_t *counts, void *stream);
+
+/* Exact tie-aware classification thresholds per relation (lkg_csr_device.hip; fit_triple_thresholds): scores f32[n],
+ * labels uint8[n] (0 or 1), rel int64[n] in [0, n_relations) (NULL: every triple under relation 0, the pooled fit).
+ * Within a relation the non-NaN scores are taken best first (lower_is_better: ascending, else descending) and grouped by
+ * float equality (-0.0 == +0.0); with TP_g / FP_g the cumulative label counts at the end of group g, correct(0) = n_neg
+ * and correct(g) = TP_g + n_neg - FP_g.  thr[rho] = the score of the smallest g that maximises correct (a zero as +0.0),
+ * or, if that g is 0 (also: no scores), the sentinel -inf (lower_is_better) / +inf.  stats int64[n_relations][4] = n (all
+ * triples of the relation), n_pos (among its non-NaN scores), correct (at the threshold; NaN scores are wrong), n_nan.
+ * 1 <= n_relations < 2^29, n <= INT32_MAX - 1.  workspace: lkg_threshold_fit_workspace(n, n_relations) bytes of device
+ * memory; the call allocates nothing.                                                                              */
+int64_t lkg_threshold_fit_workspace(int64_t n, int64_t n_relations);
+int lkg_threshold_fit_f32(int64_t n, int64_t n_relations, const float *scores, const uint8_t *labels, const int64_t *rel,
+                          int32_t lower_is_better, float *thr, int64_t *stats, void *workspace, int64_t workspace_bytes,
+                          void *stream);
+
 #ifdef __cplusplus
 }
 #endif

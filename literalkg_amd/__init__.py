@@ -14,7 +14,10 @@ from .ranking import KnownTriples, RankResult, evaluate_ranking   # noqa: F401
 from .topk import TopKResult, predict_topk   # noqa: F401
 from .pairmlp import (FoldedMLPHead, evaluate_mlp_classification, evaluate_mlp_ranking,   # noqa: F401
                       fold_mlp_head, mlp_scores, rank_pairs_mlp, score_pairs_mlp)
+from .triples import (TripleThresholds, evaluate_triple_classification, fit_triple_thresholds,   # noqa: F401
+                      score_triples)
 
 __all__ = ["LiteralKG", "Aggregator", "Gate", "GateMul", "KGStructure", "KnownTriples", "RankResult", "evaluate_ranking",
            "TopKResult", "predict_topk", "FoldedMLPHead", "fold_mlp_head", "mlp_scores", "rank_pairs_mlp",
-           "evaluate_mlp_ranking", "score_pairs_mlp", "evaluate_mlp_classification"]
+           "evaluate_mlp_ranking", "score_pairs_mlp", "evaluate_mlp_classification", "TripleThresholds", "score_triples",
+           "fit_triple_thresholds", "evaluate_triple_classification"]

@@ -110,11 +110,15 @@ PROTOTYPES = {
     "lkg_pair_mlp_pairs_f32": [i64, vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, f32, vp, vp, vp],
     "lkg_binary_curve_workspace": [i64],
     "lkg_binary_curve_f32": [i64, vp, vp, vp, vp, vp, i64, vp],
+    "lkg_triple_scores_f32": [i64, i32, vp, i64, vp, vp, vp, vp, i64, vp, f32, i32, vp, f32, vp, vp, vp],
+    "lkg_threshold_fit_workspace": [i64, i64],
+    "lkg_threshold_fit_f32": [i64, i64, vp, vp, vp, i32, vp, vp, vp, i64, vp],
 }
 _RESTYPE = {"lkg_last_error": C.c_char_p, "lkg_csr_build_device_workspace": C.c_int64,
             "lkg_gemm_tall_workspace": C.c_int64, "lkg_gemm_workspace": C.c_int64,
             "lkg_linear_act_layernorm_workspace": C.c_int64, "lkg_narrow_layer_bwd_workspace": C.c_int64,
-            "lkg_csr_transpose_device_workspace": C.c_int64, "lkg_binary_curve_workspace": C.c_int64}
+            "lkg_csr_transpose_device_workspace": C.c_int64, "lkg_binary_curve_workspace": C.c_int64,
+            "lkg_threshold_fit_workspace": C.c_int64}
 
 
 class LkgError(RuntimeError):

@@ -675,3 +675,170 @@ extern "C" int lkg_binary_curve_f32(int64_t n, const float *scores, const uint8_
     LKG_CHECK_LAUNCH("lkg_binary_curve_f32");
     return LKG_OK;
 }
+
+// ---------------------------------------------------------------------------------------------------
+// Exact tie-aware classification thresholds per relation (fit_triple_thresholds), on the same radix sort and scan.  Within
+// a relation the non-NaN scores are taken best first (ascending for distances, descending for 'dot'), grouped by float
+// equality, and cut after the smallest group g that maximises  correct(g) = TP_g + n_neg - FP_g  (correct(0) = n_neg:
+// nothing is positive).  n_neg is one number per relation, so the arg-max is that of d_g = TP_g - FP_g against d_0 = 0.
+//     key = relation << 34 | (best-first order key of the score) << 1 | label       NaN: relation << 34 | 1 << 33
+// with -0.0 canonicalised and NaN keyed past every number of its relation, exactly as bc_keys_kernel does.  Then
+//   tf_mark     pos[k] = the key's label (0 for NaN keys); per relation the segment's start, the end of its non-NaN keys
+//               and its end
+//   scan        pos -> positives before k
+//   tf_argmax   at every tie-group end, relative to its segment: d_g, packed as (d_g + 2^31) << 32 | ~(k + 1); a segmented
+//               max over the workgroup's 256 sorted keys in LDS, then one 64-bit atomicMax per (workgroup, relation).  The
+//               slot starts at 2^31 << 32 | ~0 -- the cut before every score -- which wins every tie; among groups the
+//               smaller k does.
+//   tf_finish   per relation: the winning group's score read back from its key (a zero comes back as +0.0), or the
+//               sentinel (-inf for distances, +inf for 'dot'); n, n_pos (among the non-NaN scores), correct and n_nan
+// Integers only: the result is a function of the multiset of (relation, score, label), whatever the input's order.
+namespace {
+
+constexpr int TF_THREADS = 256;
+constexpr u64 TF_INIT = (0x80000000ull << 32) | 0xffffffffull;
+
+__global__ void tf_init_kernel(long n_rel, int *__restrict__ seg, u64 *__restrict__ best) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_rel) return;
+    seg[i] = 0;
+    seg[n_rel + i] = 0;
+    seg[2 * n_rel + i] = 0;
+    best[i] = TF_INIT;
+}
+
+__global__ void tf_keys_kernel(long n, const float *__restrict__ scores, const unsigned char *__restrict__ labels,
+                               const long *__restrict__ rel, int lower, u64 *__restrict__ keys) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    u32 b = __float_as_uint(scores[i]);
+    const bool nan = (b & 0x7fffffffu) > 0x7f800000u;
+    b = (b << 1) ? b : 0u;                                        // -0.0 ties with +0.0
+    const u32 asc = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+    const u32 ord = lower ? asc : ~asc;
+    const u64 hi = (u64)(rel ? rel[i] : 0L) << 34;
+    keys[i] = hi | (nan ? BC_NAN_KEY : (((u64)ord) << 1) | (u64)(labels[i] != 0));
+}
+
+// seg: [0] first key of the relation, [1] one past its last non-NaN key, [2] one past its last key
+__global__ void tf_mark_kernel(long n, long n_rel, const u64 *__restrict__ keys, int *__restrict__ pos,
+                               int *__restrict__ seg) {
+    const long k = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    const u64 key = keys[k];
+    const long rho = (long)(key >> 34);
+    const bool valid = !(key & BC_NAN_KEY);
+    pos[k] = valid ? (int)(key & 1ull) : 0;
+    if (k == 0 || (long)(keys[k - 1] >> 34) != rho) seg[rho] = (int)k;
+    const bool last = k == n - 1 || (long)(keys[k + 1] >> 34) != rho;
+    if (valid && (last || (keys[k + 1] & BC_NAN_KEY))) seg[n_rel + rho] = (int)(k + 1);
+    if (last) seg[2 * n_rel + rho] = (int)(k + 1);
+}
+
+// pos: the exclusive scan of the labels
+__global__ __launch_bounds__(TF_THREADS) void tf_argmax_kernel(long n, const u64 *__restrict__ keys,
+                                                               const int *__restrict__ pos, const int *__restrict__ seg,
+                                                               u64 *__restrict__ best) {
+    __shared__ u64 sv[TF_THREADS];
+    __shared__ long sr[TF_THREADS];
+    const int tid = threadIdx.x;
+    const long k = (long)blockIdx.x * TF_THREADS + tid;
+    long rho = -1 - tid;                                           // (past the end: a relation of its own)
+    u64 val = 0;
+    if (k < n) {
+        const u64 key = keys[k];
+        rho = (long)(key >> 34);
+        if (!(key & BC_NAN_KEY) && (k == n - 1 || (keys[k + 1] >> 1) != (key >> 1))) {      // a tie group ends here
+            const long s0 = seg[rho];
+            const long tp = (long)pos[k] + (long)(key & 1ull) - (long)pos[s0];
+            const long d = 2 * tp - (k + 1 - s0);                  // TP_g - FP_g
+            val = ((u64)(d + 0x80000000L) << 32) | (u64)(~(u32)(k + 1));
+        }
+    }
+    sv[tid] = val;
+    sr[tid] = rho;
+    __syncthreads();
+    for (int o = 1; o < TF_THREADS; o <<= 1) {                     // (sorted keys: equal relations are contiguous)
+        const bool same = tid >= o && sr[tid - o] == rho;
+        const u64 other = same ? sv[tid - o] : 0ull;
+        __syncthreads();
+        val = other > val ? other : val;
+        sv[tid] = val;
+        __syncthreads();
+    }
+    if (k < n && val && (tid == TF_THREADS - 1 || sr[tid + 1] != rho)) atomicMax(best + rho, val);
+}
+
+// stats[rho][0..3] = n, n_pos, correct, n_nan
+__global__ void tf_finish_kernel(long n, long n_rel, const u64 *__restrict__ keys, const int *__restrict__ pos,
+                                 const int *__restrict__ seg, const u64 *__restrict__ best, int lower,
+                                 float *__restrict__ thr, long *__restrict__ stats) {
+    const long rho = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (rho >= n_rel) return;
+    const long s0 = seg[rho], v1 = seg[n_rel + rho], s1 = seg[2 * n_rel + rho];
+    const long n_all = s1 > s0 ? s1 - s0 : 0, n_valid = (n_all && v1 > s0) ? v1 - s0 : 0;
+    long n_pos = 0;
+    if (n_valid) n_pos = (long)pos[v1 - 1] + (long)(keys[v1 - 1] & 1ull) - (long)pos[s0];
+    const u64 b = best[rho];
+    const long d = (long)(b >> 32) - 0x80000000L;
+    const u32 k1 = ~(u32)b;                                        // k + 1 of the winning group end; 0 = the sentinel
+    float t = lower ? -INFINITY : INFINITY;
+    if (k1) {
+        const u32 ord = (u32)(keys[k1 - 1] >> 1);
+        const u32 asc = lower ? ord : ~ord;
+        t = __uint_as_float((asc & 0x80000000u) ? (asc & 0x7fffffffu) : ~asc);
+    }
+    thr[rho] = t;
+    stats[4 * rho + 0] = n_all;
+    stats[4 * rho + 1] = n_pos;
+    stats[4 * rho + 2] = d + (n_valid - n_pos);
+    stats[4 * rho + 3] = n_all - n_valid;
+}
+
+long tf_ws_bytes(long n, long n_rel) {
+    const long e = std::max<long>(n, 1), m = std::max<long>(n_rel, 1);
+    return sort_ws_bytes(e) + align_up(4 * e, 256) + align_up(4 * 3 * m, 256) + align_up(8 * m, 256) + 256;
+}
+
+}  // namespace
+
+extern "C" int64_t lkg_threshold_fit_workspace(int64_t n, int64_t n_relations) {
+    return (n < 0 || n_relations < 1) ? 0 : tf_ws_bytes(n, n_relations);
+}
+
+extern "C" int lkg_threshold_fit_f32(int64_t n, int64_t n_relations, const float *scores, const uint8_t *labels,
+                                     const int64_t *rel, int32_t lower_is_better, float *thr, int64_t *stats,
+                                     void *workspace, int64_t workspace_bytes, void *stream) {
+    LKG_REQUIRE(n >= 0 && n <= (int64_t)INT32_MAX - 1, "lkg_threshold_fit_f32: n %lld out of range", (long long)n);
+    LKG_REQUIRE(n_relations >= 1 && n_relations < (1LL << 29), "lkg_threshold_fit_f32: n_relations %lld out of range",
+                (long long)n_relations);
+    LKG_REQUIRE(thr && stats && workspace && (n == 0 || (scores && labels)), "lkg_threshold_fit_f32: null pointer");
+    LKG_REQUIRE(workspace_bytes >= tf_ws_bytes(n, n_relations),
+                "lkg_threshold_fit_f32: workspace of %lld bytes is smaller than the %lld required",
+                (long long)workspace_bytes, (long long)tf_ws_bytes(n, n_relations));
+    hipStream_t s = (hipStream_t)stream;
+    const long e = std::max<long>(n, 1), m = n_relations;
+    char *ws = (char *)workspace;
+    const SortWs w = carve(ws, e);
+    int *pos = (int *)(ws + sort_ws_bytes(e));
+    int *seg = (int *)((char *)pos + align_up(4 * e, 256));
+    u64 *best = (u64 *)((char *)seg + align_up(4 * 3 * m, 256));
+    u64 *keys = w.k0;
+    hipLaunchKernelGGL(tf_init_kernel, grid1d(m), dim3(256), 0, s, m, seg, best);
+    if (n > 0) {
+        hipLaunchKernelGGL(tf_keys_kernel, grid1d(n), dim3(256), 0, s, (long)n, scores, labels, (const long *)rel,
+                           (int)(lower_is_better != 0), w.k0);
+        u32 *perm;
+        int rc = radix_sort(w, n, 34 + (m > 1 ? key_bits((u64)m - 1ull) : 0), &keys, &perm, s);
+        if (rc != LKG_OK) return rc;
+        hipLaunchKernelGGL(tf_mark_kernel, grid1d(n), dim3(256), 0, s, (long)n, m, keys, pos, seg);
+        rc = exclusive_scan(pos, pos, n, w.sums, nullptr, s);
+        if (rc != LKG_OK) return rc;
+        hipLaunchKernelGGL(tf_argmax_kernel, dim3((unsigned)ceil_div(n, TF_THREADS)), dim3(TF_THREADS), 0, s, (long)n,
+                           keys, pos, seg, best);
+    }
+    hipLaunchKernelGGL(tf_finish_kernel, grid1d(m), dim3(256), 0, s, (long)n, m, keys, pos, seg, best,
+                       (int)(lower_is_better != 0), thr, (long *)stats);
+    LKG_CHECK_LAUNCH("lkg_threshold_fit_f32");
+    return LKG_OK;
+}

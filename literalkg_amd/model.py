@@ -725,6 +725,30 @@ class LiteralKG(nn.Module):
         from .pairmlp import score_pairs_mlp
         return score_pairs_mlp(self, h, t, logits=logits, batch_size=batch_size)
 
+    def score_triples(self, h, r, t, scoring: Optional[str] = None, side: str = "tail",
+                      batch_size: Optional[int] = None, kernel_scores: bool = False):
+        """float32[P]: the score of every triple (h_i, r_i, t_i) on the inference table, with the bits predict_topk
+        reports for that (query, candidate) (literalkg_amd/triples.py, score_triples)."""
+        from .triples import score_triples
+        return score_triples(self, h, r, t, scoring=scoring, side=side, batch_size=batch_size,
+                             kernel_scores=kernel_scores)
+
+    def fit_triple_thresholds(self, h, r, t, labels, scoring: Optional[str] = None, per_relation: bool = True,
+                              batch_size: Optional[int] = None):
+        """The exact per-relation classification thresholds of the labelled validation triples
+        (literalkg_amd/triples.py, fit_triple_thresholds).  Returns a triples.TripleThresholds."""
+        from .triples import fit_triple_thresholds
+        return fit_triple_thresholds(self, h, r, t, labels, scoring=scoring, per_relation=per_relation,
+                                     batch_size=batch_size)
+
+    def evaluate_triple_classification(self, h, r, t, labels, thresholds, scoring: Optional[str] = None,
+                                       batch_size: Optional[int] = None):
+        """Triple-classification metrics of the labelled triples under per-relation thresholds
+        (literalkg_amd/triples.py, evaluate_triple_classification)."""
+        from .triples import evaluate_triple_classification
+        return evaluate_triple_classification(self, h, r, t, labels, thresholds, scoring=scoring,
+                                              batch_size=batch_size)
+
     def initialize_MLP(self):
         """The pair-classification head of model.py:499-504 (same module names, so checkpoints interchange)."""
         self.fc1 = nn.Linear(self.scale_gat_dim * 2, 128)

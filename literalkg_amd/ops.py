@@ -2523,3 +2523,101 @@ def binary_curve(scores: torch.Tensor, labels: torch.Tensor):
            _stream())
     n_pos, n_neg, n_nan, n_groups, auc2 = (int(x) for x in counts.tolist())
     return n_pos, n_neg, n_nan, n_groups, auc2, float(ap.item())
+
+
+# ----------------------------------------------------------------------------- explicit triples (lkg_triples.hip)
+def triple_scores(p: torch.Tensor, q_idx: torch.Tensor, c_idx: torch.Tensor, pn: Optional[torch.Tensor] = None,
+                  e: Optional[torch.Tensor] = None, rel: Optional[torch.Tensor] = None, alpha: float = 1.0,
+                  reported: bool = True, higher_is_positive: bool = False, labels: Optional[torch.Tensor] = None,
+                  thr: Optional[float] = None, want_scores: bool = True, out: Optional[torch.Tensor] = None,
+                  counts: Optional[torch.Tensor] = None):
+    """(scores, counts) of an explicit list of triples (lkg_triple_scores_f32): triple i is (query row q_idx[i],
+    candidate row c_idx[i]) of the table of rows p, its query q = p[q_idx[i]] + alpha * e[rel[i]] (e None: the row
+    itself).  The kernel score is s = pn[c] - 2 q.p_c (pn None: dot scoring, s = -2 q.p_c), the bits rank_count compares
+    and topk_select returns as ``scores``; reported=True gives what topk_select returns as ``values``: ||q||^2 + s (pn
+    given) or -s / 2 (dot).  The indices must lie inside the tables.
+
+    scores: float32[P], or None with want_scores=False (out: an optional contiguous float32[P] to write them to).
+    counts: with labels (uint8 / bool [P], 0 or 1) and thr, an int64[5] device tensor tp, fp, tn, fn, nan -- a triple is
+    positive iff its score <= thr (higher_is_positive: >= thr) in float32, a NaN score is counted in nan alone -- else
+    None.  Passing counts (a contiguous int64[5] on the device) ADDS to it, so batches accumulate."""
+    _need_gpu(p, q_idx, c_idx, pn, e, rel, labels, out, counts)
+    p = _f32_rows(p)
+    dev = p.device
+    q_idx, c_idx = _i64(q_idx.reshape(-1)), _i64(c_idx.reshape(-1))
+    n = q_idx.numel()
+    if c_idx.numel() != n or (rel is not None and rel.numel() != n):
+        raise ValueError(f"triple_scores: {n} query rows, {c_idx.numel()} candidate rows"
+                         f"{'' if rel is None else f', {rel.numel()} relations'}: not a list of triples")
+    if n > 2 ** 31 - 2:
+        raise ValueError(f"triple_scores: {n} triples in one launch (at most 2^31 - 2): use batches")
+    if n and p.shape[0] == 0:
+        raise ValueError("triple_scores: row indices into an empty table")
+    if pn is not None and (pn.dtype != torch.float32 or pn.numel() != p.shape[0] or not pn.is_contiguous()):
+        raise ValueError(f"triple_scores: pn must be a contiguous float32[{p.shape[0]}]")
+    if e is not None:
+        e = _f32_rows(e)
+        if e.shape[1] != p.shape[1]:
+            raise ValueError(f"triple_scores: e has {e.shape[1]} columns, the rows {p.shape[1]}")
+    rel = _i64(rel.reshape(-1)) if (rel is not None and e is not None) else None
+    want_counts = labels is not None or counts is not None
+    if want_counts:
+        if labels is None or thr is None:
+            raise ValueError("triple_scores: the counts need labels and thr")
+        thr = float(thr)
+        if thr != thr:
+            raise ValueError("triple_scores: thr is NaN")
+        labels = _u8_labels("triple_scores", labels, n)
+        if counts is None:
+            counts = torch.zeros(5, dtype=torch.int64, device=dev)
+        elif counts.dtype != torch.int64 or counts.numel() != 5 or not counts.is_contiguous() or counts.device != dev:
+            raise ValueError(f"triple_scores: counts must be a contiguous int64[5] on {dev}")
+    elif not want_scores:
+        raise ValueError("triple_scores: nothing to compute (no scores wanted, no labels given)")
+    if want_scores:
+        if out is None:
+            out = torch.empty(n, dtype=torch.float32, device=dev)
+        elif out.dtype != torch.float32 or out.dim() != 1 or out.numel() != n or not out.is_contiguous() or \
+                out.device != dev:
+            raise ValueError(f"triple_scores: out must be a contiguous float32[{n}] on {dev}")
+    else:
+        out = None
+    if n:
+        flags = (1 if reported else 0) | (2 if higher_is_positive else 0)
+        N.call("lkg_triple_scores_f32", n, p.shape[1], N.ptr(p), _ld(p), N.ptr(q_idx), N.ptr(c_idx), N.ptr(pn), N.ptr(e),
+               _ld(e) if e is not None else 0, N.ptr(rel), float(alpha), flags, N.ptr(labels) if want_counts else None,
+               thr if want_counts else 0.0, N.ptr(out), N.ptr(counts) if want_counts else None, _stream())
+    return out, (counts if want_counts else None)
+
+
+def threshold_fit(scores: torch.Tensor, labels: torch.Tensor, rel: Optional[torch.Tensor], n_relations: int,
+                  lower_is_better: bool):
+    """(thr float32[n_relations], stats int64[n_relations, 4]) of lkg_threshold_fit_f32, both on the device: per
+    relation the exact tie-aware threshold that classifies most of its (score, label) pairs correctly -- the score of the
+    smallest cut that does, or the sentinel (-inf / +inf: nothing is positive) -- and n, n_pos (among the non-NaN
+    scores), correct, n_nan.  rel: int64 ids in [0, n_relations) (None: one pooled fit, n_relations = 1).  NaN scores
+    count in n and n_nan only; ties are by float equality (-0.0 == +0.0, a threshold of zero comes back as +0.0)."""
+    _need_gpu(scores, labels, rel)
+    if scores.dtype != torch.float32 or scores.dim() != 1:
+        raise ValueError("threshold_fit: scores must be a 1-D float32 tensor")
+    n, m = scores.numel(), int(n_relations)
+    labels = _u8_labels("threshold_fit", labels, n)
+    if n > 2 ** 31 - 2:
+        raise ValueError(f"threshold_fit: {n} scores (at most 2^31 - 2)")
+    if rel is None:
+        m = 1
+    else:
+        rel = _i64(rel.reshape(-1))
+        if rel.numel() != n:
+            raise ValueError(f"threshold_fit: {rel.numel()} relations for {n} scores")
+    if not 1 <= m < 2 ** 29:
+        raise ValueError(f"threshold_fit: n_relations must lie in [1, 2^29), got {m}")
+    scores = scores.contiguous()
+    dev = scores.device
+    thr = torch.empty(m, dtype=torch.float32, device=dev)
+    stats = torch.empty((m, 4), dtype=torch.int64, device=dev)
+    ws_bytes = int(N.load().lkg_threshold_fit_workspace(n, m))
+    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+    N.call("lkg_threshold_fit_f32", n, m, N.ptr(scores), N.ptr(labels), N.ptr(rel), int(bool(lower_is_better)),
+           N.ptr(thr), N.ptr(stats), N.ptr(ws), ws_bytes, _stream())
+    return thr, stats
