@@ -788,6 +788,35 @@ int lkg_threshold_fit_f32(int64_t n, int64_t n_relations, const float *scores, c
                           int32_t lower_is_better, float *thr, int64_t *stats, void *workspace, int64_t workspace_bytes,
                           void *stream);
 
+/* The relation slot of a triple (lkg_relations.hip; literalkg_amd/relations.py: score_relations, rank_relations,
+ * predict_relations).  Pair i is (query row q_idx[i], candidate row c_idx[i]); a chunk of n_rel relations is scored in one
+ * launch and the stored row of scores is then filtered, counted and selected from.  Row indices are trusted; addressing
+ * is 64-bit.
+ *
+ * lkg_relation_scores_f32: out[i * ldo + j] = the reported score of pair i under the chunk's relation j, the bits
+ *     lkg_triple_scores_f32 writes with flag 1 for (q_idx[i], c_idx[i]) on that relation's operands: |q|^2 + (pn_j[c] -
+ *     2 q.p_c) with q = p_j[q_idx[i]] + alpha e[j] (one rounding per element), |q|^2 with lkg_rank_sqnorm_f32's bits.
+ *     Relation j's table of rows starts at p + j * rel_stride (row stride ldp), its squared norms at pn + j * pn_stride,
+ *     its embedding is row j of e (row stride lde); rel_stride = pn_stride = 0: one table shared by all relations
+ *     ('transe').  One launch whatever n_rel is; n <= INT32_MAX - 1; n == 0 or n_rel == 0 launches nothing.
+ * lkg_relation_order_f32 : per pair i over scores[i * lds .. + n_rel): first every relation under which the pair is known
+ *     is dropped -- the raw edges eptr[e] .. eptr[e+1] of the entry e whose col is filter_col[i] in row filter_row[i] of
+ *     the lkg_csr_build_device structure (rowptr, col, eptr, rel); duplicates and order do not matter; rowptr NULL = no
+ *     filter.  With truth non-NULL, better[i] / equal[i] = #{r' != truth[i], not dropped : s(i, r') < / == s(i, truth[i])}
+ *     (the truth's own score is used whether or not it is known; a NaN score counts nowhere, a NaN truth gives 0 / 0).
+ *     With top_k > 0, top_ids[i, j] / top_scores[i, j] = the j-th smallest (score, relation id) among the relations
+ *     neither dropped nor NaN -- float comparison, then the id -- padded with -1 / NaN.  Compares and integer adds only.
+ *     1 <= n_rel <= LKG_RELATION_MAX (a workgroup stages four rows of scores in 64 KB of LDS), top_k in
+ *     [0, LKG_TOPK_MAX]; truth NULL and top_k == 0 together is an error.                                              */
+#define LKG_RELATION_MAX 4096
+int lkg_relation_scores_f32(int64_t n, int32_t k, int32_t n_rel, const float *p, int64_t ldp, int64_t rel_stride,
+                            const float *pn, int64_t pn_stride, const int64_t *q_idx, const int64_t *c_idx,
+                            const float *e, int64_t lde, float alpha, float *out, int64_t ldo, void *stream);
+int lkg_relation_order_f32(int64_t n, int32_t n_rel, const float *scores, int64_t lds, const int64_t *truth,
+                           const int64_t *filter_row, const int64_t *filter_col, const int32_t *rowptr,
+                           const int32_t *col, const int32_t *eptr, const int32_t *rel, int32_t top_k, int32_t *better,
+                           int32_t *equal, int64_t *top_ids, float *top_scores, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

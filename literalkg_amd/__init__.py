@@ -16,8 +16,11 @@ from .pairmlp import (FoldedMLPHead, evaluate_mlp_classification, evaluate_mlp_r
                       fold_mlp_head, mlp_scores, rank_pairs_mlp, score_pairs_mlp)
 from .triples import (TripleThresholds, evaluate_triple_classification, fit_triple_thresholds,   # noqa: F401
                       score_triples)
+from .relations import (RelationTopK, evaluate_relation_prediction, predict_relations, rank_relations,   # noqa: F401
+                        score_relations)
 
 __all__ = ["LiteralKG", "Aggregator", "Gate", "GateMul", "KGStructure", "KnownTriples", "RankResult", "evaluate_ranking",
            "TopKResult", "predict_topk", "FoldedMLPHead", "fold_mlp_head", "mlp_scores", "rank_pairs_mlp",
            "evaluate_mlp_ranking", "score_pairs_mlp", "evaluate_mlp_classification", "TripleThresholds", "score_triples",
-           "fit_triple_thresholds", "evaluate_triple_classification"]
+           "fit_triple_thresholds", "evaluate_triple_classification", "RelationTopK", "score_relations", "rank_relations",
+           "predict_relations", "evaluate_relation_prediction"]

@@ -113,6 +113,8 @@ PROTOTYPES = {
     "lkg_triple_scores_f32": [i64, i32, vp, i64, vp, vp, vp, vp, i64, vp, f32, i32, vp, f32, vp, vp, vp],
     "lkg_threshold_fit_workspace": [i64, i64],
     "lkg_threshold_fit_f32": [i64, i64, vp, vp, vp, i32, vp, vp, vp, i64, vp],
+    "lkg_relation_scores_f32": [i64, i32, i32, vp, i64, i64, vp, i64, vp, vp, vp, i64, f32, vp, i64, vp],
+    "lkg_relation_order_f32": [i64, i32, vp, i64, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp],
 }
 _RESTYPE = {"lkg_last_error": C.c_char_p, "lkg_csr_build_device_workspace": C.c_int64,
             "lkg_gemm_tall_workspace": C.c_int64, "lkg_gemm_workspace": C.c_int64,

@@ -749,6 +749,37 @@ class LiteralKG(nn.Module):
         return evaluate_triple_classification(self, h, r, t, labels, thresholds, scoring=scoring,
                                               batch_size=batch_size)
 
+    def score_relations(self, h, t, scoring: Optional[str] = None, side: str = "tail", batch_size: Optional[int] = None,
+                        relation_chunk: Optional[int] = None):
+        """float32[P, n_relations]: the score of (h_i, j, t_i) under every relation j, with the bits score_triples
+        returns for it (literalkg_amd/relations.py, score_relations)."""
+        from .relations import score_relations
+        return score_relations(self, h, t, scoring=scoring, side=side, batch_size=batch_size,
+                               relation_chunk=relation_chunk)
+
+    def rank_relations(self, h, r, t, known=None, scoring: Optional[str] = None, side: str = "tail",
+                       batch_size: Optional[int] = None, relation_chunk: Optional[int] = None):
+        """The filtered rank of the true relation r_i among all relations of (h_i, ?, t_i)
+        (literalkg_amd/relations.py, rank_relations).  Returns a RankResult."""
+        from .relations import rank_relations
+        return rank_relations(self, h, r, t, known=known, scoring=scoring, side=side, batch_size=batch_size,
+                              relation_chunk=relation_chunk)
+
+    def predict_relations(self, h, t, k: int = 1, known=None, scoring: Optional[str] = None, side: str = "tail",
+                          batch_size: Optional[int] = None, relation_chunk: Optional[int] = None):
+        """The k most likely relations of every pair (h_i, t_i) that are not already known
+        (literalkg_amd/relations.py, predict_relations).  Returns a relations.RelationTopK."""
+        from .relations import predict_relations
+        return predict_relations(self, h, t, k=k, known=known, scoring=scoring, side=side, batch_size=batch_size,
+                                 relation_chunk=relation_chunk)
+
+    def evaluate_relation_prediction(self, h, r, t, known=None, ks=(1, 3, 10), scoring: Optional[str] = None,
+                                     batch_size: Optional[int] = None):
+        """MR / MRR / Hits@k of the true relations among all relations, filtered, overall and per relation
+        (literalkg_amd/relations.py, evaluate_relation_prediction)."""
+        from .relations import evaluate_relation_prediction
+        return evaluate_relation_prediction(self, h, r, t, known=known, ks=ks, scoring=scoring, batch_size=batch_size)
+
     def initialize_MLP(self):
         """The pair-classification head of model.py:499-504 (same module names, so checkpoints interchange)."""
         self.fc1 = nn.Linear(self.scale_gat_dim * 2, 128)

@@ -2241,6 +2241,8 @@ def rank_count(q: torch.Tensor, p: torch.Tensor, pn: Optional[torch.Tensor], tru
 TOPK_MAX = 128
 TOPK_MAX_SPLITS = 64
 TOPK_WORKSPACE_BYTES = 256 << 20
+RELATION_MAX = 4096                    # lkg_relation_order_f32: four rows of this many scores are a workgroup's 64 KB of LDS
+RELATION_WORKSPACE_BYTES = 256 << 20   # relations.py: the projected slab (relations x distinct rows x padded k x 4 bytes)
 
 
 def _check_k_splits(what: str, k, splits):
@@ -2621,3 +2623,97 @@ def threshold_fit(scores: torch.Tensor, labels: torch.Tensor, rel: Optional[torc
     N.call("lkg_threshold_fit_f32", n, m, N.ptr(scores), N.ptr(labels), N.ptr(rel), int(bool(lower_is_better)),
            N.ptr(thr), N.ptr(stats), N.ptr(ws), ws_bytes, _stream())
     return thr, stats
+
+
+# ----------------------------------------------------------------------------- the relation slot (lkg_relations.hip)
+def relation_scores(p: torch.Tensor, pn: torch.Tensor, q_idx: torch.Tensor, c_idx: torch.Tensor, e: torch.Tensor,
+                    alpha: float = 1.0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[i, j] = the reported score of the pair (query row q_idx[i], candidate row c_idx[i]) under relation j of the
+    chunk e (float32[n_rel, k]), in ONE launch (lkg_relation_scores_f32): the bits triple_scores(reported=True) gives for
+    that pair on relation j's operands -- ||q||^2 + (pn_j[c] - 2 q.p_c), q = p_j[q_idx[i]] + alpha * e[j].  p is one table
+    float32[n_rows, k] shared by the relations (pn float32[n_rows]) or a slab float32[n_rel, n_rows, k] of one table per
+    relation (pn float32[n_rel, n_rows]; unit column stride, equal row strides).  out: an optional float32[P, n_rel] with
+    unit column stride (a column block of a wider matrix will do).  The indices must lie inside the tables."""
+    _need_gpu(p, pn, q_idx, c_idx, e, out)
+    if p.dtype != torch.float32 or p.dim() not in (2, 3):
+        raise ValueError("relation_scores: p must be a float32 table [n_rows, k] or a slab [n_rel, n_rows, k]")
+    e = _f32_rows(e)
+    n_rel, k = e.shape
+    dev = p.device
+    q_idx, c_idx = _i64(q_idx.reshape(-1)), _i64(c_idx.reshape(-1))
+    n = q_idx.numel()
+    if c_idx.numel() != n:
+        raise ValueError(f"relation_scores: {n} query rows, {c_idx.numel()} candidate rows: not a list of pairs")
+    if n > 2 ** 31 - 2:
+        raise ValueError(f"relation_scores: {n} pairs in one launch (at most 2^31 - 2): use batches")
+    if p.dim() == 3:
+        if p.shape[0] != n_rel or p.shape[2] != k or p.stride(2) != 1 or (p.shape[1] > 1 and p.stride(1) < k) or \
+                (n_rel > 1 and p.stride(0) < p.shape[1] * p.stride(1)):
+            raise ValueError(f"relation_scores: a slab of shape {tuple(p.shape)}, strides {p.stride()} for {n_rel} "
+                             f"relations of width {k}")
+        n_rows, ldp = p.shape[1], (p.stride(1) if p.shape[1] > 1 else max(k, p.stride(1)))
+        rel_stride = p.stride(0) if n_rel > 1 else max(p.stride(0), 1)
+        if pn.dtype != torch.float32 or tuple(pn.shape) != (n_rel, n_rows) or not pn.is_contiguous():
+            raise ValueError(f"relation_scores: pn must be a contiguous float32[{n_rel}, {n_rows}]")
+        pn_stride = max(n_rows, 1)
+    else:
+        p = _f32_rows(p)
+        if p.shape[1] != k:
+            raise ValueError(f"relation_scores: e has {k} columns, the rows {p.shape[1]}")
+        n_rows, ldp, rel_stride, pn_stride = p.shape[0], _ld(p), 0, 0
+        if pn.dtype != torch.float32 or pn.numel() != n_rows or not pn.is_contiguous():
+            raise ValueError(f"relation_scores: pn must be a contiguous float32[{n_rows}]")
+    if n and n_rows == 0:
+        raise ValueError("relation_scores: row indices into an empty table")
+    if out is None:
+        out = torch.empty((n, n_rel), dtype=torch.float32, device=dev)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (n, n_rel) or out.device != dev or \
+            (n_rel > 1 and out.stride(1) != 1) or (n > 1 and out.stride(0) < n_rel):
+        raise ValueError(f"relation_scores: out must be a float32 {n} x {n_rel} tensor with unit column stride on {dev}")
+    if n and n_rel:
+        N.call("lkg_relation_scores_f32", n, k, n_rel, N.ptr(p), ldp, rel_stride, N.ptr(pn), pn_stride, N.ptr(q_idx),
+               N.ptr(c_idx), N.ptr(e), _ld(e), float(alpha), N.ptr(out), out.stride(0) if n > 1 else max(n_rel, out.stride(0)),
+               _stream())
+    return out
+
+
+def relation_order(scores: torch.Tensor, truth: Optional[torch.Tensor] = None, filt=None,
+                   filter_row: Optional[torch.Tensor] = None, filter_col: Optional[torch.Tensor] = None, top_k: int = 0):
+    """(better, equal, top_ids, top_scores) per row of scores (float32[P, n_rel], n_rel <= RELATION_MAX), by
+    lkg_relation_order_f32.  filt = (rowptr, col, eptr, rel) of csr_build_device: row i first drops every relation of a
+    raw edge (filter_row[i], filter_col[i]) -- duplicates and order do not matter; the ids must be rows of the structure.
+    truth (int64[P]): better / equal int32[P] = the kept relations other than truth[i] whose score is < / == the truth's
+    (whose own score is used whether or not it is known); else None, None.  top_k > 0: top_ids int64[P, top_k] /
+    top_scores float32[P, top_k], the smallest (score, relation id) among the relations neither dropped nor NaN, padded
+    with -1 / NaN; else None, None.  A NaN score counts nowhere and is never selected."""
+    _need_gpu(scores, truth, filter_row, filter_col)
+    scores = _f32_rows(scores)
+    n, n_rel = scores.shape
+    top_k = int(top_k)
+    if not 1 <= n_rel <= RELATION_MAX:
+        raise ValueError(f"relation_order: {n_rel} relations; the kernel stages a row of scores per wave in LDS and takes "
+                         f"1 .. {RELATION_MAX}")
+    if not 0 <= top_k <= TOPK_MAX:
+        raise ValueError(f"relation_order: top_k must lie in [0, {TOPK_MAX}], got {top_k}")
+    if truth is None and top_k == 0:
+        raise ValueError("relation_order: nothing to compute (no truth, top_k = 0)")
+    if filt is not None and (filter_row is None or filter_col is None):
+        raise ValueError("relation_order: a filter needs filter_row and filter_col")
+    if n > 2 ** 31 - 2:
+        raise ValueError(f"relation_order: {n} rows in one launch (at most 2^31 - 2): use batches")
+    dev = scores.device
+    better = equal = ids = top = None
+    if truth is not None:
+        truth = _i64(truth.reshape(-1))
+        if truth.numel() != n:
+            raise ValueError(f"relation_order: {truth.numel()} truths for {n} rows")
+        better = torch.empty(n, dtype=torch.int32, device=dev)
+        equal = torch.empty(n, dtype=torch.int32, device=dev)
+    if top_k:
+        ids = torch.empty((n, top_k), dtype=torch.int64, device=dev)
+        top = torch.empty((n, top_k), dtype=torch.float32, device=dev)
+    fargs = _filter_args("relation_order", filt, filter_row, filter_col, n)
+    if n:
+        N.call("lkg_relation_order_f32", n, n_rel, N.ptr(scores), _ld(scores), N.ptr(truth), *fargs(), top_k,
+               N.ptr(better), N.ptr(equal), N.ptr(ids), N.ptr(top), _stream())
+    return better, equal, ids, top
