@@ -681,6 +681,42 @@ int lkg_topk_select_f32(int64_t n_q, int64_t n_cand, int32_t k, const float *q, 
 int lkg_topk_merge_f32(int64_t n_q, int32_t top_k, int32_t splits, const float *ws_s, const int32_t *ws_i,
                        const float *qn, int64_t *out_ids, float *out_scores, float *out_values, void *stream);
 
+/* Threshold retrieval (lkg_accept.hip, lkg_csr_device.hip; literalkg_amd/accepted.py).  Queries, candidates, cand_ids, the
+ * filter and the kernel score s(i, c) as for lkg_topk_select_f32, bit for bit.  The reported score is v(i, c) = qn[i] + s
+ * (pn and qn given: the squared distance, qn = lkg_rank_sqnorm_f32 of the queries) or -s / 2 (pn and qn NULL: the dot
+ * product) -- what lkg_topk_merge_f32 returns as `values`.  Candidate c of query i is ACCEPTED iff v(i, c) <= thr[i]
+ * (higher != 0: v(i, c) >= thr[i]) in one f32 compare -- a NaN score never is -- and the filter does not drop it.
+ * splits in [0, LKG_TOPK_MAX_SPLITS] (0 = automatic, as lkg_topk_splits chooses) is the number of candidate splits per 64
+ * queries; no result depends on it.  n_q, n_cand <= INT32_MAX - 1; empty inputs launch nothing; addressing is 64-bit.
+ *
+ * lkg_accept_count_f32: counts[i] += the number of accepted candidates of query i (the caller zeroes counts).  Nothing
+ *     of size n_q x n_cand, or of the size of the result, is written.
+ * lkg_accept_emit_f32 : every accepted (i, c) is written as (id(c), s, v) at out_*[base[i] + slot], slot taken from
+ *     cursor[i] (int32[n_q], zeroed by the caller), in no particular order inside the row.  counts is what
+ *     lkg_accept_count_f32 gave for the same arguments and base its exclusive scan; a slot outside [0, counts[i]) is NOT
+ *     written and *flag (zeroed by the caller) is set to 1 instead -- the two passes run the same arithmetic, so this
+ *     cannot happen, and if it did it would not become a store outside the buffers.
+ * lkg_accept_order    : rows of (id, s, v), row i owning the entries rowptr[i] .. rowptr[i + 1] (int64[n_q + 1],
+ *     rowptr[n_q] = m), sorted inside every row by ascending s (float comparison: -0.0 == +0.0; no NaN) and then ascending
+ *     id, into out_*.  ids lie in [0, id_bound), id_bound <= INT32_MAX; m <= INT32_MAX - 1.  workspace:
+ *     lkg_accept_order_workspace(m, n_q) bytes of device memory; the call allocates nothing.  out_* must not alias the
+ *     inputs.                                                                                                        */
+int lkg_accept_count_f32(int64_t n_q, int64_t n_cand, int32_t k, const float *q, int64_t ldq, const float *p,
+                         int64_t ldp, const float *pn, const float *qn, const float *thr, int32_t higher,
+                         const int64_t *cand_ids, const int64_t *filter_row, const int64_t *filter_rel,
+                         const int32_t *rowptr, const int32_t *col, const int32_t *eptr, const int32_t *rel,
+                         int32_t splits, int32_t *counts, void *stream);
+int lkg_accept_emit_f32(int64_t n_q, int64_t n_cand, int32_t k, const float *q, int64_t ldq, const float *p,
+                        int64_t ldp, const float *pn, const float *qn, const float *thr, int32_t higher,
+                        const int64_t *cand_ids, const int64_t *filter_row, const int64_t *filter_rel,
+                        const int32_t *rowptr, const int32_t *col, const int32_t *eptr, const int32_t *rel,
+                        int32_t splits, const int32_t *counts, const int64_t *base, int32_t *cursor, int64_t *out_ids,
+                        float *out_scores, float *out_values, int32_t *flag, void *stream);
+int64_t lkg_accept_order_workspace(int64_t m, int64_t n_q);
+int lkg_accept_order(int64_t m, int64_t n_q, int64_t id_bound, const int64_t *rowptr, const int64_t *ids,
+                     const float *scores, const float *values, int64_t *out_ids, float *out_scores, float *out_values,
+                     void *workspace, int64_t workspace_bytes, void *stream);
+
 /* The MLP pair head at inference (lkg_pairmlp.hip; literalkg_amd/pairmlp.py).  Queries are the n_q rows of uq, candidates
  * the n_cand rows of v (f32, 128 columns, row strides ldu / ldv: multiples of 4, 16-byte aligned bases): the two halves
  * of the head's first layer, already projected (the bias in either of them).  With the folded second and third layer --

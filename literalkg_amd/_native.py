@@ -115,12 +115,17 @@ PROTOTYPES = {
     "lkg_threshold_fit_f32": [i64, i64, vp, vp, vp, i32, vp, vp, vp, i64, vp],
     "lkg_relation_scores_f32": [i64, i32, i32, vp, i64, i64, vp, i64, vp, vp, vp, i64, f32, vp, i64, vp],
     "lkg_relation_order_f32": [i64, i32, vp, i64, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp],
+    "lkg_accept_count_f32": [i64, i64, i32, vp, i64, vp, i64, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp],
+    "lkg_accept_emit_f32": [i64, i64, i32, vp, i64, vp, i64, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp,
+                            vp, vp, vp, vp, vp],
+    "lkg_accept_order_workspace": [i64, i64],
+    "lkg_accept_order": [i64, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp],
 }
 _RESTYPE = {"lkg_last_error": C.c_char_p, "lkg_csr_build_device_workspace": C.c_int64,
             "lkg_gemm_tall_workspace": C.c_int64, "lkg_gemm_workspace": C.c_int64,
             "lkg_linear_act_layernorm_workspace": C.c_int64, "lkg_narrow_layer_bwd_workspace": C.c_int64,
             "lkg_csr_transpose_device_workspace": C.c_int64, "lkg_binary_curve_workspace": C.c_int64,
-            "lkg_threshold_fit_workspace": C.c_int64}
+            "lkg_threshold_fit_workspace": C.c_int64, "lkg_accept_order_workspace": C.c_int64}
 
 
 class LkgError(RuntimeError):

@@ -842,3 +842,92 @@ extern "C" int lkg_threshold_fit_f32(int64_t n, int64_t n_relations, const float
     LKG_CHECK_LAUNCH("lkg_threshold_fit_f32");
     return LKG_OK;
 }
+
+// ---------------------------------------------------------------------------------------------------
+// The order of an accepted list (predict_accepted, lkg_accept.hip), on the same radix sort.  Row i owns the entries
+// rowptr[i] .. rowptr[i + 1] of (id, s, v), in whatever order the emit pass left them; they leave sorted by ascending s
+// -- float comparison, so -0.0 is canonicalised to +0.0 -- and then by ascending id.  The sort is stable, so two sorts
+// give the order: one on the id, then one on
+//     key = row << 32 | (ascending order key of s)         sign flipped for s >= 0, all bits for s < 0
+// taken in the first sort's order.  The row is the key's high part, so every entry stays inside its row's range.  An
+// entry's row is found by binary search in rowptr.  No score here is NaN (a NaN is never accepted).
+namespace {
+
+__global__ void ao_id_keys_kernel(long m, const long *__restrict__ ids, u64 *__restrict__ keys) {
+    const long j = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j < m) keys[j] = (u64)ids[j];
+}
+
+// first[j] = the first sort's permutation (kept: the second sort reuses its buffers); keys[j] = the second sort's key
+__global__ void ao_row_keys_kernel(long m, long n_q, const long *__restrict__ rowptr, const float *__restrict__ s,
+                                   const u32 *__restrict__ perm, u32 *__restrict__ first, u64 *__restrict__ keys) {
+    const long j = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= m) return;
+    const u32 e = perm[j];
+    long lo = 0, hi = n_q - 1;                                     // the last row with rowptr[row] <= e
+    while (lo < hi) {
+        const long mid = (lo + hi + 1) >> 1;
+        if (rowptr[mid] <= (long)e) lo = mid;
+        else hi = mid - 1;
+    }
+    u32 b = __float_as_uint(s[e]);
+    b = (b << 1) ? b : 0u;                                        // -0.0 ties with +0.0
+    const u32 asc = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+    first[j] = e;
+    keys[j] = ((u64)lo << 32) | (u64)asc;
+}
+
+__global__ void ao_gather_kernel(long m, const u32 *__restrict__ perm, const u32 *__restrict__ first,
+                                 const long *__restrict__ ids, const float *__restrict__ s, const float *__restrict__ v,
+                                 long *__restrict__ out_ids, float *__restrict__ out_s, float *__restrict__ out_v) {
+    const long j = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= m) return;
+    const u32 e = first[perm[j]];
+    out_ids[j] = ids[e];
+    out_s[j] = s[e];
+    out_v[j] = v[e];
+}
+
+long ao_ws_bytes(long m) {
+    const long e = std::max<long>(m, 1);
+    return sort_ws_bytes(e) + align_up(4 * e, 256) + 256;
+}
+
+}  // namespace
+
+extern "C" int64_t lkg_accept_order_workspace(int64_t m, int64_t n_q) {
+    return (m < 0 || n_q < 0) ? 0 : ao_ws_bytes(m);
+}
+
+extern "C" int lkg_accept_order(int64_t m, int64_t n_q, int64_t id_bound, const int64_t *rowptr, const int64_t *ids,
+                                const float *scores, const float *values, int64_t *out_ids, float *out_scores,
+                                float *out_values, void *workspace, int64_t workspace_bytes, void *stream) {
+    LKG_REQUIRE(m >= 0 && m <= (int64_t)INT32_MAX - 1, "lkg_accept_order: m %lld out of range", (long long)m);
+    LKG_REQUIRE(n_q >= 0 && n_q <= (int64_t)INT32_MAX - 1, "lkg_accept_order: n_q %lld out of range", (long long)n_q);
+    LKG_REQUIRE(id_bound >= 1 && id_bound <= (int64_t)INT32_MAX, "lkg_accept_order: id_bound %lld out of range",
+                (long long)id_bound);
+    if (m == 0) return LKG_OK;
+    LKG_REQUIRE(n_q >= 1, "lkg_accept_order: entries without rows");
+    LKG_REQUIRE(rowptr && ids && scores && values && out_ids && out_scores && out_values && workspace,
+                "lkg_accept_order: null pointer");
+    LKG_REQUIRE(workspace_bytes >= ao_ws_bytes(m),
+                "lkg_accept_order: workspace of %lld bytes is smaller than the %lld required", (long long)workspace_bytes,
+                (long long)ao_ws_bytes(m));
+    hipStream_t s = (hipStream_t)stream;
+    char *ws = (char *)workspace;
+    const SortWs w = carve(ws, m);
+    u32 *first = (u32 *)(ws + sort_ws_bytes(m));
+    hipLaunchKernelGGL(ao_id_keys_kernel, grid1d(m), dim3(256), 0, s, (long)m, (const long *)ids, w.k0);
+    u64 *keys;
+    u32 *perm;
+    int rc = radix_sort(w, m, key_bits((u64)id_bound - 1ull), &keys, &perm, s);
+    if (rc != LKG_OK) return rc;
+    hipLaunchKernelGGL(ao_row_keys_kernel, grid1d(m), dim3(256), 0, s, (long)m, (long)n_q, (const long *)rowptr, scores,
+                       perm, first, w.k0);
+    rc = radix_sort(w, m, 32 + (n_q > 1 ? key_bits((u64)n_q - 1ull) : 0), &keys, &perm, s);
+    if (rc != LKG_OK) return rc;
+    hipLaunchKernelGGL(ao_gather_kernel, grid1d(m), dim3(256), 0, s, (long)m, perm, first, (const long *)ids, scores,
+                       values, (long *)out_ids, out_scores, out_values);
+    LKG_CHECK_LAUNCH("lkg_accept_order");
+    return LKG_OK;
+}

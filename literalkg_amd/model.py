@@ -773,6 +773,23 @@ class LiteralKG(nn.Module):
         return predict_relations(self, h, t, k=k, known=known, scoring=scoring, side=side, batch_size=batch_size,
                                  relation_chunk=relation_chunk)
 
+    def predict_accepted(self, ids, r, thresholds, side: str = "tail", known=None, scoring: Optional[str] = None,
+                         candidates=None, batch_size: Optional[int] = None, splits: int = 0, max_total: int = 1 << 26):
+        """Every tail of (ids, r, ?) (side 'tail') or head of (?, r, ids) (side 'head') whose score passes the thresholds
+        and that is not already known, best first (literalkg_amd/accepted.py, predict_accepted).  Returns an
+        accepted.AcceptedResult (rowptr, ids, scores, kernel_scores, counts)."""
+        from .accepted import predict_accepted
+        return predict_accepted(self, ids, r, thresholds, side=side, known=known, scoring=scoring, candidates=candidates,
+                                batch_size=batch_size, splits=splits, max_total=max_total)
+
+    def count_accepted(self, ids, r, thresholds, side: str = "tail", known=None, scoring: Optional[str] = None,
+                       candidates=None, batch_size: Optional[int] = None, splits: int = 0):
+        """int64[B]: how many candidates predict_accepted would list for every query (literalkg_amd/accepted.py,
+        count_accepted); nothing of the size of the lists is allocated."""
+        from .accepted import count_accepted
+        return count_accepted(self, ids, r, thresholds, side=side, known=known, scoring=scoring, candidates=candidates,
+                              batch_size=batch_size, splits=splits)
+
     def evaluate_relation_prediction(self, h, r, t, known=None, ks=(1, 3, 10), scoring: Optional[str] = None,
                                      batch_size: Optional[int] = None):
         """MR / MRR / Hits@k of the true relations among all relations, filtered, overall and per relation

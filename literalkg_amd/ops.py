@@ -2717,3 +2717,99 @@ def relation_order(scores: torch.Tensor, truth: Optional[torch.Tensor] = None, f
         N.call("lkg_relation_order_f32", n, n_rel, N.ptr(scores), _ld(scores), N.ptr(truth), *fargs(), top_k,
                N.ptr(better), N.ptr(equal), N.ptr(ids), N.ptr(top), _stream())
     return better, equal, ids, top
+
+
+# ----------------------------------------------------------------------------- threshold retrieval (lkg_accept.hip)
+def _accept_operands(what: str, q, p, pn, thr, filt, filter_row, filter_rel, cand_ids, splits, qn):
+    """The checked operands of an accept launch: (q, p, thr, qn, cand_ids, fargs, splits)."""
+    _need_gpu(q, p, pn, thr, cand_ids, filter_row, filter_rel, qn)
+    _, splits = _check_k_splits(what, 1, splits)
+    q, p = _f32_rows(q), _f32_rows(p)
+    n_q, kd = q.shape
+    n_c = p.shape[0]
+    if p.shape[1] != kd or (pn is not None and pn.numel() != n_c) or (cand_ids is not None and cand_ids.numel() != n_c):
+        raise ValueError(f"{what}: queries {tuple(q.shape)}, candidates {tuple(p.shape)}")
+    if thr.dtype != torch.float32 or thr.dim() != 1 or thr.numel() != n_q:
+        raise ValueError(f"{what}: thr must be a float32 tensor of {n_q} elements (one per query)")
+    if max(n_q, n_c) > 2 ** 31 - 2:
+        raise ValueError(f"{what}: {n_q} queries, {n_c} candidates (at most 2^31 - 2 each)")
+    if pn is not None and qn is None:
+        qn = rank_sqnorm(q)
+    cand_ids = _i64(cand_ids.reshape(-1)) if cand_ids is not None else None
+    fargs = _filter_args(what, filt, filter_row, filter_rel, n_q)
+    return q, p, thr.contiguous(), (qn if pn is not None else None), cand_ids, fargs, splits
+
+
+def accept_count(q: torch.Tensor, p: torch.Tensor, pn: Optional[torch.Tensor], thr: torch.Tensor, higher: bool = False,
+                 filt=None, filter_row: Optional[torch.Tensor] = None, filter_rel: Optional[torch.Tensor] = None,
+                 cand_ids: Optional[torch.Tensor] = None, splits: int = 0, qn: Optional[torch.Tensor] = None):
+    """int32[n_q]: per query row of q the number of candidate rows of p whose reported score -- topk_select's ``values``,
+    ||q||^2 + s (pn given) or -s / 2 (dot), bit for bit -- passes thr[i] in one float32 compare (<=; higher: >=; a NaN
+    never passes) and that the filter does not drop (filt, filter_row, filter_rel, cand_ids as for topk_select).
+    lkg_accept_count_f32: nothing of the size of the result is written.  qn: rank_sqnorm(q) if the caller has it."""
+    q, p, thr, qn, cand_ids, fargs, splits = _accept_operands("accept_count", q, p, pn, thr, filt, filter_row, filter_rel,
+                                                              cand_ids, splits, qn)
+    counts = torch.zeros(q.shape[0], dtype=torch.int32, device=q.device)
+    N.call("lkg_accept_count_f32", q.shape[0], p.shape[0], q.shape[1], N.ptr(q), _ld(q), N.ptr(p), _ld(p), N.ptr(pn),
+           N.ptr(qn), N.ptr(thr), int(bool(higher)), N.ptr(cand_ids), *fargs(), splits, N.ptr(counts), _stream())
+    return counts
+
+
+def accept_check_flag(flag: torch.Tensor):
+    """Raise if the emit pass refused a store (its flag is set): the two passes disagreed, the lists are incomplete."""
+    if int(flag.sum()) != 0:
+        raise RuntimeError("accept_emit: the emit pass met a candidate the count pass had not counted (nothing was written "
+                           "out of bounds; the result is incomplete and was dropped)")
+
+
+def accept_emit(q: torch.Tensor, p: torch.Tensor, pn: Optional[torch.Tensor], thr: torch.Tensor, counts: torch.Tensor,
+                higher: bool = False, filt=None, filter_row: Optional[torch.Tensor] = None,
+                filter_rel: Optional[torch.Tensor] = None, cand_ids: Optional[torch.Tensor] = None, splits: int = 0,
+                qn: Optional[torch.Tensor] = None, total: Optional[int] = None):
+    """(rowptr int64[n_q + 1], ids int64[M], scores f32[M], values f32[M]): the accepted candidates of accept_count's
+    arguments, row i in [rowptr[i], rowptr[i + 1]) in NO particular order (accept_order sorts) -- ids are cand_ids[c]
+    (None: c), scores the kernel score s, values the reported one.  counts: accept_count's result for the same
+    arguments; total: its sum if the caller has it.  lkg_accept_emit_f32 refuses any store outside a row's counted
+    range and raises a flag, which surfaces here as a RuntimeError."""
+    q, p, thr, qn, cand_ids, fargs, splits = _accept_operands("accept_emit", q, p, pn, thr, filt, filter_row, filter_rel,
+                                                              cand_ids, splits, qn)
+    n_q, dev = q.shape[0], q.device
+    if counts.dtype != torch.int32 or counts.dim() != 1 or counts.numel() != n_q or counts.device != dev:
+        raise ValueError(f"accept_emit: counts must be an int32 tensor of {n_q} elements on {dev}")
+    counts = counts.contiguous()
+    rowptr = torch.zeros(n_q + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(counts, 0, out=rowptr[1:])
+    m = int(rowptr[-1]) if total is None else int(total)
+    ids = torch.empty(m, dtype=torch.int64, device=dev)
+    scores = torch.empty(m, dtype=torch.float32, device=dev)
+    values = torch.empty(m, dtype=torch.float32, device=dev)
+    if m == 0:
+        return rowptr, ids, scores, values
+    cursor = torch.zeros(n_q, dtype=torch.int32, device=dev)
+    flag = torch.zeros(1, dtype=torch.int32, device=dev)
+    N.call("lkg_accept_emit_f32", n_q, p.shape[0], q.shape[1], N.ptr(q), _ld(q), N.ptr(p), _ld(p), N.ptr(pn), N.ptr(qn),
+           N.ptr(thr), int(bool(higher)), N.ptr(cand_ids), *fargs(), splits, N.ptr(counts), N.ptr(rowptr), N.ptr(cursor),
+           N.ptr(ids), N.ptr(scores), N.ptr(values), N.ptr(flag), _stream())
+    accept_check_flag(flag)
+    return rowptr, ids, scores, values
+
+
+def accept_order(rowptr: torch.Tensor, ids: torch.Tensor, scores: torch.Tensor, values: torch.Tensor, id_bound: int):
+    """(ids, scores, values) of accept_emit with every row sorted by ascending score -- float comparison, -0.0 == +0.0 --
+    then ascending id (lkg_accept_order: two stable radix sorts).  ids lie in [0, id_bound)."""
+    _need_gpu(rowptr, ids, scores, values)
+    m, n_q = ids.numel(), rowptr.numel() - 1
+    if rowptr.dtype != torch.int64 or ids.dtype != torch.int64 or scores.dtype != torch.float32 or \
+            values.dtype != torch.float32 or scores.numel() != m or values.numel() != m or n_q < 0:
+        raise ValueError("accept_order: rowptr int64[n_q + 1], ids int64[M], scores and values float32[M]")
+    if m > 2 ** 31 - 2:
+        raise ValueError(f"accept_order: {m} entries in one call (at most 2^31 - 2): use batches")
+    rowptr, ids, scores, values = rowptr.contiguous(), ids.contiguous(), scores.contiguous(), values.contiguous()
+    out = torch.empty_like(ids), torch.empty_like(scores), torch.empty_like(values)
+    if m == 0:
+        return out
+    ws_bytes = int(N.load().lkg_accept_order_workspace(m, n_q))
+    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=ids.device)
+    N.call("lkg_accept_order", m, n_q, int(id_bound), N.ptr(rowptr), N.ptr(ids), N.ptr(scores), N.ptr(values),
+           N.ptr(out[0]), N.ptr(out[1]), N.ptr(out[2]), N.ptr(ws), ws_bytes, _stream())
+    return out
