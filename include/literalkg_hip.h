@@ -853,6 +853,47 @@ int lkg_relation_order_f32(int64_t n, int32_t n_rel, const float *scores, int64_
                            const int32_t *col, const int32_t *eptr, const int32_t *rel, int32_t top_k, int32_t *better,
                            int32_t *equal, int64_t *top_ids, float *top_scores, void *stream);
 
+/* Multi-answer retrieval (lkg_retrieval.hip; literalkg_amd/retrieval.py): the place of every answer of a query in the
+ * query's ranked list.  Candidates, cand_ids, the filter structure and the kernel score s(i, c) as for lkg_topk_select_f32,
+ * bit for bit.  The answers of the queries are given as KEYS (s, id): key_s / key_id, per query a contiguous run sorted by
+ * ascending s (float comparison) and then ascending id, as lkg_accept_order sorts, the s from lkg_triple_scores_f32, no
+ * NaN.  A ROW is a query vector (row row_q[i] of q) with a slice of key_n[i] <= LKG_RETRIEVAL_SLICE consecutive keys of its
+ * query starting at key_off[i]; the query's whole run is qkey_off[i] .. + qkey_n[i] and its slices are cut every
+ * LKG_RETRIEVAL_SLICE keys.  buckets is int32[n_rows][LKG_RETRIEVAL_SLICE].
+ *
+ * lkg_retrieval_prepare_f32: WRITES every bucket of every row: bucket 0 = -(key_off[i] - qkey_off[i]), the others 0, less
+ *     one in bucket g for every filter entry of the query (row filter_row[i], relation filter_rel[i], < 0: any) that is a
+ *     candidate, whose score is not NaN, that is not one of the query's keys, and that has g < key_n[i] of the row's keys
+ *     before it.  cand_slot int32[n_ids] maps an entity id to its candidate row, -1 = not a candidate; NULL = the identity
+ *     (n_ids == n_cand).  rowptr NULL = no filter.
+ * lkg_retrieval_count_f32  : bucket g of row i += #{c : s(i, c) not NaN, (s, id(c)) not a key of the row, exactly g <
+ *     key_n[i] of the row's keys before (s, id(c))} (int32 atomics, one per non-zero bucket per workgroup; the scores are
+ *     never stored).  After prepare + count the inclusive prefix of a row's buckets up to g is the number of listed
+ *     candidates that are not answers of the query ahead of key g.
+ * lkg_retrieval_finish     : per query u with keys qkey_ptr[u] .. qkey_ptr[u + 1] (int64[n_q + 1]) and rows row_base[u] ..:
+ *     before[j] = that prefix and position[j] = 1 + before[j] + (index of key j in its query), int64 per key.  With hits
+ *     non-NULL also, per query and k = ks[x]: hits[u, x] = #{position <= k}; ndcg[u, x] = (sum over position <= k of
+ *     disc[position]) / icum[min(n_answers[u], k)]; ap[u] = (sum_i i / position_i) / n_answers[u]; rr[u] = 1 / position_1
+ *     (0 without keys) -- float64, summed in an order fixed by the sorted positions.  disc / icum: double[k_tab + 1], disc[p]
+ *     = 1 / log2(1 + p), icum its running sums, k_tab >= min(max ks, the largest position).
+ * n_rows, n_cand, n_ids <= INT32_MAX - 1; empty inputs launch nothing; addressing is 64-bit.                           */
+#define LKG_RETRIEVAL_SLICE 32
+int lkg_retrieval_prepare_f32(int64_t n_rows, int64_t n_cand, int32_t k, const float *q, int64_t ldq,
+                              const int64_t *row_q, const float *p, int64_t ldp, const float *pn, int64_t n_ids,
+                              const int32_t *cand_slot, const int64_t *key_off, const int32_t *key_n,
+                              const int64_t *qkey_off, const int64_t *qkey_n, const float *key_s, const int64_t *key_id,
+                              const int64_t *filter_row, const int64_t *filter_rel, const int32_t *rowptr,
+                              const int32_t *col, const int32_t *eptr, const int32_t *rel, int32_t *buckets,
+                              void *stream);
+int lkg_retrieval_count_f32(int64_t n_rows, int64_t n_cand, int32_t k, const float *q, int64_t ldq, const int64_t *row_q,
+                            const float *p, int64_t ldp, const float *pn, const int64_t *cand_ids,
+                            const int64_t *key_off, const int32_t *key_n, const float *key_s, const int64_t *key_id,
+                            int32_t *buckets, void *stream);
+int lkg_retrieval_finish(int64_t n_q, const int64_t *qkey_ptr, const int64_t *row_base, const int64_t *n_answers,
+                         const int32_t *buckets, int32_t n_ks, const int64_t *ks, int64_t k_tab, const double *disc,
+                         const double *icum, int64_t *before, int64_t *position, int64_t *hits, double *ndcg, double *ap,
+                         double *rr, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,6 +13,7 @@ from .graph import KGStructure           # noqa: F401
 from .ranking import KnownTriples, RankResult, evaluate_ranking   # noqa: F401
 from .topk import TopKResult, predict_topk   # noqa: F401
 from .accepted import AcceptedResult, count_accepted, predict_accepted   # noqa: F401
+from .retrieval import AnswerRanks, evaluate_retrieval, rank_answers   # noqa: F401
 from .pairmlp import (FoldedMLPHead, evaluate_mlp_classification, evaluate_mlp_ranking,   # noqa: F401
                       fold_mlp_head, mlp_scores, rank_pairs_mlp, score_pairs_mlp)
 from .triples import (TripleThresholds, evaluate_triple_classification, fit_triple_thresholds,   # noqa: F401
@@ -24,4 +25,5 @@ __all__ = ["LiteralKG", "Aggregator", "Gate", "GateMul", "KGStructure", "KnownTr
            "TopKResult", "predict_topk", "FoldedMLPHead", "fold_mlp_head", "mlp_scores", "rank_pairs_mlp",
            "evaluate_mlp_ranking", "score_pairs_mlp", "evaluate_mlp_classification", "TripleThresholds", "score_triples",
            "fit_triple_thresholds", "evaluate_triple_classification", "RelationTopK", "score_relations", "rank_relations",
-           "predict_relations", "evaluate_relation_prediction", "AcceptedResult", "predict_accepted", "count_accepted"]
+           "predict_relations", "evaluate_relation_prediction", "AcceptedResult", "predict_accepted", "count_accepted",
+           "AnswerRanks", "rank_answers", "evaluate_retrieval"]

@@ -120,6 +120,10 @@ PROTOTYPES = {
                             vp, vp, vp, vp, vp],
     "lkg_accept_order_workspace": [i64, i64],
     "lkg_accept_order": [i64, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp],
+    "lkg_retrieval_prepare_f32": [i64, i64, i32, vp, i64, vp, vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                  vp, vp, vp, vp],
+    "lkg_retrieval_count_f32": [i64, i64, i32, vp, i64, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp],
+    "lkg_retrieval_finish": [i64, vp, vp, vp, vp, i32, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp],
 }
 _RESTYPE = {"lkg_last_error": C.c_char_p, "lkg_csr_build_device_workspace": C.c_int64,
             "lkg_gemm_tall_workspace": C.c_int64, "lkg_gemm_workspace": C.c_int64,

@@ -790,6 +790,23 @@ class LiteralKG(nn.Module):
         return count_accepted(self, ids, r, thresholds, side=side, known=known, scoring=scoring, candidates=candidates,
                               batch_size=batch_size, splits=splits)
 
+    def rank_answers(self, h, r, t, side: str = "tail", known=None, scoring: Optional[str] = None, candidates=None,
+                     batch_size: Optional[int] = None, ks=None):
+        """The place of every answer of every distinct query (h, r, ?) -- or (?, r, t) -- in the query's ranked list, each
+        query scored once however many answers it has (literalkg_amd/retrieval.py, rank_answers).  Returns a
+        retrieval.AnswerRanks."""
+        from .retrieval import rank_answers
+        return rank_answers(self, h, r, t, side=side, known=known, scoring=scoring, candidates=candidates,
+                            batch_size=batch_size, ks=ks)
+
+    def evaluate_retrieval(self, h, r, t, known=None, ks=(1, 3, 10), side: str = "tail", scoring: Optional[str] = None,
+                           candidates=None, batch_size: Optional[int] = None):
+        """precision@k / recall@k / hit@k / NDCG@k, MAP and MRR over the distinct queries of the triples, every answer
+        placed exactly at any depth (literalkg_amd/retrieval.py, evaluate_retrieval)."""
+        from .retrieval import evaluate_retrieval
+        return evaluate_retrieval(self, h, r, t, known=known, ks=ks, side=side, scoring=scoring, candidates=candidates,
+                                  batch_size=batch_size)
+
     def evaluate_relation_prediction(self, h, r, t, known=None, ks=(1, 3, 10), scoring: Optional[str] = None,
                                      batch_size: Optional[int] = None):
         """MR / MRR / Hits@k of the true relations among all relations, filtered, overall and per relation

@@ -2813,3 +2813,105 @@ def accept_order(rowptr: torch.Tensor, ids: torch.Tensor, scores: torch.Tensor, 
     N.call("lkg_accept_order", m, n_q, int(id_bound), N.ptr(rowptr), N.ptr(ids), N.ptr(scores), N.ptr(values),
            N.ptr(out[0]), N.ptr(out[1]), N.ptr(out[2]), N.ptr(ws), ws_bytes, _stream())
     return out
+
+
+# ----------------------------------------------------------------------------- multi-answer retrieval (lkg_retrieval.hip)
+RETRIEVAL_SLICE = 32                   # LKG_RETRIEVAL_SLICE: the keys of one row of the counting kernel
+
+
+def retrieval_count(q: torch.Tensor, row_q: torch.Tensor, p: torch.Tensor, pn: Optional[torch.Tensor],
+                    key_off: torch.Tensor, key_n: torch.Tensor, qkey_off: torch.Tensor, qkey_n: torch.Tensor,
+                    key_s: torch.Tensor, key_id: torch.Tensor, filt=None, filter_row: Optional[torch.Tensor] = None,
+                    filter_rel: Optional[torch.Tensor] = None, cand_ids: Optional[torch.Tensor] = None,
+                    cand_slot: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """int32[n_rows, RETRIEVAL_SLICE]: the buckets of lkg_retrieval_prepare_f32 + lkg_retrieval_count_f32.  Row i is the
+    query vector q[row_q[i]] with the key_n[i] <= RETRIEVAL_SLICE keys (key_s, key_id)[key_off[i] ..] -- a slice of its
+    query's sorted run qkey_off[i] .. + qkey_n[i] (ascending score by float comparison, then ascending id, no NaN; the
+    scores from triple_scores(reported=False)).  After the call the inclusive prefix of a row's buckets up to g is the
+    number of candidate rows of p that are not answers of the query, not NaN, not dropped by the filter, and sort before
+    key g.  filt, filter_row, filter_rel (per row), cand_ids as for topk_select; cand_slot: pair_mlp_cand_slot of cand_ids
+    over the filter's ids, for a caller that counts batch after batch."""
+    _need_gpu(q, row_q, p, pn, key_off, key_n, qkey_off, qkey_n, key_s, key_id, cand_ids, cand_slot, filter_row, filter_rel)
+    q, p = _f32_rows(q), _f32_rows(p)
+    kd, n_c = q.shape[1], p.shape[0]
+    row_q, key_off, qkey_off, qkey_n = (_i64(x.reshape(-1)) for x in (row_q, key_off, qkey_off, qkey_n))
+    n_rows = row_q.numel()
+    if p.shape[1] != kd or (pn is not None and pn.numel() != n_c) or (cand_ids is not None and cand_ids.numel() != n_c):
+        raise ValueError(f"retrieval_count: queries {tuple(q.shape)}, candidates {tuple(p.shape)}")
+    if key_n.dtype != torch.int32 or any(x.numel() != n_rows for x in (key_off, key_n, qkey_off, qkey_n)):
+        raise ValueError(f"retrieval_count: key_off, qkey_off, qkey_n int64 and key_n int32, {n_rows} elements each")
+    if key_s.dtype != torch.float32 or key_id.dtype != torch.int64 or key_s.numel() != key_id.numel():
+        raise ValueError("retrieval_count: the keys are float32 scores with int64 ids")
+    if max(n_rows, n_c) > 2 ** 31 - 2:
+        raise ValueError(f"retrieval_count: {n_rows} rows, {n_c} candidates (at most 2^31 - 2 each)")
+    buckets = torch.zeros((n_rows, RETRIEVAL_SLICE), dtype=torch.int32, device=q.device)
+    if n_rows == 0:
+        return buckets
+    if n_c == 0:
+        raise ValueError("retrieval_count: no candidates")
+    key_n, key_s, key_id = key_n.contiguous(), key_s.contiguous(), key_id.contiguous()
+    cand_ids = _i64(cand_ids.reshape(-1)) if cand_ids is not None else None
+    n_ids, slot = n_c, None
+    if filt is not None:
+        n_ids = filt[0].numel() - 1
+        if cand_ids is None and n_ids != n_c:
+            raise ValueError(f"retrieval_count: the filter covers {n_ids} rows, the candidates {n_c}")
+        if cand_ids is not None:
+            slot = cand_slot if cand_slot is not None else pair_mlp_cand_slot(n_ids, cand_ids)
+            if slot.numel() != n_ids or slot.dtype != torch.int32 or not slot.is_contiguous():
+                raise ValueError(f"retrieval_count: cand_slot must be a contiguous int32[{n_ids}]")
+    fargs = _filter_args("retrieval_count", filt, filter_row, filter_rel, n_rows)
+    N.call("lkg_retrieval_prepare_f32", n_rows, n_c, kd, N.ptr(q), _ld(q), N.ptr(row_q), N.ptr(p), _ld(p), N.ptr(pn), n_ids,
+           N.ptr(slot), N.ptr(key_off), N.ptr(key_n), N.ptr(qkey_off), N.ptr(qkey_n), N.ptr(key_s), N.ptr(key_id), *fargs(),
+           N.ptr(buckets), _stream())
+    N.call("lkg_retrieval_count_f32", n_rows, n_c, kd, N.ptr(q), _ld(q), N.ptr(row_q), N.ptr(p), _ld(p), N.ptr(pn),
+           N.ptr(cand_ids), N.ptr(key_off), N.ptr(key_n), N.ptr(key_s), N.ptr(key_id), N.ptr(buckets), _stream())
+    return buckets
+
+
+def retrieval_tables(k_tab: int, device):
+    """(disc, icum) float64[k_tab + 1] on the device: disc[p] = 1 / log2(1 + p) (disc[0] = 0) and its running sums --
+    built on the host, so no log2 runs on the device."""
+    import numpy as np
+    disc = np.zeros(int(k_tab) + 1, dtype=np.float64)
+    disc[1:] = 1.0 / np.log2(1.0 + np.arange(1, int(k_tab) + 1, dtype=np.float64))
+    return torch.from_numpy(disc).to(device), torch.from_numpy(np.cumsum(disc)).to(device)
+
+
+def retrieval_finish(qkey_ptr: torch.Tensor, row_base: torch.Tensor, buckets: torch.Tensor,
+                     n_answers: Optional[torch.Tensor] = None, ks: Optional[Sequence[int]] = None,
+                     k_tab: Optional[int] = None):
+    """(before int64[M], position int64[M], metrics) of lkg_retrieval_finish: query u owns the keys qkey_ptr[u] ..
+    qkey_ptr[u + 1] and the rows row_base[u] .. of ``buckets`` (retrieval_count's, one row per RETRIEVAL_SLICE keys).
+    With ks (positive integers) and n_answers (int64 per query: its answers, the NaN ones included) metrics is
+    (hits int64[Q, len(ks)], ndcg float64[Q, len(ks)], ap float64[Q], rr float64[Q]), else None.  k_tab: an upper bound of
+    every position (the number of candidates); the tables stop at min(max(ks), k_tab)."""
+    _need_gpu(qkey_ptr, row_base, buckets, n_answers)
+    qkey_ptr, row_base = _i64(qkey_ptr.reshape(-1)), _i64(row_base.reshape(-1))
+    n_q, dev = row_base.numel(), qkey_ptr.device
+    if qkey_ptr.numel() != n_q + 1 or buckets.dtype != torch.int32 or buckets.dim() != 2 or \
+            buckets.shape[1] != RETRIEVAL_SLICE or not buckets.is_contiguous():
+        raise ValueError(f"retrieval_finish: qkey_ptr int64[n_q + 1], row_base int64[n_q], buckets a contiguous "
+                         f"int32[rows, {RETRIEVAL_SLICE}]")
+    m = int(qkey_ptr[-1]) if n_q else 0
+    before = torch.empty(m, dtype=torch.int64, device=dev)
+    position = torch.empty(m, dtype=torch.int64, device=dev)
+    metrics, margs = None, [None, 0, None, 0, None, None]
+    outs = [None] * 4
+    if ks is not None:
+        if n_answers is None or n_answers.numel() != n_q:
+            raise ValueError("retrieval_finish: the metrics need n_answers, one per query")
+        n_answers = _i64(n_answers.reshape(-1))
+        top = max(ks, default=0)
+        k_tab = int(top if k_tab is None else min(top, int(k_tab)))
+        disc, icum = retrieval_tables(k_tab, dev)
+        ks_t = torch.tensor(list(ks), dtype=torch.int64, device=dev)
+        metrics = (torch.zeros((n_q, len(ks)), dtype=torch.int64, device=dev),
+                   torch.zeros((n_q, len(ks)), dtype=torch.float64, device=dev),
+                   torch.zeros(n_q, dtype=torch.float64, device=dev), torch.zeros(n_q, dtype=torch.float64, device=dev))
+        margs = [N.ptr(n_answers), len(ks), N.ptr(ks_t), k_tab, N.ptr(disc), N.ptr(icum)]
+        outs = [N.ptr(x) for x in metrics]
+    if n_q:
+        N.call("lkg_retrieval_finish", n_q, N.ptr(qkey_ptr), N.ptr(row_base), margs[0], N.ptr(buckets), *margs[1:],
+               N.ptr(before), N.ptr(position), *outs, _stream())
+    return before, position, metrics
