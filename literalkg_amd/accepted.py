@@ -25,9 +25,8 @@ import torch
 
 from . import _queries as Q
 from . import ops
-from .ranking import KnownTriples, _check_scoring, scoring_groups
-from .topk import _check_side
-from .triples import TripleThresholds, _lower_is_better, _threshold_list
+from .ranking import KnownTriples
+from .triples import TripleThresholds, threshold_list
 
 
 @dataclass
@@ -65,33 +64,22 @@ def _query_thresholds(model, thresholds, scoring: str, r: Optional[torch.Tensor]
     if r is None:
         if isinstance(thresholds, (TripleThresholds, torch.Tensor)):
             raise ValueError("without relations (r=None) the threshold must be one float")
-        return _threshold_list(SimpleNamespace(n_relations=1), thresholds, scoring)
-    return _threshold_list(model, thresholds, scoring)
+        return threshold_list(SimpleNamespace(n_relations=1), thresholds, scoring)
+    return threshold_list(model, thresholds, scoring)
 
 
 def _front(model, ids, r, thresholds, side, known, scoring, candidates, batch_size, splits):
-    """The argument checks of predict_topk, in its order, and the thresholds; everything before any device work."""
-    side = _check_side(side)
-    scoring = scoring if scoring is not None else model.scoring
-    if scoring == "mlp":
-        raise ValueError("scoring='mlp' has no acceptance threshold here: the pair head's lists come from "
-                         "predict_topk(scoring='mlp')")
-    scoring = _check_scoring(scoring)
-    Q.check_ids("ids", ids)
-    if r is None:
-        if scoring != "dot":
-            raise ValueError(f"scoring={scoring!r} needs the relations r (only 'dot' can filter without them)")
-    else:
-        Q.check_ids("r", r)
-        if r.numel() != ids.numel():
-            raise ValueError(f"ids and r have different lengths ({ids.numel()}, {r.numel()})")
+    """The argument checks predict_topk makes, through the same functions in the same order, and the thresholds;
+    everything before any device work."""
+    side = Q.check_one_side(side, "top-k ranks one side at a time")
+    scoring = Q.resolve_scoring(model, scoring, "scoring='mlp' has no acceptance threshold here: the pair head's lists "
+                                "come from predict_topk(scoring='mlp')")
+    Q.check_query_lists(ids, r, scoring)
     if candidates is not None:
         Q.check_ids("candidates", candidates)
     Q.check_batch_size(batch_size)
-    if isinstance(splits, bool) or int(splits) != splits or not 0 <= splits <= ops.TOPK_MAX_SPLITS:
-        raise ValueError(f"splits must be an integer in [0, {ops.TOPK_MAX_SPLITS}], got {splits!r}")
-    if scoring == "transr" and getattr(model, "gat_trans_M", None) is None:
-        raise ValueError("scoring='transr' needs a model with gat_trans_M (built with scoring='transr')")
+    Q.check_splits(splits)
+    Q.check_transr_model(model, scoring)
     thr = _query_thresholds(model, thresholds, scoring, r)
     Q.check_known_entities(known, model)
     Q.check_unique(candidates)
@@ -106,27 +94,20 @@ def _run(model, ids, r, thr, side, known, scoring, cand, batch_size, splits, max
     total their entries; with max_total None only the count pass runs."""
     dev = ids.device
     b = ids.numel()
-    higher = not _lower_is_better(scoring)
+    higher = not Q.lower_is_better(scoring)
     filt = known.for_side(side) if known is not None else None
-    alpha = 1.0 if side == "tail" else -1.0             # q = P_r[h] + e_r  /  q = P_r[t] - e_r
-    frel_all = Q.filter_relations(r, b, dev)
     thr_t = torch.tensor(thr, dtype=torch.float32, device=dev)
     thr_q = thr_t[r] if r is not None else thr_t.expand(b).contiguous()
     counts = torch.zeros(b, dtype=torch.int64, device=dev)
     chunks, total = [], 0
     with torch.no_grad():
-        table = model._table_for_inference().detach()
-        for p, pn, pos in scoring_groups(model, scoring, table, r, b):
-            qid, rel = ids[pos], (r[pos] if r is not None else None)
-            q = ops.rank_queries(p, qid, None if scoring == "dot" else model.relation_embed.weight.detach(), rel, alpha)
-            qn = ops.rank_sqnorm(q) if pn is not None else None
-            if cand is not None:                         # the candidate rows, scored with the same bits
-                p = ops.gather_rows(p, cand)
-                pn = ops.rank_sqnorm(p) if pn is not None else None
-            frel, tq = frel_all[pos], thr_q[pos]
+        for g in Q.query_groups(model, scoring, side, ids, r, cand):
+            pos = g.pos
+            qn = ops.rank_sqnorm(g.q) if g.pn is not None else None
+            tq = thr_q[pos]
             for lo, hi in Q.batches(pos.numel(), batch_size):
-                args = (q[lo:hi], p, pn, tq[lo:hi])
-                kw = dict(higher=higher, filt=filt, filter_row=qid[lo:hi], filter_rel=frel[lo:hi], cand_ids=cand,
+                args = (g.q[lo:hi], g.p, g.pn, tq[lo:hi])
+                kw = dict(higher=higher, filt=filt, filter_row=g.qid[lo:hi], filter_rel=g.frel[lo:hi], cand_ids=cand,
                           splits=splits, qn=None if qn is None else qn[lo:hi])
                 cnt = ops.accept_count(*args, **kw)
                 m = int(cnt.sum())
@@ -140,7 +121,6 @@ def _run(model, ids, r, thr, side, known, scoring, cand, batch_size, splits, max
                 rowptr, ii, ss, vv = ops.accept_emit(*args, cnt, total=m, **kw)
                 ii, ss, vv = ops.accept_order(rowptr, ii, ss, vv, model.n_entities)
                 chunks.append((pos[lo:hi], rowptr, ii, ss, vv))
-            del p, pn, q
     return counts, chunks, total
 
 

@@ -21,15 +21,8 @@ import torch
 
 from . import _queries as Q
 from . import ops
-from ._queries import SIDES, RankResult, metrics_from_counts, realistic_rank  # noqa: F401  (public under this module)
-
-SCORINGS = ("transr", "transe", "dot")
-
-
-def _check_scoring(scoring: str) -> str:
-    if scoring not in SCORINGS:
-        raise ValueError(f"scoring must be one of {SCORINGS}, got {scoring!r}")
-    return scoring
+from ._queries import (SCORINGS, SIDES, RankResult, metrics_from_counts,  # noqa: F401  (public under this module)
+                       realistic_rank, scoring_groups)
 
 
 def _check_triples(h, r, t):
@@ -66,45 +59,13 @@ class KnownTriples:
 def _count_group(model, scoring, side, p, pn, pos, h, r, t, known, batch_size, better, equal):
     """better / equal of one side for the queries at positions pos, against the candidate rows p (squared norms pn)."""
     q_ids, truth = (h, t) if side == "tail" else (t, h)
-    alpha = 1.0 if side == "tail" else -1.0              # q = T_h W_r + e_r  /  q = T_t W_r - e_r
     filt = known.for_side(side) if known is not None else None
     ids, tru, rel = q_ids[pos], truth[pos], r[pos]
-    q = ops.rank_queries(p, ids, None if scoring == "dot" else model.relation_embed.weight.detach(), rel, alpha)
+    q, _, _ = Q.side_queries(model, scoring, side, p, pn, ids, rel)
     for lo, hi in Q.batches(pos.numel(), batch_size):
         bb, ee, _ = ops.rank_count(q[lo:hi], p, pn, tru[lo:hi], filt, ids[lo:hi], rel[lo:hi])
         better[pos[lo:hi]] = bb
         equal[pos[lo:hi]] = ee
-
-
-def scoring_groups(model, scoring: str, table: torch.Tensor, r: Optional[torch.Tensor], b: Optional[int] = None):
-    """Check the table's width against the scoring and return a generator of (p, pn, pos): the candidate rows, their
-    squared norms (None for dot) and the positions of the queries they serve.  TransR: one projection P_r = T W_r per
-    relation present in r (the tall GEMM, one rowmax for all), each alive while the caller uses it; otherwise the table
-    itself, serving all b = len(r) queries (r may be None then).  Shared by ranking and top-k (topk.py), so both score
-    with the same P_r, bit for bit."""
-    c = table.shape[1]
-    dev = table.device
-    if scoring == "transe" and c != model.relation_dim:
-        raise ValueError(f"scoring='transe' needs the table width ({c}) to equal relation_dim ({model.relation_dim})")
-    if scoring == "transr":
-        w = model.gat_trans_M.detach()
-        if w.shape[1] != c:
-            raise ValueError(f"gat_trans_M is {tuple(w.shape)} for a table of width {c}")
-        perm, seg = ops.group_by_key(r, model.n_relations)
-        perm, seg = perm.long(), seg.tolist()
-        rowmax = ops.row_absmax(table)
-
-        def groups():
-            for rr in range(model.n_relations):
-                if seg[rr + 1] > seg[rr]:
-                    p = ops.gemm_tall([table], [[w[rr]]], trans_b=False, rowmax=rowmax)
-                    yield p, ops.rank_sqnorm(p), perm[seg[rr]:seg[rr + 1]]
-    else:
-        n = r.numel() if b is None else int(b)
-
-        def groups():
-            yield table, (ops.rank_sqnorm(table) if scoring == "transe" else None), torch.arange(n, device=dev)
-    return groups()
 
 
 def rank_triples(model, h: torch.Tensor, r: torch.Tensor, t: torch.Tensor, side: str = "tail",
@@ -113,11 +74,10 @@ def rank_triples(model, h: torch.Tensor, r: torch.Tensor, t: torch.Tensor, side:
     """Filtered ranks of the triples (h, r, t) on the model's inference table (see the module docstring).  The model's
     mode is left as it is (evaluate_ranking switches to eval); nothing of the model is changed."""
     side = Q.check_side(side)
-    scoring = _check_scoring(scoring if scoring is not None else model.scoring)
+    scoring = Q.resolve_scoring(model, scoring)
     _check_triples(h, r, t)
     Q.check_batch_size(batch_size)
-    if scoring == "transr" and getattr(model, "gat_trans_M", None) is None:
-        raise ValueError("scoring='transr' needs a model with gat_trans_M (built with scoring='transr')")
+    Q.check_transr_model(model, scoring)
     Q.check_known_entities(known, model)
     dev = model.entity_embed.weight.device
     b = h.numel()
@@ -142,7 +102,7 @@ def evaluate_ranking(model, h: torch.Tensor, r: torch.Tensor, t: torch.Tensor, k
     restores the model's previous mode."""
     ks = Q.check_ks(ks)
     side = Q.check_side(side)
-    _check_scoring(scoring if scoring is not None else model.scoring)
+    Q.resolve_scoring(model, scoring)
     with Q.eval_mode(model):
         res = rank_triples(model, h, r, t, side=side, known=known, scoring=scoring, batch_size=batch_size)
     return Q.ranking_metrics(res, ks)

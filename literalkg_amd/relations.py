@@ -29,7 +29,6 @@ from . import _queries as Q
 from . import ops
 from . import triples as T
 from .ranking import KnownTriples
-from .topk import _check_k
 
 PROJECT: Optional[str] = None      # 'transr' projections, as triples.PROJECT: None = the distinct rows of a batch when they
 #                                    are fewer than the entities; 'distinct' / 'full' force a route (the choice changes no bit)
@@ -45,10 +44,9 @@ class RelationTopK:
 
 
 def _check_scoring(model, scoring: Optional[str]) -> str:
-    scoring = scoring if scoring is not None else model.scoring
-    if scoring == "dot":
+    if (scoring if scoring is not None else model.scoring) == "dot":
         raise ValueError("scoring='dot' has no relation prediction: the dot product does not depend on the relation")
-    return T._check_scoring(model, scoring)
+    return T.check_scoring(model, scoring)
 
 
 def _check_pairs(h, t, r=None):
@@ -85,7 +83,7 @@ def _check_known(known, model):
 def _check_common(model, scoring, side, h, t, r, known, batch_size, relation_chunk):
     """Every argument check that needs no device; (scoring, side)."""
     scoring = _check_scoring(model, scoring)
-    side = T._check_side(side)
+    side = Q.check_one_side(side, "a triple is scored from one side at a time")
     _check_pairs(h, t, r)
     Q.check_batch_size(batch_size)
     _check_chunk(relation_chunk)
@@ -110,17 +108,14 @@ def _scan(model, scoring: str, side: str, h, t, batch_size, relation_chunk) -> t
     """float32[P, n_relations] of the checked, non-empty pairs on the model's device (ids already there)."""
     dev = h.device
     qid, cid = (h, t) if side == "tail" else (t, h)
-    alpha = 1.0 if side == "tail" else -1.0              # q = P_j[h] + e_j  /  q = P_j[t] - e_j
+    alpha = Q.side_alpha(side)                           # q = P_j[h] + e_j  /  q = P_j[t] - e_j
     n, n_rel = h.numel(), model.n_relations
     out = torch.empty((n, n_rel), dtype=torch.float32, device=dev)
     with torch.no_grad():
         table = model._table_for_inference().detach()
-        n_ent, c = table.shape
-        e = model.relation_embed.weight.detach()
+        Q.check_table_shape(model, scoring, table)
+        e = Q.relation_rows(model, scoring)
         if scoring == "transe":
-            if c != model.relation_dim:
-                raise ValueError(f"scoring='transe' needs the table width ({c}) to equal relation_dim "
-                                 f"({model.relation_dim})")
             pn = ops.rank_sqnorm(table)
             chunk = n_rel if relation_chunk is None else int(relation_chunk)
             for lo, hi in Q.batches(n, batch_size):
@@ -129,22 +124,12 @@ def _scan(model, scoring: str, side: str, h, t, batch_size, relation_chunk) -> t
                     ops.relation_scores(table, pn, qid[lo:hi], cid[lo:hi], e[r0:r1], alpha, out=out[lo:hi, r0:r1])
             return out
         w = model.gat_trans_M.detach()
-        if w.shape[1] != c:
-            raise ValueError(f"gat_trans_M is {tuple(w.shape)} for a table of width {c}")
         k = w.shape[2]
         kp = (k + 3) // 4 * 4                            # rows of the slab start 16 bytes apart: the kernel's float4 loads
         batch, chunk = _default_sizes(n, n_rel, k, batch_size, relation_chunk)
         rowmax = ops.row_absmax(table)
         for lo, hi in Q.batches(n, batch):
-            m = hi - lo
-            full = PROJECT == "full"
-            if not full:
-                uniq, inv = torch.unique(torch.cat((qid[lo:hi], cid[lo:hi])), return_inverse=True)
-                full = PROJECT is None and uniq.numel() >= n_ent
-            if full:
-                rows, rm, qi, ci = table, rowmax, qid[lo:hi], cid[lo:hi]
-            else:
-                rows, rm, qi, ci = ops.gather_rows(table, uniq), rowmax[uniq], inv[:m], inv[m:]
+            rows, rm, qi, ci = Q.rows_to_project(table, rowmax, qid[lo:hi], cid[lo:hi], PROJECT)   # once per pair batch
             n_rows = rows.shape[0]
             for r0 in range(0, n_rel, chunk):
                 r1 = min(r0 + chunk, n_rel)
@@ -207,7 +192,7 @@ def predict_relations(model, h: torch.Tensor, t: torch.Tensor, k: int = 1, known
     (lowest score) first, ties to the smaller relation id, a NaN score never listed; rows with fewer than k eligible
     relations are padded with -1 / NaN.  k in [1, ops.TOPK_MAX].  The model's mode, parameters and caches are left as
     they are."""
-    k = _check_k(k)
+    k = Q.check_k(k)
     scoring, side = _check_common(model, scoring, side, h, t, None, known, batch_size, relation_chunk)
     dev = model.entity_embed.weight.device
     if h.numel() == 0:

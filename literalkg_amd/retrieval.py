@@ -35,9 +35,7 @@ import torch
 
 from . import _queries as Q
 from . import ops
-from .ranking import KnownTriples, _check_scoring, scoring_groups
-from .topk import _check_side
-from .triples import _check_triples
+from .ranking import KnownTriples
 
 
 @dataclass
@@ -69,26 +67,18 @@ class AnswerRanks:
 
 def _front(model, h, r, t, side, known, scoring, candidates, batch_size):
     """Every argument check, before any device work; (side, scoring, device)."""
-    side = _check_side(side)
-    scoring = scoring if scoring is not None else model.scoring
-    if scoring == "mlp":
-        raise ValueError("scoring='mlp' has no kernel score to place answers by here: the pair head's filtered ranks come "
-                         "from rank_pairs_mlp")
-    scoring = _check_scoring(scoring)
+    side = Q.check_one_side(side, "top-k ranks one side at a time")
+    scoring = Q.resolve_scoring(model, scoring, "scoring='mlp' has no kernel score to place answers by here: the pair "
+                                "head's filtered ranks come from rank_pairs_mlp")
+    Q.check_has_relations(r, scoring)
     if r is None:
-        if scoring != "dot":
-            raise ValueError(f"scoring={scoring!r} needs the relations r (only 'dot' can filter without them)")
-        Q.check_ids("h", h)
-        Q.check_ids("t", t)
-        if h.numel() != t.numel():
-            raise ValueError(f"h and t have different lengths ({h.numel()}, {t.numel()})")
+        Q.check_id_pair(h, t, ("h", "t"))
     else:
-        _check_triples(h, r, t)
+        Q.check_triple_lists(h, r, t)
     if candidates is not None:
         Q.check_ids("candidates", candidates)
     Q.check_batch_size(batch_size)
-    if scoring == "transr" and getattr(model, "gat_trans_M", None) is None:
-        raise ValueError("scoring='transr' needs a model with gat_trans_M (built with scoring='transr')")
+    Q.check_transr_model(model, scoring)
     Q.check_known_entities(known, model)
     Q.check_unique(candidates)
     dev = model.entity_embed.weight.device
@@ -152,7 +142,6 @@ def _run(model, h, r, t, side, known, scoring, cand, batch_size, ks) -> AnswerRa
         if bool((slot[a_id] < 0).any()):
             raise ValueError("candidates must contain every answer (the evaluated entity of every triple)")
     filt = known.for_side(side) if known is not None else None
-    alpha = 1.0 if side == "tail" else -1.0             # q = P_r[h] + e_r  /  q = P_r[t] - e_r
     a_before = torch.full((up.numel(),), -1, dtype=torch.int64, device=dev)
     a_position = torch.full((up.numel(),), -1, dtype=torch.int64, device=dev)
     res = AnswerRanks(query, None, None, None, q_ent, q_rel, n_answers, side, a_query, a_id, a_before, a_position)
@@ -162,17 +151,12 @@ def _run(model, h, r, t, side, known, scoring, cand, batch_size, ks) -> AnswerRa
         res.ndcg = torch.zeros((n_q, len(ks)), dtype=torch.float64, device=dev)
         res.ap = torch.zeros(n_q, dtype=torch.float64, device=dev)
         res.rr = torch.zeros(n_q, dtype=torch.float64, device=dev)
+    e, alpha = Q.relation_rows(model, scoring), Q.side_alpha(side)
     with torch.no_grad():
-        table = model._table_for_inference().detach()
-        e = None if scoring == "dot" else model.relation_embed.weight.detach()
-        for p, pn, pos in scoring_groups(model, scoring, table, q_rel if r is not None else None, n_q):
-            qid, rel = q_ent[pos], (q_rel[pos] if r is not None else None)
-            q = ops.rank_queries(p, qid, e, rel, alpha)
-            key_ans, key_s, key_id, counts, qkey_ptr = _group_answers(model, scoring, p, pn, e, alpha, q_ent, q_rel,
-                                                                      a_query, a_ptr, a_id, pos)
-            if cand is not None:                         # the candidate rows, scored with the same bits
-                p = ops.gather_rows(p, cand)
-                pn = ops.rank_sqnorm(p) if pn is not None else None
+        for g in Q.query_groups(model, scoring, side, q_ent, q_rel if r is not None else None, cand):
+            pos = g.pos
+            key_ans, key_s, key_id, counts, qkey_ptr = _group_answers(model, scoring, g.table, g.table_n, e, alpha, q_ent,
+                                                                      q_rel, a_query, a_ptr, a_id, pos)
             # one row per RETRIEVAL_SLICE keys of a query
             n_slices = (counts + tee - 1) // tee
             row_base = torch.cumsum(n_slices, 0) - n_slices
@@ -182,17 +166,16 @@ def _run(model, h, r, t, side, known, scoring, cand, batch_size, ks) -> AnswerRa
             qkey_off, qkey_n = qkey_ptr[:-1][row_q], counts[row_q]
             key_off = qkey_off + in_query * tee
             key_n = torch.clamp(qkey_n - in_query * tee, max=tee).to(torch.int32)
-            frow, frel = qid[row_q], (rel[row_q] if rel is not None else torch.full_like(row_q, -1))
+            frow, frel = g.qid[row_q], g.frel[row_q]
             buckets = torch.empty((n_rows, tee), dtype=torch.int32, device=dev)
             for lo, hi in Q.batches(n_rows, batch_size):
-                buckets[lo:hi] = ops.retrieval_count(q, row_q[lo:hi], p, pn, key_off[lo:hi], key_n[lo:hi],
+                buckets[lo:hi] = ops.retrieval_count(g.q, row_q[lo:hi], g.p, g.pn, key_off[lo:hi], key_n[lo:hi],
                                                      qkey_off[lo:hi], qkey_n[lo:hi], key_s, key_id, filt, frow[lo:hi],
                                                      frel[lo:hi], cand, slot)
-            before, position, metrics = ops.retrieval_finish(qkey_ptr, row_base, buckets, n_answers[pos], ks, p.shape[0])
+            before, position, metrics = ops.retrieval_finish(qkey_ptr, row_base, buckets, n_answers[pos], ks, g.p.shape[0])
             a_before[key_ans], a_position[key_ans] = before, position
             if ks is not None:
                 res.hits[pos], res.ndcg[pos], res.ap[pos], res.rr[pos] = metrics
-            del p, pn, q
     res.before, res.position = a_before[answer], a_position[answer]
     res.nan = res.position < 0
     return res

@@ -26,9 +26,7 @@ import torch
 
 from . import _queries as Q
 from . import ops
-from .ranking import KnownTriples, _check_scoring, scoring_groups
-
-SIDES = ("tail", "head")
+from .ranking import KnownTriples
 
 
 @dataclass
@@ -42,18 +40,6 @@ class TopKResult:
     kernel_scores: torch.Tensor
 
 
-def _check_side(side: str) -> str:
-    if side not in SIDES:
-        raise ValueError(f"side must be one of {SIDES} (top-k ranks one side at a time), got {side!r}")
-    return side
-
-
-def _check_k(k) -> int:
-    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= ops.TOPK_MAX:
-        raise ValueError(f"k must be an integer in [1, {ops.TOPK_MAX}], got {k!r}")
-    return k
-
-
 def predict_topk(model, ids: torch.Tensor, r: Optional[torch.Tensor] = None, side: str = "tail", k: int = 10,
                  known: Optional[KnownTriples] = None, scoring: Optional[str] = None,
                  candidates: Optional[torch.Tensor] = None, batch_size: Optional[int] = None,
@@ -62,27 +48,18 @@ def predict_topk(model, ids: torch.Tensor, r: Optional[torch.Tensor] = None, sid
     candidates: optional 1-D tensor of unique entity ids to select among (ids are still entity ids).  batch_size: queries
     per launch (None: as many as the workspace bound allows); splits: candidate splits per launch (0 = automatic).
     Neither changes the result.  The model's mode, parameters and caches are left as they are."""
-    side = _check_side(side)
+    side = Q.check_one_side(side, "top-k ranks one side at a time")
     scoring = scoring if scoring is not None else model.scoring
-    mlp = scoring == "mlp"                               # the pair head (pairmlp.py); ranking.SCORINGS are the embedding scores
+    mlp = scoring == "mlp"                               # the pair head (pairmlp.py); Q.SCORINGS are the embedding scores
     if not mlp:
-        scoring = _check_scoring(scoring)
-    k = _check_k(k)
-    Q.check_ids("ids", ids)
-    if r is None:
-        if scoring not in ("dot", "mlp"):
-            raise ValueError(f"scoring={scoring!r} needs the relations r (only 'dot' can filter without them)")
-    else:
-        Q.check_ids("r", r)
-        if r.numel() != ids.numel():
-            raise ValueError(f"ids and r have different lengths ({ids.numel()}, {r.numel()})")
+        scoring = Q.check_scoring(scoring)
+    k = Q.check_k(k)
+    Q.check_query_lists(ids, r, scoring)
     if candidates is not None:
         Q.check_ids("candidates", candidates)
     Q.check_batch_size(batch_size)
-    if isinstance(splits, bool) or int(splits) != splits or not 0 <= splits <= ops.TOPK_MAX_SPLITS:
-        raise ValueError(f"splits must be an integer in [0, {ops.TOPK_MAX_SPLITS}], got {splits!r}")
-    if scoring == "transr" and getattr(model, "gat_trans_M", None) is None:
-        raise ValueError("scoring='transr' needs a model with gat_trans_M (built with scoring='transr')")
+    Q.check_splits(splits)
+    Q.check_transr_model(model, scoring)
     Q.check_known_entities(known, model)
     head = None
     if mlp:
@@ -101,24 +78,14 @@ def predict_topk(model, ids: torch.Tensor, r: Optional[torch.Tensor] = None, sid
     if mlp:
         out_ids, out_p, out_z = predict_topk_mlp(model, head, ids, r, side, k, filt, cand, batch_size, splits)
         return TopKResult(out_ids, out_p, side, out_z)
-    alpha = 1.0 if side == "tail" else -1.0             # q = P_r[h] + e_r  /  q = P_r[t] - e_r
-    frel_all = Q.filter_relations(r, b, dev)
     out_ids = torch.empty((b, k), dtype=torch.int64, device=dev)
     out_sc = torch.empty((b, k), dtype=torch.float32, device=dev)
     out_s = torch.empty((b, k), dtype=torch.float32, device=dev)
     with torch.no_grad():
-        table = model._table_for_inference().detach()
-        for p, pn, pos in scoring_groups(model, scoring, table, r, b):
-            qid, rel = ids[pos], (r[pos] if r is not None else None)
-            q = ops.rank_queries(p, qid, None if scoring == "dot" else model.relation_embed.weight.detach(), rel, alpha)
-            if cand is not None:                         # the candidate rows, scored with the same bits
-                p = ops.gather_rows(p, cand)
-                pn = ops.rank_sqnorm(p) if pn is not None else None
-            frel = frel_all[pos]
-            for lo, hi in Q.batches(pos.numel(), batch_size):
-                ii, ss, vv = ops.topk_select(q[lo:hi], p, pn, k, filt, qid[lo:hi], frel[lo:hi], cand, splits)
-                out_ids[pos[lo:hi]] = ii
-                out_s[pos[lo:hi]] = ss
-                out_sc[pos[lo:hi]] = vv
-            del p, pn, q
+        for g in Q.query_groups(model, scoring, side, ids, r, cand):
+            for lo, hi in Q.batches(g.pos.numel(), batch_size):
+                ii, ss, vv = ops.topk_select(g.q[lo:hi], g.p, g.pn, k, filt, g.qid[lo:hi], g.frel[lo:hi], cand, splits)
+                out_ids[g.pos[lo:hi]] = ii
+                out_s[g.pos[lo:hi]] = ss
+                out_sc[g.pos[lo:hi]] = vv
     return TopKResult(out_ids, out_sc, side, out_s)

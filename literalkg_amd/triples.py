@@ -24,9 +24,7 @@ import torch
 from . import _queries as Q
 from . import ops
 from .pairmlp import classification_metrics
-from .ranking import SCORINGS
 
-SIDES = ("tail", "head")
 PROJECT: Optional[str] = None      # 'transr' projections: None = the distinct rows when they are fewer than the entities;
 #                                    'distinct' / 'full' force a route (tests run both: the choice changes no bit)
 
@@ -44,39 +42,16 @@ class TripleThresholds:
     correct: torch.Tensor
 
 
-def _lower_is_better(scoring: str) -> bool:
-    return scoring != "dot"
-
-
 def sentinel(scoring: str) -> float:
     """The threshold under which nothing is positive."""
-    return float("-inf") if _lower_is_better(scoring) else float("inf")
+    return float("-inf") if Q.lower_is_better(scoring) else float("inf")
 
 
-def _check_scoring(model, scoring: Optional[str]) -> str:
-    scoring = scoring if scoring is not None else model.scoring
-    if scoring == "mlp":
-        raise ValueError("scoring='mlp' has no triple score: the pair head scores (h, t) pairs -- use score_pairs_mlp / "
-                         "evaluate_mlp_classification")
-    if scoring not in SCORINGS:
-        raise ValueError(f"scoring must be one of {SCORINGS}, got {scoring!r}")
-    if scoring == "transr" and getattr(model, "gat_trans_M", None) is None:
-        raise ValueError("scoring='transr' needs a model with gat_trans_M (built with scoring='transr')")
+def check_scoring(model, scoring: Optional[str]) -> str:
+    scoring = Q.resolve_scoring(model, scoring, "scoring='mlp' has no triple score: the pair head scores (h, t) pairs -- "
+                                "use score_pairs_mlp / evaluate_mlp_classification")
+    Q.check_transr_model(model, scoring)
     return scoring
-
-
-def _check_side(side: str) -> str:
-    if side not in SIDES:
-        raise ValueError(f"side must be one of {SIDES} (a triple is scored from one side at a time), got {side!r}")
-    return side
-
-
-def _check_triples(h, r, t):
-    Q.check_ids("h", h)
-    Q.check_ids("r", r)
-    Q.check_ids("t", t)
-    if not h.numel() == r.numel() == t.numel():
-        raise ValueError(f"h, r, t have different lengths ({h.numel()}, {r.numel()}, {t.numel()})")
 
 
 def _check_labels(labels, n: int) -> torch.Tensor:
@@ -92,25 +67,17 @@ def _groups(model, scoring: str, table: torch.Tensor, qid, cid, r, by_relation: 
     over P_r of the distinct rows its triples touch -- or of the whole table when those are not fewer -- a projected row
     being the same bits either way (the tall GEMM's row does not depend on the rows projected with it).  Otherwise the
     groups share the table: one per relation present with by_relation (the counts), else a single one."""
-    c = table.shape[1]
-    n_ent = table.shape[0]
-    if scoring == "transe" and c != model.relation_dim:
-        raise ValueError(f"scoring='transe' needs the table width ({c}) to equal relation_dim ({model.relation_dim})")
-    e = None if scoring == "dot" else model.relation_embed.weight.detach()
-    if scoring == "transr":
-        w = model.gat_trans_M.detach()
-        if w.shape[1] != c:
-            raise ValueError(f"gat_trans_M is {tuple(w.shape)} for a table of width {c}")
+    Q.check_table_shape(model, scoring, table)
+    e = Q.relation_rows(model, scoring)
+    pn = ops.rank_sqnorm(table) if scoring == "transe" else None
     if scoring != "transr" and not by_relation:
-        pn = ops.rank_sqnorm(table) if scoring == "transe" else None
         yield table, pn, e, qid, cid, r, None, None
         return
     perm, seg = ops.group_by_key(r, model.n_relations)
     perm, seg = perm.long(), seg.tolist()
     if scoring == "transr":
+        w = model.gat_trans_M.detach()
         rowmax = ops.row_absmax(table)
-    else:
-        pn = ops.rank_sqnorm(table) if scoring == "transe" else None
     for rr in range(model.n_relations):
         if seg[rr + 1] == seg[rr]:
             continue
@@ -119,16 +86,9 @@ def _groups(model, scoring: str, table: torch.Tensor, qid, cid, r, by_relation: 
         if scoring != "transr":
             yield table, pn, e, qi, ci, rel, pos, rr
             continue
-        m = pos.numel()
-        full = PROJECT == "full"
-        if not full:
-            uniq, inv = torch.unique(torch.cat((qi, ci)), return_inverse=True)
-            full = PROJECT is None and uniq.numel() >= n_ent
-        if full:
-            p = ops.gemm_tall([table], [[w[rr]]], trans_b=False, rowmax=rowmax)
-        else:
-            p = ops.gemm_tall([ops.gather_rows(table, uniq)], [[w[rr]]], trans_b=False, rowmax=rowmax[uniq])
-            qi, ci = inv[:m], inv[m:]
+        rows, rm, qi, ci = Q.rows_to_project(table, rowmax, qi, ci, PROJECT)
+        p = ops.gemm_tall([rows], [[w[rr]]], trans_b=False, rowmax=rm)
+        del rows, rm
         yield p, ops.rank_sqnorm(p), e, qi, ci, rel, pos, rr
         del p
 
@@ -138,7 +98,7 @@ def _scores(model, scoring, side, h, r, t, batch_size, kernel_scores=False, labe
     (ids already there).  thr: one threshold per relation (a list of floats) for the counts against labels."""
     dev = h.device
     qid, cid = (h, t) if side == "tail" else (t, h)
-    alpha = 1.0 if side == "tail" else -1.0              # q = P_r[h] + e_r  /  q = P_r[t] - e_r
+    alpha = Q.side_alpha(side)
     n = h.numel()
     out = torch.empty(n, dtype=torch.float32, device=dev)
     counts = torch.zeros((model.n_relations, 5), dtype=torch.int64, device=dev) if labels is not None else None
@@ -150,7 +110,7 @@ def _scores(model, scoring, side, h, r, t, batch_size, kernel_scores=False, labe
             lab = None if labels is None else (labels if pos is None else labels[pos])
             for lo, hi in Q.batches(m, batch_size):
                 ops.triple_scores(p, qi[lo:hi], ci[lo:hi], pn, e, rel[lo:hi], alpha, reported=not kernel_scores,
-                                  higher_is_positive=not _lower_is_better(scoring),
+                                  higher_is_positive=not Q.lower_is_better(scoring),
                                   labels=None if lab is None else lab[lo:hi], thr=None if lab is None else thr[rr],
                                   out=sc[lo:hi], counts=None if lab is None else counts[rr])
             if pos is not None:
@@ -164,9 +124,9 @@ def score_triples(model, h: torch.Tensor, r: torch.Tensor, t: torch.Tensor, scor
     predict_topk reports for that (query, candidate) on that side (see the module docstring): TopKResult.scores, or
     .kernel_scores with kernel_scores=True.  batch_size: triples per launch (None: all of a group); it changes nothing.
     The model's mode, parameters and caches are left as they are."""
-    scoring = _check_scoring(model, scoring)
-    side = _check_side(side)
-    _check_triples(h, r, t)
+    scoring = check_scoring(model, scoring)
+    side = Q.check_one_side(side, "a triple is scored from one side at a time")
+    Q.check_triple_lists(h, r, t)
     Q.check_batch_size(batch_size)
     dev = model.entity_embed.weight.device
     if h.numel() == 0:
@@ -189,13 +149,13 @@ def fit_triple_thresholds(model, h: torch.Tensor, r: torch.Tensor, t: torch.Tens
     ``global_threshold``, the same fit over all triples pooled, which per_relation=False puts everywhere.  labels: a
     uint8 or bool tensor of 0 / 1.  NaN scores are classified wrongly whatever the threshold.  Runs in eval mode and
     restores the model's previous mode."""
-    scoring = _check_scoring(model, scoring)
-    _check_triples(h, r, t)
+    scoring = check_scoring(model, scoring)
+    Q.check_triple_lists(h, r, t)
     labels = _check_labels(labels, h.numel())
     Q.check_batch_size(batch_size)
     dev = model.entity_embed.weight.device
     n_rel = model.n_relations
-    lower = _lower_is_better(scoring)
+    lower = Q.lower_is_better(scoring)
     if h.numel() == 0:
         s_ = sentinel(scoring)
         zeros = torch.zeros(n_rel, dtype=torch.int64, device=dev)
@@ -219,7 +179,7 @@ def fit_triple_thresholds(model, h: torch.Tensor, r: torch.Tensor, t: torch.Tens
         return TripleThresholds(thr, float(thr_g.item()), scoring, n, correct)
 
 
-def _threshold_list(model, thresholds, scoring: str):
+def threshold_list(model, thresholds, scoring: str):
     """One Python float per relation from a TripleThresholds, a float or a float32[n_relations] tensor."""
     n_rel = model.n_relations
     if isinstance(thresholds, TripleThresholds):
@@ -271,11 +231,11 @@ def evaluate_triple_classification(model, h: torch.Tensor, r: torch.Tensor, t: t
     The scores are those of score_triples (tail side), computed once for the counts (taken in the scoring kernel, one
     float32 compare each) and the curve.  labels: a uint8 or bool tensor of 0 / 1.  batch_size changes nothing.  Runs in
     eval mode and restores the model's previous mode."""
-    scoring = _check_scoring(model, scoring)
-    _check_triples(h, r, t)
+    scoring = check_scoring(model, scoring)
+    Q.check_triple_lists(h, r, t)
     labels = _check_labels(labels, h.numel())
     Q.check_batch_size(batch_size)
-    thr = _threshold_list(model, thresholds, scoring)
+    thr = threshold_list(model, thresholds, scoring)
     n_rel = model.n_relations
     if h.numel() == 0:
         return triple_metrics(torch.zeros((n_rel, 5), dtype=torch.int64), 0, 0)
@@ -284,6 +244,6 @@ def evaluate_triple_classification(model, h: torch.Tensor, r: torch.Tensor, t: t
         (h, t), r, _ = Q.ids_to_device(model, dev, (h, t), r)
         lab = labels.to(dev)
         scores, counts = _scores(model, scoring, "tail", h, r, t, batch_size, labels=lab, thr=thr)
-        curve = ops.binary_curve(-scores if _lower_is_better(scoring) else scores, lab)
+        curve = ops.binary_curve(-scores if Q.lower_is_better(scoring) else scores, lab)
         n_pos = int((lab != 0).sum())
     return triple_metrics(counts, n_pos, h.numel() - n_pos, curve)

@@ -144,7 +144,7 @@ def test_argument_errors_come_before_any_device_work():
             call(ids, r, 1.0, known=SimpleNamespace(n_entities=41, device=torch.device("cpu")))
         with pytest.raises(ValueError, match="known triples live on"):
             call(ids, r, 1.0, known=SimpleNamespace(n_entities=40, device=torch.device("meta")))
-        # the thresholds, through triples._threshold_list
+        # the thresholds, through triples.threshold_list
         with pytest.raises(ValueError, match="NaN"):
             call(ids, r, NAN)
         with pytest.raises(ValueError, match="NaN"):
