@@ -44,6 +44,10 @@ def main():
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--batch-groups", type=int, default=683)
     ap.add_argument("--lr", type=float, default=1e-4)
+    ap.add_argument("--objective", choices=("sampled", "one_vs_all"), default="sampled",
+                    help="sampled: the reference's loss over pre_training_neg_rate sampled negatives (mode='pre_training'); "
+                         "one_vs_all: cross-entropy of the true tail against the softmax over every entity "
+                         "(mode='one_vs_all'; the sampled negatives of the batch are not used)")
     a = ap.parse_args()
     device = torch.device("cuda:0")
     args = SimpleNamespace(use_pretrain=0, device=device, embed_dim=a.dim, relation_dim=a.dim, scale_gat_dim=None,
@@ -67,7 +71,10 @@ def main():
             bh, br, bp, bn = (torch.from_numpy(x).to(device)
                               for x in make_batch(a.entities, a.batch_groups, 3, seed=epoch * 10_000 + it))
             optimizer.zero_grad()
-            loss = model(bh, br, bp, bn, device=device, mode="pre_training")
+            if a.objective == "one_vs_all":
+                loss = model(bh[::3], br[::3], bp[::3], device=device, mode="one_vs_all")   # one triple per group
+            else:
+                loss = model(bh, br, bp, bn, device=device, mode="pre_training")
             if np.isnan(loss.cpu().detach().numpy()):
                 sys.exit("ERROR (Pre-training): loss is nan")
             loss.backward()

@@ -894,6 +894,40 @@ int lkg_retrieval_finish(int64_t n_q, const int64_t *qkey_ptr, const int64_t *ro
                          const double *icum, int64_t *before, int64_t *position, int64_t *hits, double *ndcg, double *ap,
                          double *rr, void *stream);
 
+/* 1-vs-all training loss (lkg_softmax.hip; literalkg_amd/one_vs_all.py): cross-entropy of the truth against the softmax
+ * over ALL candidates.  Queries, candidates and the kernel score s(i, c) as for lkg_rank_* above, bit for bit.  The logit is
+ *     z(i, c) = -scale * beta * s(i, c)      (pn given: beta = 1, minus the squared distance up to the row constant
+ *                                              ||q_i||^2, which cancels;  pn NULL: beta = 1/2, z = scale q_i . p_c)
+ * one rounded product of the score; scale > 0, finite.  loss_i = logsumexp_c z(i, c) - z(i, truth[i]).
+ *
+ * lkg_softmax_all_splits     : as lkg_topk_splits.  The loss's last bits may depend on S; for a given S every output is
+ *     the same from run to run (no float atomics anywhere).
+ * lkg_softmax_all_partial_f32: per split j and query i the running pair ws_m[j * n_q + i] = the largest logit of the
+ *     split's candidates and ws_l[j * n_q + i] = sum exp(z - that maximum) (splits = lkg_softmax_all_splits(n_q, n_cand,
+ *     splits)).  The n_q x n_cand logits are never stored.
+ * lkg_softmax_all_finish_f32 : the truth's logit (lkg_rank_prepare_f32's pair routine: the bits it has inside a tile), the
+ *     S partials merged in split order in float64: lse[i] = fl32(M + log L), loss[i] = fl32((M + log L) - z_t), and
+ *     (lse_lo nullable) lse_lo[i] = fl32((M + log L) - lse[i]), what lse's rounding dropped.  A NaN in query row i gives
+ *     lse[i] = loss[i] = NaN and touches no other row.  truth is clamped into [0, n_cand).
+ * lkg_softmax_all_weights_f32: the backward's recompute for a chunk of n_cand candidates that starts at candidate c_base
+ *     of the table the forward pass ran over (p and pn point AT the chunk; truth, lse, lse_lo and g are per query):
+ *         v[i * ldv + c] = scale * beta * g[i] * (exp(z(i, c_base + c) - lse[i] - lse_lo[i]) - [c_base + c == truth[i]]),
+ *     ldv >= n_cand, lse_lo NULL = 0 (every weight of row i then carries lse[i]'s rounding, |lse| u / 2, relative).
+ *     With it  dQ = 2 V P  and  dP = 2 V^T Q - 2 diag(colsum V) P  (the second term only with pn).
+ * n_q == 0 launches nothing; addressing is 64-bit.                                                                    */
+#define LKG_SOFTMAX_MAX_SPLITS 64
+int32_t lkg_softmax_all_splits(int64_t n_q, int64_t n_cand, int32_t requested);
+int lkg_softmax_all_partial_f32(int64_t n_q, int64_t n_cand, int32_t k, const float *q, int64_t ldq, const float *p,
+                                int64_t ldp, const float *pn, float scale, int32_t splits, float *ws_m, float *ws_l,
+                                void *stream);
+int lkg_softmax_all_finish_f32(int64_t n_q, int64_t n_cand, int32_t k, const float *q, int64_t ldq, const float *p,
+                               int64_t ldp, const float *pn, const int64_t *truth, float scale, int32_t splits,
+                               const float *ws_m, const float *ws_l, float *lse, float *lse_lo, float *loss,
+                               void *stream);
+int lkg_softmax_all_weights_f32(int64_t n_q, int64_t n_cand, int32_t k, const float *q, int64_t ldq, const float *p,
+                                int64_t ldp, const float *pn, int64_t c_base, const int64_t *truth, const float *lse,
+                                const float *lse_lo, const float *g, float scale, float *v, int64_t ldv, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -124,6 +124,10 @@ PROTOTYPES = {
                                   vp, vp, vp, vp],
     "lkg_retrieval_count_f32": [i64, i64, i32, vp, i64, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp],
     "lkg_retrieval_finish": [i64, vp, vp, vp, vp, i32, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+    "lkg_softmax_all_splits": [i64, i64, i32],
+    "lkg_softmax_all_partial_f32": [i64, i64, i32, vp, i64, vp, i64, vp, f32, i32, vp, vp, vp],
+    "lkg_softmax_all_finish_f32": [i64, i64, i32, vp, i64, vp, i64, vp, vp, f32, i32, vp, vp, vp, vp, vp, vp],
+    "lkg_softmax_all_weights_f32": [i64, i64, i32, vp, i64, vp, i64, vp, i64, vp, vp, vp, vp, f32, vp, i64, vp],
 }
 _RESTYPE = {"lkg_last_error": C.c_char_p, "lkg_csr_build_device_workspace": C.c_int64,
             "lkg_gemm_tall_workspace": C.c_int64, "lkg_gemm_workspace": C.c_int64,

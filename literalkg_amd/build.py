@@ -16,7 +16,7 @@ OBJ = os.path.join(HERE, "lib", "obj")
 SOURCES = ["lkg_graph_host.cpp", "lkg_spmm.hip", "lkg_attention.hip", "lkg_score.hip", "lkg_rowwise.hip",
            "lkg_gemm.hip", "lkg_batch.hip", "lkg_csr_device.hip", "lkg_gemm_tall.hip", "lkg_gemm_wgrad.hip", "lkg_layer.hip",
            "lkg_rank.hip", "lkg_topk.hip", "lkg_pairmlp.hip", "lkg_triples.hip", "lkg_relations.hip",
-           "lkg_accept.hip", "lkg_retrieval.hip"]
+           "lkg_accept.hip", "lkg_retrieval.hip", "lkg_softmax.hip"]
 FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17"]
 
 

@@ -5,8 +5,9 @@
 // Arithmetic: the exact f32 MFMA v_mfma_f32_16x16x4_f32 -- every output element is a k-ordered chain of f32 fmas (one
 // rounding per product, no wider accumulator), independent of its position in the 16 x 16 tile.  So a (query, candidate)
 // pair scored in ANY tile position, with the same operands fed in the same k order, gives the same bits: the truth's
-// score (the threshold) and the scores of filtered candidates come from rank_pair_scores below, which feeds the same
-// lane -> k map as the counting kernel.  A candidate whose row is bit-identical to the truth's ties exactly.
+// score (the threshold) and the scores of filtered candidates come from rank_pair_scores (lkg_rank_common.h), which
+// feeds the same lane -> k map as the counting kernel.  A candidate whose row is bit-identical to the truth's ties
+// exactly.
 //
 // k order (both kernels, load4 / mfma_chunk of lkg_rank_common.h, shared with lkg_topk.hip): k is taken in chunks of 16;
 // lane l holds elements 4(l>>4) .. 4(l>>4)+3 of the chunk for row l & 15; MFMA j of the chunk feeds element j.
@@ -112,22 +113,6 @@ __global__ __launch_bounds__(RK_THREADS) void rank_count_kernel(long n_q, long n
         if (cnt[0][tid]) atomicAdd(better + q0 + tid, cnt[0][tid]);
         if (cnt[1][tid]) atomicAdd(equal + q0 + tid, cnt[1][tid]);
     }
-}
-
-// "Score these pairs with the counting arithmetic": lanes 0..15 return s(q, p[cand of lane]) -- every row of the A
-// operand is q, column r of B is the candidate of lane r (lanes >= 16 feed the same candidates: the B map is r = l & 15).
-template <bool VEC>
-__device__ __forceinline__ float rank_pair_scores(const float *__restrict__ qrow, const float *__restrict__ p, long ldp,
-                                                  const float *__restrict__ pn, long cand, int k) {
-    const int s = (threadIdx.x & 63) >> 4;
-    const float *prow = p + cand * ldp;
-    f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
-    for (int k0 = 0; k0 < k; k0 += 16) {
-        const float4 a = load4<VEC>(qrow, k0 + 4 * s, k);
-        const float4 b = load4<VEC>(prow, k0 + 4 * s, k);
-        mfma_chunk(acc, a, b);
-    }
-    return rank_score(acc[0], pn, cand);     // C[4 s + 0][r]: the same value on every s
 }
 
 // One wave per query: thr = the truth's score; better / equal = minus the filtered candidates (other than the truth)

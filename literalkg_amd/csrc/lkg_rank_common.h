@@ -33,6 +33,23 @@ __device__ __forceinline__ float rank_score(float dot, const float *__restrict__
     return __builtin_fmaf(-2.f, dot, pn ? pn[c] : 0.f);
 }
 
+// "Score these pairs with the counting arithmetic": lanes 0..15 return s(q, p[cand of lane]) -- every row of the A
+// operand is q, column r of B is the candidate of lane r (lanes >= 16 feed the same candidates: the B map is r = l & 15).
+// (lkg_rank.hip's prepare kernel and lkg_softmax.hip's finish kernel score the truth with it.)
+template <bool VEC>
+__device__ __forceinline__ float rank_pair_scores(const float *__restrict__ qrow, const float *__restrict__ p, long ldp,
+                                                  const float *__restrict__ pn, long cand, int k) {
+    const int s = (threadIdx.x & 63) >> 4;
+    const float *prow = p + cand * ldp;
+    f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int k0 = 0; k0 < k; k0 += 16) {
+        const float4 a = load4<VEC>(qrow, k0 + 4 * s, k);
+        const float4 b = load4<VEC>(prow, k0 + 4 * s, k);
+        mfma_chunk(acc, a, b);
+    }
+    return rank_score(acc[0], pn, cand);     // C[4 s + 0][r]: the same value on every s
+}
+
 // One wave's 64 x 64 block of dot products: acc[i][j][v] = q_(16 i + 4 s + v) . p_(16 j + r) for lane (r, s) = (l & 15,
 // l >> 4), qrow[i] / prow[i] the rows that lane feeds (16 i + r).  The next k-chunk is in flight while this one runs on
 // the matrix pipe.  (rank_count_kernel keeps the same loop inline: through this helper its register allocation, though

@@ -1,0 +1,297 @@
+// 1-vs-all training loss (literalkg_amd/one_vs_all.py): for every query q_i the cross-entropy of the truth t_i against the
+// softmax over ALL n_c candidates,  loss_i = logsumexp_c z_ic - z_i,t_i,  with the logit  z_ic = -scale * beta * s_ic  of the
+// kernel score  s_ic = pn_c - 2 q_i . p_c  (beta = 1;  dot scoring: pn = NULL, s = -2 q.p, beta = 1/2, z = scale q.p).
+// ||q_i||^2 is common to a row and cancels in the softmax as it cancels in ranking.  The B x N logits are never stored by
+// the forward pass; the backward pass recomputes them chunk by chunk into the weights V.
+//
+// Arithmetic: exactly that of rank_count_kernel (lkg_rank_common.h: the exact f32 MFMA, the same lane -> k map, zero
+// padding past k, the same final fma), then ONE rounded product nsb * s with nsb = -scale * beta.  The truth's logit comes
+// from rank_pair_scores and the same product, so it has the bits it has inside a tile: with one candidate the loss is
+// exactly 0.  Floating-point contraction is off in this file: z - m must subtract the ROUNDED z the maximum was taken of.
+//
+// Forward: a 256-thread workgroup owns 64 query rows and a contiguous range of 256-candidate tiles (split `split` of S, as
+// lkg_topk.hip).  Every wave carries, per row, the running pair (m, l) of its own 64 columns of each tile: m the largest
+// logit so far, l = sum exp(z - m), rescaled when m moves.  Per tile the reductions run in registers (the lane's 4
+// columns of a row) and across the 16 lanes of a row (group_max / group_sum); the 4 waves meet in LDS once, after the last
+// tile (a per-tile meeting would cost two barriers per tile and change nothing but the association).  The workgroup's (m, l)
+// goes to workspace [S][B]; softmax_finish_kernel merges the S partials of a row in split order in float64.  No float
+// atomics: for a given S every bit is the same from run to run.
+#include "lkg_rank_common.h"
+
+#pragma clang fp contract(off)
+
+namespace {
+
+constexpr int SM_THREADS = 256;
+constexpr int SM_ROWS = 64;           // queries per workgroup
+constexpr int SM_COLS = 256;          // candidates per tile (64 per wave)
+constexpr int SM_MAX_SPLITS = LKG_SOFTMAX_MAX_SPLITS;
+
+// exp(z - m) must not see inf - inf: a pair that has met no candidate yet is (-inf, 0) and takes 0 as its reference
+__device__ __forceinline__ float safe_ref(float m) { return m == -__builtin_inff() ? 0.f : m; }
+
+template <bool VEC>
+__global__ __launch_bounds__(SM_THREADS) void softmax_partial_kernel(long n_q, long n_c, int k, const float *__restrict__ q,
+                                                                     long ldq, const float *__restrict__ p, long ldp,
+                                                                     const float *__restrict__ pn, float nsb, int splits,
+                                                                     long tiles_q, long tiles_c, float *__restrict__ ws_m,
+                                                                     float *__restrict__ ws_l) {
+    __shared__ float sm_m[4][SM_ROWS], sm_l[4][SM_ROWS];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int r = lane & 15, s = lane >> 4;
+    const long bid = blockIdx.x;
+    const long q0 = (bid % tiles_q) * SM_ROWS;
+    const int split = (int)(bid / tiles_q);
+    const long t_lo = split * tiles_c / splits, t_hi = (split + 1) * tiles_c / splits;
+    const float *qrow[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) qrow[i] = q + min(q0 + 16 * i + r, n_q - 1) * ldq;    // rows past the end: never written
+    float m[4][4], l[4][4];           // [i][v]: query row 16 i + 4 s + v, the same on the 16 lanes of the row
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+            m[i][v] = -__builtin_inff();
+            l[i][v] = 0.f;
+        }
+
+    for (long t = t_lo; t < t_hi; ++t) {
+        const long c0 = t * SM_COLS + wave * 64;
+        const float *prow[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) prow[i] = p + min(c0 + 16 * i + r, n_c - 1) * ldp;
+        f32x4 acc[4][4];
+        rank_tile_dots<VEC>(acc, qrow, prow, k, s);
+        // acc[i][j][v]: query row 16 i + 4 s + v, candidate c0 + 16 j + r
+        float pnv[4];
+        bool ok[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const long c = c0 + 16 * j + r;
+            ok[j] = c < n_c;
+            pnv[j] = (pn && ok[j]) ? pn[c] : 0.f;
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int v = 0; v < 4; ++v) {
+                float z[4], mt = -__builtin_inff();
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {       // a column past the end is -inf: no maximum, exp = 0
+                    z[j] = ok[j] ? nsb * __builtin_fmaf(-2.f, acc[i][j][v], pnv[j]) : -__builtin_inff();
+                    mt = fmaxf(mt, z[j]);           // (a NaN logit is skipped here and poisons l below)
+                }
+                mt = group_max<16>(mt);
+                const float mn = fmaxf(m[i][v], mt), ref = safe_ref(mn);
+                float sum = 0.f;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) sum += expf(z[j] - ref);
+                sum = group_sum<16>(sum);
+                l[i][v] = l[i][v] * expf(m[i][v] - ref) + sum;
+                m[i][v] = mn;
+            }
+    }
+    if (r == 0) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int v = 0; v < 4; ++v) {
+                sm_m[wave][16 * i + 4 * s + v] = m[i][v];
+                sm_l[wave][16 * i + 4 * s + v] = l[i][v];
+            }
+    }
+    __syncthreads();
+    if (tid < SM_ROWS && q0 + tid < n_q) {
+        float mw = sm_m[0][tid];
+#pragma unroll
+        for (int w = 1; w < 4; ++w) mw = fmaxf(mw, sm_m[w][tid]);
+        const float ref = safe_ref(mw);
+        float lw = 0.f;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) lw += sm_l[w][tid] * expf(sm_m[w][tid] - ref);
+        const long o = (long)split * n_q + q0 + tid;
+        ws_m[o] = mw;
+        ws_l[o] = lw;
+    }
+}
+
+// One wave per query: the truth's logit with the pair routine of the ranking kernels, the S partials merged in split
+// order in float64, lse and loss rounded once each; lse_lo (nullable) is the remainder of lse's rounding, with which the
+// backward's exp(z - lse) does not carry |lse| u / 2 into every weight of the row.
+template <bool VEC>
+__global__ __launch_bounds__(SM_THREADS) void softmax_finish_kernel(long n_q, long n_c, int k, const float *__restrict__ q,
+                                                                    long ldq, const float *__restrict__ p, long ldp,
+                                                                    const float *__restrict__ pn,
+                                                                    const long *__restrict__ truth, float nsb, int splits,
+                                                                    const float *__restrict__ ws_m,
+                                                                    const float *__restrict__ ws_l, float *__restrict__ lse,
+                                                                    float *__restrict__ lse_lo, float *__restrict__ loss) {
+    const long i = (long)blockIdx.x * (SM_THREADS / 64) + (threadIdx.x >> 6);
+    if (i >= n_q) return;                           // (a whole wave leaves)
+    const int lane = threadIdx.x & 63;
+    const long tr = min(max(truth[i], 0L), n_c - 1);
+    const float st = __shfl(rank_pair_scores<VEC>(q + i * ldq, p, ldp, pn, tr, k), 0);
+    const float zt = nsb * st;
+    double mx = -__builtin_inf();
+    for (int j = 0; j < splits; ++j) mx = fmax(mx, (double)ws_m[(long)j * n_q + i]);
+    const double ref = mx == -__builtin_inf() ? 0.0 : mx;
+    double sum = 0.0;
+    for (int j = 0; j < splits; ++j) sum += (double)ws_l[(long)j * n_q + i] * exp((double)ws_m[(long)j * n_q + i] - ref);
+    const double lsed = mx + log(sum);
+    if (lane == 0) {
+        const float hi = (float)lsed;
+        lse[i] = hi;
+        if (lse_lo) lse_lo[i] = (float)(lsed - (double)hi);     // what the rounding of lse dropped (NaN for a non-finite lse)
+        loss[i] = (float)(lsed - (double)zt);
+    }
+}
+
+// The backward's recompute: V[i, c] = sb g_i (exp((z_ic - lse_i) - lse_lo_i) - [c_base + c == t_i]) for the n_c candidates
+// of a chunk that starts at candidate c_base of the table (p, pn point at the chunk).  One 64 x 256 tile per workgroup, stored
+// straight from the accumulator layout: the 16 lanes of a row write 64 consecutive bytes.
+template <bool VEC>
+__global__ __launch_bounds__(SM_THREADS) void softmax_weights_kernel(long n_q, long n_c, int k, const float *__restrict__ q,
+                                                                     long ldq, const float *__restrict__ p, long ldp,
+                                                                     const float *__restrict__ pn, long c_base,
+                                                                     const long *__restrict__ truth,
+                                                                     const float *__restrict__ lse,
+                                                                     const float *__restrict__ lse_lo,
+                                                                     const float *__restrict__ g, float nsb, float sb,
+                                                                     float *__restrict__ vout, long ldv, long tiles_q) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int r = lane & 15, s = lane >> 4;
+    const long bid = blockIdx.x;
+    const long q0 = (bid % tiles_q) * SM_ROWS, c0 = (bid / tiles_q) * SM_COLS + wave * 64;
+    const float *qrow[4], *prow[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        qrow[i] = q + min(q0 + 16 * i + r, n_q - 1) * ldq;        // rows and columns past the end are clamped, never stored
+        prow[i] = p + min(c0 + 16 * i + r, n_c - 1) * ldp;
+    }
+    f32x4 acc[4][4];
+    rank_tile_dots<VEC>(acc, qrow, prow, k, s);
+    float pnv[4];
+    long cid[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        cid[j] = c0 + 16 * j + r;
+        pnv[j] = (pn && cid[j] < n_c) ? pn[cid[j]] : 0.f;
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+            const long row = q0 + 16 * i + 4 * s + v;
+            const long rr = min(row, n_q - 1);
+            const float ls = lse[rr], lo = lse_lo ? lse_lo[rr] : 0.f, coef = sb * g[rr];
+            const long tl = truth[rr] - c_base;
+            float *out = vout + rr * ldv;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float z = nsb * __builtin_fmaf(-2.f, acc[i][j][v], pnv[j]);
+                // exp(z - lse) with lse = ls + lo: d = fl(z - ls), its rounding error recovered exactly (TwoSum) and, with
+                // lo, applied to first order -- neither subtraction's rounding (up to |z - lse| u each) reaches the weight
+                const float d = z - ls, zp = d + ls, e = (z - zp) + (-ls - (d - zp));
+                const float w = expf(d) * (1.f + (e - lo)) - (cid[j] == tl ? 1.f : 0.f);
+                if (row < n_q && cid[j] < n_c) out[cid[j]] = coef * w;
+            }
+        }
+}
+
+bool vec_ok(const void *a, long lda, const void *b, long ldb) {
+    return lkg_aligned16(a) && lkg_aligned16(b) && lda % 4 == 0 && ldb % 4 == 0;
+}
+
+bool scale_ok(float scale) { return scale > 0.f && scale < __builtin_inff(); }
+
+// -scale * beta: beta = 1 with squared norms (minus the squared distance), 1/2 without (the dot product); exact
+float neg_scale_beta(float scale, const float *pn) { return pn ? -scale : -0.5f * scale; }
+
+}  // namespace
+
+extern "C" int32_t lkg_softmax_all_splits(int64_t n_q, int64_t n_cand, int32_t requested) {
+    if (n_q <= 0 || n_cand <= 0 || requested < 0 || requested > SM_MAX_SPLITS) return 0;
+    const long tiles_q = (n_q + SM_ROWS - 1) / SM_ROWS, tiles_c = (n_cand + SM_COLS - 1) / SM_COLS;
+    long s_ = requested > 0 ? requested : (2 * 256 + tiles_q - 1) / tiles_q;   // auto: >= 2 workgroups per CU
+    s_ = s_ < SM_MAX_SPLITS ? s_ : SM_MAX_SPLITS;
+    s_ = s_ < tiles_c ? s_ : tiles_c;
+    return (int32_t)(s_ > 1 ? s_ : 1);
+}
+
+extern "C" int lkg_softmax_all_partial_f32(int64_t n_q, int64_t n_cand, int32_t k, const float *q, int64_t ldq,
+                                           const float *p, int64_t ldp, const float *pn, float scale, int32_t splits,
+                                           float *ws_m, float *ws_l, void *stream) {
+    LKG_REQUIRE(n_q >= 0 && n_cand > 0 && n_cand < INT32_MAX && k > 0 && ldq >= k && ldp >= k,
+                "lkg_softmax_all_partial_f32: bad sizes");
+    LKG_REQUIRE(scale_ok(scale), "lkg_softmax_all_partial_f32: scale must be positive and finite");
+    if (n_q == 0) return LKG_OK;
+    LKG_REQUIRE(splits >= 1 && splits == lkg_softmax_all_splits(n_q, n_cand, splits),
+                "lkg_softmax_all_partial_f32: splits must come from lkg_softmax_all_splits");
+    LKG_REQUIRE(q && p && ws_m && ws_l, "lkg_softmax_all_partial_f32: null pointer");
+    const long tiles_q = (n_q + SM_ROWS - 1) / SM_ROWS, tiles_c = (n_cand + SM_COLS - 1) / SM_COLS;
+    LKG_REQUIRE(tiles_q * splits < INT32_MAX, "lkg_softmax_all_partial_f32: too many workgroups (split the queries)");
+    const dim3 grid((unsigned)(tiles_q * splits)), block(SM_THREADS);
+    const float nsb = neg_scale_beta(scale, pn);
+    if (vec_ok(q, ldq, p, ldp))
+        hipLaunchKernelGGL(softmax_partial_kernel<true>, grid, block, 0, (hipStream_t)stream, (long)n_q, (long)n_cand, k,
+                           q, (long)ldq, p, (long)ldp, pn, nsb, splits, tiles_q, tiles_c, ws_m, ws_l);
+    else
+        hipLaunchKernelGGL(softmax_partial_kernel<false>, grid, block, 0, (hipStream_t)stream, (long)n_q, (long)n_cand, k,
+                           q, (long)ldq, p, (long)ldp, pn, nsb, splits, tiles_q, tiles_c, ws_m, ws_l);
+    LKG_CHECK_LAUNCH("lkg_softmax_all_partial_f32");
+    return LKG_OK;
+}
+
+extern "C" int lkg_softmax_all_finish_f32(int64_t n_q, int64_t n_cand, int32_t k, const float *q, int64_t ldq,
+                                          const float *p, int64_t ldp, const float *pn, const int64_t *truth, float scale,
+                                          int32_t splits, const float *ws_m, const float *ws_l, float *lse, float *lse_lo,
+                                          float *loss, void *stream) {
+    LKG_REQUIRE(n_q >= 0 && n_cand > 0 && n_cand < INT32_MAX && k > 0 && ldq >= k && ldp >= k,
+                "lkg_softmax_all_finish_f32: bad sizes");
+    LKG_REQUIRE(scale_ok(scale), "lkg_softmax_all_finish_f32: scale must be positive and finite");
+    LKG_REQUIRE(splits >= 1 && splits <= SM_MAX_SPLITS, "lkg_softmax_all_finish_f32: splits must lie in [1, %d]",
+                SM_MAX_SPLITS);
+    if (n_q == 0) return LKG_OK;
+    LKG_REQUIRE(q && p && truth && ws_m && ws_l && lse && loss, "lkg_softmax_all_finish_f32: null pointer");
+    const dim3 grid((unsigned)((n_q + 3) / 4)), block(SM_THREADS);
+    const float nsb = neg_scale_beta(scale, pn);
+    if (vec_ok(q, ldq, p, ldp))
+        hipLaunchKernelGGL(softmax_finish_kernel<true>, grid, block, 0, (hipStream_t)stream, (long)n_q, (long)n_cand, k, q,
+                           (long)ldq, p, (long)ldp, pn, (const long *)truth, nsb, splits, ws_m, ws_l, lse, lse_lo, loss);
+    else
+        hipLaunchKernelGGL(softmax_finish_kernel<false>, grid, block, 0, (hipStream_t)stream, (long)n_q, (long)n_cand, k,
+                           q, (long)ldq, p, (long)ldp, pn, (const long *)truth, nsb, splits, ws_m, ws_l, lse, lse_lo, loss);
+    LKG_CHECK_LAUNCH("lkg_softmax_all_finish_f32");
+    return LKG_OK;
+}
+
+extern "C" int lkg_softmax_all_weights_f32(int64_t n_q, int64_t n_cand, int32_t k, const float *q, int64_t ldq,
+                                           const float *p, int64_t ldp, const float *pn, int64_t c_base,
+                                           const int64_t *truth, const float *lse, const float *lse_lo, const float *g,
+                                           float scale, float *v, int64_t ldv, void *stream) {
+    LKG_REQUIRE(n_q >= 0 && n_cand >= 0 && n_cand < INT32_MAX && k > 0 && ldq >= k && ldp >= k && ldv >= n_cand &&
+                    c_base >= 0,
+                "lkg_softmax_all_weights_f32: bad sizes");
+    LKG_REQUIRE(scale_ok(scale), "lkg_softmax_all_weights_f32: scale must be positive and finite");
+    if (n_q == 0 || n_cand == 0) return LKG_OK;
+    LKG_REQUIRE(q && p && truth && lse && g && v, "lkg_softmax_all_weights_f32: null pointer");
+    const long tiles_q = (n_q + SM_ROWS - 1) / SM_ROWS, tiles_c = (n_cand + SM_COLS - 1) / SM_COLS;
+    LKG_REQUIRE(tiles_q * tiles_c < INT32_MAX, "lkg_softmax_all_weights_f32: too many tiles (use smaller chunks)");
+    const dim3 grid((unsigned)(tiles_q * tiles_c)), block(SM_THREADS);
+    const float nsb = neg_scale_beta(scale, pn);
+    if (vec_ok(q, ldq, p, ldp))
+        hipLaunchKernelGGL(softmax_weights_kernel<true>, grid, block, 0, (hipStream_t)stream, (long)n_q, (long)n_cand, k,
+                           q, (long)ldq, p, (long)ldp, pn, (long)c_base, (const long *)truth, lse, lse_lo, g, nsb, -nsb, v,
+                           (long)ldv, tiles_q);
+    else
+        hipLaunchKernelGGL(softmax_weights_kernel<false>, grid, block, 0, (hipStream_t)stream, (long)n_q, (long)n_cand, k,
+                           q, (long)ldq, p, (long)ldp, pn, (long)c_base, (const long *)truth, lse, lse_lo, g, nsb, -nsb, v,
+                           (long)ldv, tiles_q);
+    LKG_CHECK_LAUNCH("lkg_softmax_all_weights_f32");
+    return LKG_OK;
+}
+
+int lkg_internal_preload_softmax() {
+    hipFuncAttributes attr;
+    return hipFuncGetAttributes(&attr, reinterpret_cast<const void *>(&softmax_finish_kernel<true>)) == hipSuccess ? 0 : 1;
+}

@@ -616,6 +616,9 @@ class ShardedLiteralKG(nn.Module):
         if mode == "update_att":
             self.local.device = device
             return self.update_attention(*input)
+        if mode == "one_vs_all":
+            raise NotImplementedError("mode='one_vs_all' scores every entity of the whole table: the row-sharded model "
+                                      "holds a block of it per rank (train 1-vs-all on a single-device LiteralKG)")
         # pre_training / fine_tuning / predict / mlp: the module's own code over the gathered rows (unknown modes: None)
         return self.local(*input, device=device, mode=mode)
 

@@ -561,6 +561,15 @@ class LiteralKG(nn.Module):
         return ops.transe_loss(self.gat_embed, self.relation_embed.weight, h, r, pos_t, neg_t,
                                self.kg_l2loss_lambda, keep, sparse)
 
+    def calc_one_vs_all_loss(self, h, r, t, side: str = "tail", scale: float = 1.0, reduction: str = "mean",
+                             scoring: Optional[str] = None, splits: Optional[int] = None):
+        """1-vs-all training loss of the triples (h, r, t) (literalkg_amd/one_vs_all.py): cross-entropy of the true tail
+        (side 'tail'), head ('head') or the mean of both ('both') against the softmax over EVERY entity under scoring
+        'transr' / 'transe' / 'dot' (default: self.scoring).  Always on the full table of the step (prune_to_batch does
+        not apply); no L2 term (weight decay is the optimizer's).  Also ``model(h, r, t, device=, mode='one_vs_all')``."""
+        from .one_vs_all import one_vs_all_loss
+        return one_vs_all_loss(self, h, r, t, side=side, scale=scale, reduction=reduction, scoring=scoring, splits=splits)
+
     def _rows_only_projection_applies(self) -> bool:
         """A loss that reads a few rows of linear_gat's output and has to run the encoder anyway (a training step, or any call
         with autograd on: the inference heads' kept table is for eval mode under no_grad)."""
@@ -847,10 +856,12 @@ class LiteralKG(nn.Module):
         self.device = device
         if self.__dict__.get("_prune_skip", 0) > 0 and mode != "update_att":
             self._prune_skip -= 1
-        if mode in ("pre_training", "fine_tuning", "mlp") and (self.training or torch.is_grad_enabled()):
+        if mode in ("pre_training", "fine_tuning", "mlp", "one_vs_all") and (self.training or torch.is_grad_enabled()):
             self._eval_cache = None           # a training step: whatever table the inference heads kept is about to be stale
         if mode == "pre_training":
             return self.calc_triplet_loss(*input)
+        if mode == "one_vs_all":
+            return self.calc_one_vs_all_loss(*input)
         if mode == "update_att":
             return self.update_attention(*input)
         if mode == "predict":

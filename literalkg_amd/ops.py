@@ -2915,3 +2915,163 @@ def retrieval_finish(qkey_ptr: torch.Tensor, row_base: torch.Tensor, buckets: to
         N.call("lkg_retrieval_finish", n_q, N.ptr(qkey_ptr), N.ptr(row_base), margs[0], N.ptr(buckets), *margs[1:],
                N.ptr(before), N.ptr(position), *outs, _stream())
     return before, position, metrics
+
+
+# ----------------------------------------------------------------------------- 1-vs-all loss (lkg_softmax.hip)
+SOFTMAX_MAX_SPLITS = 64
+SOFTMAX_CHUNK_BYTES = 256 << 20        # the backward's weights V: B x Nc x 4 bytes per chunk of candidates
+SOFTMAX_DQ_SLICE = 4096                # dQ += 2 V P in reductions of this many candidates: lkg_gemm_f32's f32 MFMA sums a
+#                                        reduction in ONE chain, whose rounding grows like sqrt(length); short chains from
+#                                        zero, added up, keep dQ near torch's blocked sum
+
+
+def check_softmax_args(scale, splits, chunk_bytes=SOFTMAX_CHUNK_BYTES):
+    """(scale, splits, chunk_bytes) of softmax_all_loss as a float > 0, an int in [0, SOFTMAX_MAX_SPLITS] (None -> 0 =
+    automatic) and a positive int; ValueError otherwise.  Host only."""
+    if isinstance(scale, bool) or not isinstance(scale, (int, float)) or not 0.0 < float(scale) < float("inf"):
+        raise ValueError(f"scale must be a positive finite number, got {scale!r}")
+    splits = 0 if splits is None else splits
+    if isinstance(splits, bool) or int(splits) != splits or not 0 <= splits <= SOFTMAX_MAX_SPLITS:
+        raise ValueError(f"splits must be None or an integer in [0, {SOFTMAX_MAX_SPLITS}], got {splits!r}")
+    if isinstance(chunk_bytes, bool) or int(chunk_bytes) != chunk_bytes or chunk_bytes <= 0:
+        raise ValueError(f"chunk_bytes must be a positive integer, got {chunk_bytes!r}")
+    return float(scale), int(splits), int(chunk_bytes)
+
+
+def softmax_all_splits(n_q: int, n_c: int, splits: Optional[int] = None) -> int:
+    """The number S of candidate splits lkg_softmax_all_partial_f32 runs n_q queries against n_c candidates in (splits
+    None / 0: automatic).  The loss's last bits may depend on S; for a given S they do not change from run to run."""
+    return int(N.load().lkg_softmax_all_splits(int(n_q), int(n_c), int(splits or 0)))
+
+
+def softmax_chunk_width(n_q: int, n_c: int, chunk_bytes: int = SOFTMAX_CHUNK_BYTES) -> int:
+    """Candidates per chunk of the backward pass: whole 256-candidate tiles whose weights fit chunk_bytes (one tile at least)."""
+    return min(max(n_c, 1), max(256, int(chunk_bytes) // (4 * max(n_q, 1)) // 256 * 256))
+
+
+def _softmax_operands(what: str, q, p, truth, pn=None):
+    _need_gpu(q, p, truth, pn)
+    q, p, truth = _f32_rows(q), _f32_rows(p), _i64(truth.reshape(-1))
+    if p.shape[1] != q.shape[1] or q.shape[1] == 0 or p.shape[0] == 0 or truth.numel() != q.shape[0] or \
+            (pn is not None and pn.numel() != p.shape[0]):
+        raise ValueError(f"{what}: queries {tuple(q.shape)}, candidates {tuple(p.shape)}, {truth.numel()} truths")
+    return q, p, truth
+
+
+def softmax_all_forward(q: torch.Tensor, p: torch.Tensor, pn: Optional[torch.Tensor], truth: torch.Tensor,
+                        scale: float = 1.0, splits: Optional[int] = None):
+    """(lse float32[2, B], loss float32[B]) of lkg_softmax_all_partial_f32 + lkg_softmax_all_finish_f32, no autograd: the
+    logits are z = -scale (pn[c] - 2 q.p_c) with pn = rank_sqnorm(p), or scale q.p_c with pn None; lse[0] = logsumexp_c z
+    rounded once, lse[1] what that rounding dropped (softmax_all_weights takes both), loss = logsumexp - z at truth.
+    truth outside [0, N) is clamped (callers hand in checked ids)."""
+    q, p, truth = _softmax_operands("softmax_all_forward", q, p, truth, pn)
+    scale, splits, _ = check_softmax_args(scale, splits)
+    (b, k), n, dev = q.shape, p.shape[0], q.device
+    lse = torch.empty((2, b), dtype=torch.float32, device=dev)
+    loss = torch.empty(b, dtype=torch.float32, device=dev)
+    if b == 0:
+        return lse, loss
+    s_ = softmax_all_splits(b, n, splits)
+    ws = torch.empty((2, s_, b), dtype=torch.float32, device=dev)
+    N.call("lkg_softmax_all_partial_f32", b, n, k, N.ptr(q), _ld(q), N.ptr(p), _ld(p), N.ptr(pn), scale, s_, N.ptr(ws[0]),
+           N.ptr(ws[1]), _stream())
+    N.call("lkg_softmax_all_finish_f32", b, n, k, N.ptr(q), _ld(q), N.ptr(p), _ld(p), N.ptr(pn), N.ptr(truth), scale, s_,
+           N.ptr(ws[0]), N.ptr(ws[1]), N.ptr(lse[0]), N.ptr(lse[1]), N.ptr(loss), _stream())
+    return lse, loss
+
+
+def softmax_all_weights(q: torch.Tensor, p: torch.Tensor, pn: Optional[torch.Tensor], truth: torch.Tensor,
+                        lse: torch.Tensor, g: torch.Tensor, scale: float = 1.0, c0: int = 0, c1: Optional[int] = None,
+                        out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """V[:, c0:c1] of lkg_softmax_all_weights_f32 (B x (c1 - c0), into ``out`` when given, whose row stride is free):
+    V[i, c] = scale beta g[i] (exp(z_ic - lse[i]) - [c == truth[i]]), beta = 1 with pn, 1/2 without.  lse: float32[2, B]
+    as softmax_all_forward returns it (the rounded value and its remainder), or float32[B] (no remainder)."""
+    q, p, truth = _softmax_operands("softmax_all_weights", q, p, truth, pn)
+    _need_gpu(lse, g, out)
+    scale = check_softmax_args(scale, 0)[0]
+    (b, k), n = q.shape, p.shape[0]
+    c1 = n if c1 is None else int(c1)
+    c0 = int(c0)
+    if not 0 <= c0 <= c1 <= n:
+        raise ValueError(f"softmax_all_weights: the chunk [{c0}, {c1}) does not lie in [0, {n}]")
+    lse, g = lse.reshape(-1, b).contiguous() if b else lse.reshape(-1, 0), g.reshape(-1).contiguous()
+    if lse.shape[0] not in (1, 2) or g.numel() != b or lse.dtype != torch.float32 or g.dtype != torch.float32:
+        raise ValueError(f"softmax_all_weights: lse must be float32[{b}] or [2, {b}], g float32[{b}]")
+    if b == 0:
+        return out if out is not None else torch.empty((0, c1 - c0), dtype=torch.float32, device=q.device)
+    if out is None:
+        out = torch.empty((b, c1 - c0), dtype=torch.float32, device=q.device)
+    elif tuple(out.shape) != (b, c1 - c0) or out.dtype != torch.float32 or (out.numel() and out.stride(1) != 1) or \
+            (b > 1 and out.stride(0) < c1 - c0):
+        raise ValueError(f"softmax_all_weights: out must be a float32 {b} x {c1 - c0} tensor with unit column stride")
+    pc = p[c0:c1]
+    N.call("lkg_softmax_all_weights_f32", b, c1 - c0, k, N.ptr(q), _ld(q), N.ptr(pc), _ld(p), N.ptr(pn[c0:c1]) if pn is not None
+           else None, c0, N.ptr(truth), N.ptr(lse[0]), N.ptr(lse[1]) if lse.shape[0] == 2 else None, N.ptr(g), scale,
+           N.ptr(out), max(_ld(out), c1 - c0), _stream())
+    return out
+
+
+class _SoftmaxAllLoss(Function):
+    """loss_i = logsumexp_c z_ic - z_i,truth_i over ALL rows of p.  Forward: two launches, nothing of size B x N.  Backward:
+    per chunk of candidates the weights V (lkg_softmax_all_weights_f32), then dQ += 2 V P_chunk and dP_chunk = 2 V^T Q -
+    2 diag(colsum V) P_chunk on ops.gemm.  Both products run with beta = 1 onto an initialised output: lkg_gemm_f32 splits
+    a beta = 0 product with a long reduction over float atomics, whose sum changes from run to run; for the same reason
+    the column sums come out of the second product (a column of ones next to Q), not from ops.colsum."""
+
+    @staticmethod
+    def forward(ctx, q, p, truth, distance, scale, splits, chunk_bytes):
+        q_, p_, truth = _softmax_operands("softmax_all_loss", q, p, truth)
+        pn = rank_sqnorm(p_) if distance else None
+        lse, loss = softmax_all_forward(q_, p_, pn, truth, scale, splits)
+        ctx.save_for_backward(q_, p_, pn, truth, lse)
+        ctx.meta = (scale, chunk_bytes)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        q, p, pn, truth, lse = ctx.saved_tensors
+        scale, chunk_bytes = ctx.meta
+        want_q, want_p = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        (b, k), n, dev = q.shape, p.shape[0], q.device
+        dq = torch.zeros((b, k), dtype=torch.float32, device=dev) if want_q else None
+        dp = torch.empty((n, k), dtype=torch.float32, device=dev) if want_p else None
+        if b == 0:
+            return dq, dp.zero_() if want_p else None, None, None, None, None, None
+        g = g.reshape(-1).float().contiguous()
+        width = softmax_chunk_width(b, n, chunk_bytes)
+        vbuf = torch.empty((b, width), dtype=torch.float32, device=dev)
+        if want_p and pn is not None:
+            # colsum V rides in the product as a column of ones next to Q (k + 1 columns fill the same 128-wide tiles as
+            # k = 300): lkg_colsum_f32 adds its partial sums with float atomics, whose order changes from run to run
+            q1 = torch.cat((q, torch.ones((b, 1), dtype=torch.float32, device=dev)), dim=1)
+            tmp = torch.empty((width, k + 1), dtype=torch.float32, device=dev)
+        for c0 in range(0, n, width):                  # a fixed order: dQ accumulates slice after slice, chunk after chunk
+            c1 = min(n, c0 + width)
+            v = softmax_all_weights(q, p, pn, truth, lse, g, scale, c0, c1, out=vbuf[:, :c1 - c0])
+            pc = p[c0:c1]
+            if want_q:
+                for s0 in range(0, c1 - c0, SOFTMAX_DQ_SLICE):
+                    s1 = min(c1 - c0, s0 + SOFTMAX_DQ_SLICE)
+                    gemm(v[:, s0:s1], pc[s0:s1], alpha=2.0, beta=1.0, out=dq)
+            if want_p:
+                dpc = dp[c0:c1]                        # written once
+                if pn is not None:
+                    t = tmp[:c1 - c0].zero_()
+                    gemm(v, q1, trans_a=True, alpha=2.0, beta=1.0, out=t)          # [2 V^T Q | 2 colsum V]
+                    torch.addcmul(t[:, :k], t[:, k:], pc, value=-1.0, out=dpc)
+                else:
+                    gemm(v, q, trans_a=True, alpha=2.0, beta=1.0, out=dpc.zero_())
+        return dq, dp, None, None, None, None, None
+
+
+def softmax_all_loss(q: torch.Tensor, p: torch.Tensor, truth: torch.Tensor, distance: bool = True, scale: float = 1.0,
+                     splits: Optional[int] = None, chunk_bytes: int = SOFTMAX_CHUNK_BYTES) -> torch.Tensor:
+    """float32[B]: the cross-entropy of truth[i] against the softmax over ALL N rows of p for query row q[i] (1-vs-all).
+    distance True: logits z = -scale ||q - p_c||^2 (||q||^2 cancels; ||p_c||^2 is computed here, so the gradient of p is
+    complete); False: z = scale q.p_c.  Differentiable in q and p; the gradient of p is a dense N x k table (no RowSet
+    tag: every row is reached).  splits: candidate splits of the forward pass (None: automatic) -- the last bits of the
+    loss may depend on it, for a given value they do not change from run to run.  chunk_bytes bounds the backward's B x Nc
+    weights.  No L2 term: weight decay belongs to the optimizer (lkg_adam_step_f32)."""
+    _need_gpu(q, p, truth)
+    scale, splits, chunk_bytes = check_softmax_args(scale, splits, chunk_bytes)
+    return _SoftmaxAllLoss.apply(q, p, truth, bool(distance), scale, splits, chunk_bytes)
