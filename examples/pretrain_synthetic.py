@@ -21,6 +21,7 @@ import __graft_entry__ as ge  # noqa: E402
 
 ge.build()
 from literalkg_amd import LiteralKG                      # noqa: E402  (the one-line change vs `from model import LiteralKG`)
+from literalkg_amd import KnownTriples                   # noqa: E402  (--filtered)
 from literalkg_amd.synth import make_batch, make_kg      # noqa: E402
 
 
@@ -48,7 +49,12 @@ def main():
                     help="sampled: the reference's loss over pre_training_neg_rate sampled negatives (mode='pre_training'); "
                          "one_vs_all: cross-entropy of the true tail against the softmax over every entity "
                          "(mode='one_vs_all'; the sampled negatives of the batch are not used)")
+    ap.add_argument("--filtered", action="store_true",
+                    help="with --objective one_vs_all: the other known tails of (h, r, ?) among the training triples leave "
+                         "the row's softmax (calc_one_vs_all_loss(known=...)), as filtered MRR drops them")
     a = ap.parse_args()
+    if a.filtered and a.objective != "one_vs_all":
+        ap.error("--filtered goes with --objective one_vs_all")
     device = torch.device("cuda:0")
     args = SimpleNamespace(use_pretrain=0, device=device, embed_dim=a.dim, relation_dim=a.dim, scale_gat_dim=None,
                            use_residual=False, alpha=0.1, lamda=0.5, aggregation_type="gcn", n_conv_layers=a.layers,
@@ -64,6 +70,7 @@ def main():
     model.to(device)
     h_list, t_list, r_list = (torch.from_numpy(x).to(device) for x in (h, t, r))
     relations = list(range(16))
+    known = KnownTriples(h_list, r_list, t_list, a.entities, 16) if a.filtered else None
     for epoch in range(1, a.epochs + 1):
         model.train()
         t0, total = time.time(), 0.0
@@ -71,7 +78,9 @@ def main():
             bh, br, bp, bn = (torch.from_numpy(x).to(device)
                               for x in make_batch(a.entities, a.batch_groups, 3, seed=epoch * 10_000 + it))
             optimizer.zero_grad()
-            if a.objective == "one_vs_all":
+            if a.filtered:
+                loss = model.calc_one_vs_all_loss(bh[::3], br[::3], bp[::3], known=known)
+            elif a.objective == "one_vs_all":
                 loss = model(bh[::3], br[::3], bp[::3], device=device, mode="one_vs_all")   # one triple per group
             else:
                 loss = model(bh, br, bp, bn, device=device, mode="pre_training")

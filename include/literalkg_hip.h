@@ -928,6 +928,34 @@ int lkg_softmax_all_weights_f32(int64_t n_q, int64_t n_cand, int32_t k, const fl
                                 int64_t ldp, const float *pn, int64_t c_base, const int64_t *truth, const float *lse,
                                 const float *lse_lo, const float *g, float scale, float *v, int64_t ldv, void *stream);
 
+/* The filtered 1-vs-all loss: query i drops the candidate POSITIONS xcol[xptr[i] .. xptr[i + 1]) (ascending, unique,
+ * n_excl = xptr[n_q] < 2^31 entries in all) from its softmax -- a dropped candidate has logit -inf before the running
+ * (max, sum) sees it, and weight exactly 0.  The truth of a query must not be in its list (lkg_softmax_excluded never puts
+ * it there), so lkg_softmax_all_finish_f32 serves both routes.  With every list empty the masked entry points give the
+ * bits of the unmasked ones for the same splits.  No float atomics.
+ *
+ * lkg_softmax_excluded: builds the lists from the known-triple structure of lkg_csr_build_device over n_rows entities
+ *     (rowptr, col, eptr, rel), one wave per query, in two passes.  Query i walks row filter_row[i] and keeps an entry iff
+ *     it is known under relation filter_rel[i] (< 0: under any relation), its entity maps to a candidate -- position
+ *     pos[entity] (pos int32[n_rows], -1 = not a candidate; must be increasing over the candidates), or the entity id
+ *     itself with pos NULL -- inside [0, n_cand), and that position is not truth[i].  First pass (count given, xptr and
+ *     xcol NULL): count[i] = the list's length.  The caller forms xptr = the exclusive cumulative sum.  Second pass
+ *     (count NULL): fills xcol.
+ * lkg_softmax_all_partial_masked_f32 / lkg_softmax_all_weights_masked_f32: as the unmasked entry points; in the weights
+ *     the lists hold positions of the whole table (c_base + the chunk's column).                                      */
+int lkg_softmax_excluded(int64_t n_q, int64_t n_rows, int64_t n_cand, const int64_t *filter_row, const int64_t *filter_rel,
+                         const int64_t *truth, const int32_t *rowptr, const int32_t *col, const int32_t *eptr,
+                         const int32_t *rel, const int32_t *pos, int32_t *count, const int32_t *xptr, int32_t *xcol,
+                         void *stream);
+int lkg_softmax_all_partial_masked_f32(int64_t n_q, int64_t n_cand, int32_t k, const float *q, int64_t ldq, const float *p,
+                                       int64_t ldp, const float *pn, float scale, int32_t splits, const int32_t *xptr,
+                                       const int32_t *xcol, int64_t n_excl, float *ws_m, float *ws_l, void *stream);
+int lkg_softmax_all_weights_masked_f32(int64_t n_q, int64_t n_cand, int32_t k, const float *q, int64_t ldq, const float *p,
+                                       int64_t ldp, const float *pn, int64_t c_base, const int64_t *truth,
+                                       const float *lse, const float *lse_lo, const float *g, float scale,
+                                       const int32_t *xptr, const int32_t *xcol, int64_t n_excl, float *v, int64_t ldv,
+                                       void *stream);
+
 #ifdef __cplusplus
 }
 #endif

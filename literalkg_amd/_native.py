@@ -128,6 +128,10 @@ PROTOTYPES = {
     "lkg_softmax_all_partial_f32": [i64, i64, i32, vp, i64, vp, i64, vp, f32, i32, vp, vp, vp],
     "lkg_softmax_all_finish_f32": [i64, i64, i32, vp, i64, vp, i64, vp, vp, f32, i32, vp, vp, vp, vp, vp, vp],
     "lkg_softmax_all_weights_f32": [i64, i64, i32, vp, i64, vp, i64, vp, i64, vp, vp, vp, vp, f32, vp, i64, vp],
+    "lkg_softmax_excluded": [i64, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+    "lkg_softmax_all_partial_masked_f32": [i64, i64, i32, vp, i64, vp, i64, vp, f32, i32, vp, vp, i64, vp, vp, vp],
+    "lkg_softmax_all_weights_masked_f32": [i64, i64, i32, vp, i64, vp, i64, vp, i64, vp, vp, vp, vp, f32, vp, vp, i64, vp,
+                                           i64, vp],
 }
 _RESTYPE = {"lkg_last_error": C.c_char_p, "lkg_csr_build_device_workspace": C.c_int64,
             "lkg_gemm_tall_workspace": C.c_int64, "lkg_gemm_workspace": C.c_int64,

@@ -16,7 +16,17 @@
 // tile (a per-tile meeting would cost two barriers per tile and change nothing but the association).  The workgroup's (m, l)
 // goes to workspace [S][B]; softmax_finish_kernel merges the S partials of a row in split order in float64.  No float
 // atomics: for a given S every bit is the same from run to run.
+//
+// Filtered variants (MASKED): query i drops the sorted candidate positions xcol[xptr[i] .. xptr[i + 1]) from
+// its softmax -- the other known answers of the query.  A dropped column gets z = -inf inside the tile, exactly as a column
+// past n_c does, BEFORE the running (max, sum) sees it (subtracting the dropped mass afterwards is amplified by
+// 1 / (1 - dropped mass) without bound); the weights kernel stores exactly 0 there.  Lane = row of the wave's 64 walks its
+// row's list with a cursor, turns the entries inside the wave's 64 columns into a 64-bit mask and leaves it in LDS for the
+// lanes that hold the row's logits (wave-local: no workgroup barrier); a wave none of whose rows drops a column of the
+// tile skips all of it.  The truth is never in a list (softmax_excluded_kernel), so the finish kernel serves both.
 #include "lkg_rank_common.h"
+
+#include <climits>
 
 #pragma clang fp contract(off)
 
@@ -29,6 +39,59 @@ constexpr int SM_MAX_SPLITS = LKG_SOFTMAX_MAX_SPLITS;
 
 // exp(z - m) must not see inf - inf: a pair that has met no candidate yet is (-inf, 0) and takes 0 as its reference
 __device__ __forceinline__ float safe_ref(float m) { return m == -__builtin_inff() ? 0.f : m; }
+
+// A row's walk through its exclusion list: entries [cur, end) of xcol are still ahead, next = xcol[cur] (INT_MAX when
+// none is left: positions are < n_c < INT32_MAX).  xptr is clamped into [0, m_total], so a bad list cannot be read past.
+struct ExclCursor {
+    int cur, end, next;
+};
+
+// the list of query `row` (empty past n_q) from its first entry >= first (binary search)
+__device__ __forceinline__ ExclCursor excl_seek(const int *__restrict__ xptr, const int *__restrict__ xcol, int m_total,
+                                                long row, long n_q, long first) {
+    ExclCursor x{0, 0, INT_MAX};
+    if (row < n_q) {
+        x.cur = min(max(xptr[row], 0), m_total);
+        x.end = min(max(xptr[row + 1], x.cur), m_total);
+    }
+    int lo = x.cur, hi = x.end;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (xcol[mid] < first) lo = mid + 1;
+        else hi = mid;
+    }
+    x.cur = lo;
+    if (x.cur < x.end) x.next = xcol[x.cur];
+    return x;
+}
+
+// bit b set: position c0 + b is excluded; the cursor moves past every entry below c0 + 64
+__device__ __forceinline__ unsigned long long excl_tile_mask(ExclCursor &x, const int *__restrict__ xcol, long c0) {
+    unsigned long long mk = 0ull;
+    while ((long)x.next < c0 + 64) {
+        if ((long)x.next >= c0) mk |= 1ull << ((long)x.next - c0);
+        ++x.cur;
+        x.next = x.cur < x.end ? xcol[x.cur] : INT_MAX;
+    }
+    return mk;
+}
+
+// The wave's masks of one tile: lane = row computes its row's, the wave leaves them in sm (its own 64 words) when any is
+// non-zero.  Returns that wave-uniform "any".  LDS operations of one wave complete in order, so the rows' readers need no
+// workgroup barrier; the wave barriers keep the compiler from moving the accesses across each other.
+__device__ __forceinline__ bool excl_publish(ExclCursor &x, const int *__restrict__ xcol, long c0,
+                                             unsigned long long *sm, int lane) {
+    const unsigned long long mk = excl_tile_mask(x, xcol, c0);
+    const bool any = __ballot(mk != 0ull) != 0ull;
+    if (any) {
+        __builtin_amdgcn_wave_barrier();            // the previous tile's reads come first
+        sm[lane] = mk;
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    }
+    return any;
+}
 
 template <bool VEC>
 __global__ __launch_bounds__(SM_THREADS) void softmax_partial_kernel(long n_q, long n_c, int k, const float *__restrict__ q,
@@ -115,6 +178,99 @@ __global__ __launch_bounds__(SM_THREADS) void softmax_partial_kernel(long n_q, l
     }
 }
 
+// The filtered forward pass: softmax_partial_kernel with the exclusion lists (see the head of this file); everything
+// else -- the tile, nsb * s, the (m, l) recurrence, the meeting in LDS -- is the same text.
+template <bool VEC>
+__global__ __launch_bounds__(SM_THREADS) void softmax_partial_masked_kernel(
+    long n_q, long n_c, int k, const float *__restrict__ q, long ldq, const float *__restrict__ p, long ldp,
+    const float *__restrict__ pn, float nsb, int splits, long tiles_q, long tiles_c, float *__restrict__ ws_m,
+    float *__restrict__ ws_l, const int *__restrict__ xptr, const int *__restrict__ xcol, int m_total) {
+    __shared__ unsigned long long sm_x[4][SM_ROWS];
+    __shared__ float sm_m[4][SM_ROWS], sm_l[4][SM_ROWS];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int r = lane & 15, s = lane >> 4;
+    const long bid = blockIdx.x;
+    const long q0 = (bid % tiles_q) * SM_ROWS;
+    const int split = (int)(bid / tiles_q);
+    const long t_lo = split * tiles_c / splits, t_hi = (split + 1) * tiles_c / splits;
+    const float *qrow[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) qrow[i] = q + min(q0 + 16 * i + r, n_q - 1) * ldq;    // rows past the end: never written
+    float m[4][4], l[4][4];           // [i][v]: query row 16 i + 4 s + v, the same on the 16 lanes of the row
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+            m[i][v] = -__builtin_inff();
+            l[i][v] = 0.f;
+        }
+    ExclCursor x = excl_seek(xptr, xcol, m_total, q0 + lane, n_q, t_lo * SM_COLS);
+
+    for (long t = t_lo; t < t_hi; ++t) {
+        const long c0 = t * SM_COLS + wave * 64;
+        const float *prow[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) prow[i] = p + min(c0 + 16 * i + r, n_c - 1) * ldp;
+        f32x4 acc[4][4];
+        rank_tile_dots<VEC>(acc, qrow, prow, k, s);
+        // acc[i][j][v]: query row 16 i + 4 s + v, candidate c0 + 16 j + r
+        const bool any = excl_publish(x, xcol, c0, sm_x[wave], lane);      // wave-uniform: some row drops a column here
+        float pnv[4];
+        bool ok[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const long c = c0 + 16 * j + r;
+            ok[j] = c < n_c;
+            pnv[j] = (pn && ok[j]) ? pn[c] : 0.f;
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int v = 0; v < 4; ++v) {
+                float z[4], mt = -__builtin_inff();
+                unsigned long long mrow = 0ull;     // the row's dropped columns of the wave's 64
+                if (any) mrow = sm_x[wave][16 * i + 4 * s + v];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {       // a column past the end, or a dropped one, is -inf: no maximum, exp = 0
+                    const bool keep = ok[j] && !((mrow >> (16 * j + r)) & 1ull);
+                    z[j] = keep ? nsb * __builtin_fmaf(-2.f, acc[i][j][v], pnv[j]) : -__builtin_inff();
+                    mt = fmaxf(mt, z[j]);           // (a NaN logit is skipped here and poisons l below)
+                }
+                mt = group_max<16>(mt);
+                const float mn = fmaxf(m[i][v], mt), ref = safe_ref(mn);
+                float sum = 0.f;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) sum += expf(z[j] - ref);
+                sum = group_sum<16>(sum);
+                l[i][v] = l[i][v] * expf(m[i][v] - ref) + sum;
+                m[i][v] = mn;
+            }
+    }
+    if (r == 0) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int v = 0; v < 4; ++v) {
+                sm_m[wave][16 * i + 4 * s + v] = m[i][v];
+                sm_l[wave][16 * i + 4 * s + v] = l[i][v];
+            }
+    }
+    __syncthreads();
+    if (tid < SM_ROWS && q0 + tid < n_q) {
+        float mw = sm_m[0][tid];
+#pragma unroll
+        for (int w = 1; w < 4; ++w) mw = fmaxf(mw, sm_m[w][tid]);
+        const float ref = safe_ref(mw);
+        float lw = 0.f;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) lw += sm_l[w][tid] * expf(sm_m[w][tid] - ref);
+        const long o = (long)split * n_q + q0 + tid;
+        ws_m[o] = mw;
+        ws_l[o] = lw;
+    }
+}
+
+
 // One wave per query: the truth's logit with the pair routine of the ranking kernels, the S partials merged in split
 // order in float64, lse and loss rounded once each; lse_lo (nullable) is the remainder of lse's rounding, with which the
 // backward's exp(z - lse) does not carry |lse| u / 2 into every weight of the row.
@@ -196,6 +352,102 @@ __global__ __launch_bounds__(SM_THREADS) void softmax_weights_kernel(long n_q, l
                 if (row < n_q && cid[j] < n_c) out[cid[j]] = coef * w;
             }
         }
+}
+
+// The filtered backward's recompute: softmax_weights_kernel, a dropped column stored as exactly 0.
+template <bool VEC>
+__global__ __launch_bounds__(SM_THREADS) void softmax_weights_masked_kernel(
+    long n_q, long n_c, int k, const float *__restrict__ q, long ldq, const float *__restrict__ p, long ldp,
+    const float *__restrict__ pn, long c_base, const long *__restrict__ truth, const float *__restrict__ lse,
+    const float *__restrict__ lse_lo, const float *__restrict__ g, float nsb, float sb, float *__restrict__ vout, long ldv,
+    long tiles_q, const int *__restrict__ xptr, const int *__restrict__ xcol, int m_total) {
+    __shared__ unsigned long long sm_x[4][SM_ROWS];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int r = lane & 15, s = lane >> 4;
+    const long bid = blockIdx.x;
+    const long q0 = (bid % tiles_q) * SM_ROWS, c0 = (bid / tiles_q) * SM_COLS + wave * 64;
+    const float *qrow[4], *prow[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        qrow[i] = q + min(q0 + 16 * i + r, n_q - 1) * ldq;        // rows and columns past the end are clamped, never stored
+        prow[i] = p + min(c0 + 16 * i + r, n_c - 1) * ldp;
+    }
+    f32x4 acc[4][4];
+    rank_tile_dots<VEC>(acc, qrow, prow, k, s);
+    // as in the forward pass; the lists hold table positions: c_base + the chunk's column
+    ExclCursor x = excl_seek(xptr, xcol, m_total, q0 + lane, n_q, c_base + c0);
+    const bool any = excl_publish(x, xcol, c_base + c0, sm_x[wave], lane);
+    float pnv[4];
+    long cid[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        cid[j] = c0 + 16 * j + r;
+        pnv[j] = (pn && cid[j] < n_c) ? pn[cid[j]] : 0.f;
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+            const long row = q0 + 16 * i + 4 * s + v;
+            const long rr = min(row, n_q - 1);
+            const float ls = lse[rr], lo = lse_lo ? lse_lo[rr] : 0.f, coef = sb * g[rr];
+            const long tl = truth[rr] - c_base;
+            float *out = vout + rr * ldv;
+            unsigned long long mrow = 0ull;
+            if (any) mrow = sm_x[wave][16 * i + 4 * s + v];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const bool dropped = (mrow >> (16 * j + r)) & 1ull;
+                const float z = nsb * __builtin_fmaf(-2.f, acc[i][j][v], pnv[j]);
+                // exp(z - lse) with lse = ls + lo: d = fl(z - ls), its rounding error recovered exactly (TwoSum) and, with
+                // lo, applied to first order -- neither subtraction's rounding (up to |z - lse| u each) reaches the weight
+                const float d = z - ls, zp = d + ls, e = (z - zp) + (-ls - (d - zp));
+                const float w = expf(d) * (1.f + (e - lo)) - (cid[j] == tl ? 1.f : 0.f);
+                if (row < n_q && cid[j] < n_c) out[cid[j]] = dropped ? 0.f : coef * w;
+            }
+        }
+}
+
+
+// The exclusion lists of the filtered loss, one wave per query and two passes (FILL false: cnt[i] = the length of query
+// i's list; a cumulative sum on the host side makes xptr; FILL true: the entries).  Query i walks the known row frow[i]
+// (rowptr / col / eptr / rel of lkg_csr_build_device: cols ascending and unique) 64 entries at a time and keeps an entry
+// iff it is known under relation frel[i] (< 0: under any), maps to a candidate (pos[entity], or the entity itself without
+// pos) and is not the row's truth.  pos is monotone where it is not -1, so the kept positions come out ascending.
+template <bool FILL>
+__global__ __launch_bounds__(SM_THREADS) void softmax_excluded_kernel(
+    long n_q, long n_rows, long n_c, const long *__restrict__ frow, const long *__restrict__ frel,
+    const long *__restrict__ truth, const int *__restrict__ rowptr, const int *__restrict__ col,
+    const int *__restrict__ eptr, const int *__restrict__ rel, const int *__restrict__ pos, int *__restrict__ cnt,
+    const int *__restrict__ xptr, int *__restrict__ xcol) {
+    const long i = (long)blockIdx.x * (SM_THREADS / 64) + (threadIdx.x >> 6);
+    if (i >= n_q) return;                           // (a whole wave leaves)
+    const int lane = threadIdx.x & 63;
+    const long f = min(max(frow[i], 0L), n_rows - 1), tr = truth[i];
+    const int want = (int)frel[i];
+    const int e0 = rowptr[f], e1 = rowptr[f + 1];
+    int base = FILL ? xptr[i] : 0;
+    const int stop = FILL ? xptr[i + 1] : 0;
+    for (int eb = e0; eb < e1; eb += 64) {          // (uniform trip count in the wave)
+        const int e = eb + lane;
+        bool keep = false;
+        int c = -1;
+        if (e < e1) {
+            const int ent = col[e];
+            if (ent >= 0 && ent < n_rows) c = pos ? pos[ent] : ent;
+            if (c >= 0 && c < n_c && c != tr) {
+                keep = want < 0;
+                for (int x = eptr[e]; x < eptr[e + 1] && !keep; ++x) keep = rel[x] == want;
+            }
+        }
+        const unsigned long long kept = __ballot(keep);
+        if (FILL) {
+            const int o = base + __popcll(kept & ((1ull << lane) - 1ull));
+            if (keep && o < stop) xcol[o] = c;
+        }
+        base += __popcll(kept);
+    }
+    if (!FILL && lane == 0) cnt[i] = base;
 }
 
 bool vec_ok(const void *a, long lda, const void *b, long ldb) {
@@ -288,6 +540,87 @@ extern "C" int lkg_softmax_all_weights_f32(int64_t n_q, int64_t n_cand, int32_t 
                            q, (long)ldq, p, (long)ldp, pn, (long)c_base, (const long *)truth, lse, lse_lo, g, nsb, -nsb, v,
                            (long)ldv, tiles_q);
     LKG_CHECK_LAUNCH("lkg_softmax_all_weights_f32");
+    return LKG_OK;
+}
+
+extern "C" int lkg_softmax_excluded(int64_t n_q, int64_t n_rows, int64_t n_cand, const int64_t *filter_row,
+                                    const int64_t *filter_rel, const int64_t *truth, const int32_t *rowptr,
+                                    const int32_t *col, const int32_t *eptr, const int32_t *rel, const int32_t *pos,
+                                    int32_t *count, const int32_t *xptr, int32_t *xcol, void *stream) {
+    LKG_REQUIRE(n_q >= 0 && n_rows > 0 && n_rows < INT32_MAX && n_cand > 0 && n_cand < INT32_MAX,
+                "lkg_softmax_excluded: bad sizes");
+    LKG_REQUIRE((count && !xptr && !xcol) || (!count && xptr && xcol),
+                "lkg_softmax_excluded: either count (first pass) or xptr and xcol (second pass)");
+    if (n_q == 0) return LKG_OK;
+    LKG_REQUIRE(filter_row && filter_rel && truth && rowptr && col && eptr && rel, "lkg_softmax_excluded: null pointer");
+    const dim3 grid((unsigned)((n_q + 3) / 4)), block(SM_THREADS);
+    if (count)
+        hipLaunchKernelGGL(softmax_excluded_kernel<false>, grid, block, 0, (hipStream_t)stream, (long)n_q, (long)n_rows,
+                           (long)n_cand, (const long *)filter_row, (const long *)filter_rel, (const long *)truth, rowptr,
+                           col, eptr, rel, pos, count, xptr, xcol);
+    else
+        hipLaunchKernelGGL(softmax_excluded_kernel<true>, grid, block, 0, (hipStream_t)stream, (long)n_q, (long)n_rows,
+                           (long)n_cand, (const long *)filter_row, (const long *)filter_rel, (const long *)truth, rowptr,
+                           col, eptr, rel, pos, count, xptr, xcol);
+    LKG_CHECK_LAUNCH("lkg_softmax_excluded");
+    return LKG_OK;
+}
+
+extern "C" int lkg_softmax_all_partial_masked_f32(int64_t n_q, int64_t n_cand, int32_t k, const float *q, int64_t ldq,
+                                                  const float *p, int64_t ldp, const float *pn, float scale,
+                                                  int32_t splits, const int32_t *xptr, const int32_t *xcol, int64_t n_excl,
+                                                  float *ws_m, float *ws_l, void *stream) {
+    LKG_REQUIRE(n_q >= 0 && n_cand > 0 && n_cand < INT32_MAX && k > 0 && ldq >= k && ldp >= k && n_excl >= 0 &&
+                    n_excl < INT32_MAX,
+                "lkg_softmax_all_partial_masked_f32: bad sizes");
+    LKG_REQUIRE(scale_ok(scale), "lkg_softmax_all_partial_masked_f32: scale must be positive and finite");
+    if (n_q == 0) return LKG_OK;
+    LKG_REQUIRE(splits >= 1 && splits == lkg_softmax_all_splits(n_q, n_cand, splits),
+                "lkg_softmax_all_partial_masked_f32: splits must come from lkg_softmax_all_splits");
+    LKG_REQUIRE(q && p && ws_m && ws_l && xptr && (xcol || n_excl == 0),
+                "lkg_softmax_all_partial_masked_f32: null pointer");
+    const long tiles_q = (n_q + SM_ROWS - 1) / SM_ROWS, tiles_c = (n_cand + SM_COLS - 1) / SM_COLS;
+    LKG_REQUIRE(tiles_q * splits < INT32_MAX,
+                "lkg_softmax_all_partial_masked_f32: too many workgroups (split the queries)");
+    const dim3 grid((unsigned)(tiles_q * splits)), block(SM_THREADS);
+    const float nsb = neg_scale_beta(scale, pn);
+    if (vec_ok(q, ldq, p, ldp))
+        hipLaunchKernelGGL(softmax_partial_masked_kernel<true>, grid, block, 0, (hipStream_t)stream, (long)n_q,
+                           (long)n_cand, k, q, (long)ldq, p, (long)ldp, pn, nsb, splits, tiles_q, tiles_c, ws_m, ws_l, xptr,
+                           xcol, (int)n_excl);
+    else
+        hipLaunchKernelGGL(softmax_partial_masked_kernel<false>, grid, block, 0, (hipStream_t)stream, (long)n_q,
+                           (long)n_cand, k, q, (long)ldq, p, (long)ldp, pn, nsb, splits, tiles_q, tiles_c, ws_m, ws_l, xptr,
+                           xcol, (int)n_excl);
+    LKG_CHECK_LAUNCH("lkg_softmax_all_partial_masked_f32");
+    return LKG_OK;
+}
+
+extern "C" int lkg_softmax_all_weights_masked_f32(int64_t n_q, int64_t n_cand, int32_t k, const float *q, int64_t ldq,
+                                                  const float *p, int64_t ldp, const float *pn, int64_t c_base,
+                                                  const int64_t *truth, const float *lse, const float *lse_lo,
+                                                  const float *g, float scale, const int32_t *xptr, const int32_t *xcol,
+                                                  int64_t n_excl, float *v, int64_t ldv, void *stream) {
+    LKG_REQUIRE(n_q >= 0 && n_cand >= 0 && n_cand < INT32_MAX && k > 0 && ldq >= k && ldp >= k && ldv >= n_cand &&
+                    c_base >= 0 && c_base < INT32_MAX && n_excl >= 0 && n_excl < INT32_MAX,
+                "lkg_softmax_all_weights_masked_f32: bad sizes");
+    LKG_REQUIRE(scale_ok(scale), "lkg_softmax_all_weights_masked_f32: scale must be positive and finite");
+    if (n_q == 0 || n_cand == 0) return LKG_OK;
+    LKG_REQUIRE(q && p && truth && lse && g && v && xptr && (xcol || n_excl == 0),
+                "lkg_softmax_all_weights_masked_f32: null pointer");
+    const long tiles_q = (n_q + SM_ROWS - 1) / SM_ROWS, tiles_c = (n_cand + SM_COLS - 1) / SM_COLS;
+    LKG_REQUIRE(tiles_q * tiles_c < INT32_MAX, "lkg_softmax_all_weights_masked_f32: too many tiles (use smaller chunks)");
+    const dim3 grid((unsigned)(tiles_q * tiles_c)), block(SM_THREADS);
+    const float nsb = neg_scale_beta(scale, pn);
+    if (vec_ok(q, ldq, p, ldp))
+        hipLaunchKernelGGL(softmax_weights_masked_kernel<true>, grid, block, 0, (hipStream_t)stream, (long)n_q,
+                           (long)n_cand, k, q, (long)ldq, p, (long)ldp, pn, (long)c_base, (const long *)truth, lse, lse_lo, g,
+                           nsb, -nsb, v, (long)ldv, tiles_q, xptr, xcol, (int)n_excl);
+    else
+        hipLaunchKernelGGL(softmax_weights_masked_kernel<false>, grid, block, 0, (hipStream_t)stream, (long)n_q,
+                           (long)n_cand, k, q, (long)ldq, p, (long)ldp, pn, (long)c_base, (const long *)truth, lse, lse_lo, g,
+                           nsb, -nsb, v, (long)ldv, tiles_q, xptr, xcol, (int)n_excl);
+    LKG_CHECK_LAUNCH("lkg_softmax_all_weights_masked_f32");
     return LKG_OK;
 }
 

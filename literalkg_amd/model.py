@@ -562,13 +562,16 @@ class LiteralKG(nn.Module):
                                self.kg_l2loss_lambda, keep, sparse)
 
     def calc_one_vs_all_loss(self, h, r, t, side: str = "tail", scale: float = 1.0, reduction: str = "mean",
-                             scoring: Optional[str] = None, splits: Optional[int] = None):
+                             scoring: Optional[str] = None, splits: Optional[int] = None, known=None, candidates=None):
         """1-vs-all training loss of the triples (h, r, t) (literalkg_amd/one_vs_all.py): cross-entropy of the true tail
         (side 'tail'), head ('head') or the mean of both ('both') against the softmax over EVERY entity under scoring
         'transr' / 'transe' / 'dot' (default: self.scoring).  Always on the full table of the step (prune_to_batch does
-        not apply); no L2 term (weight decay is the optimizer's).  Also ``model(h, r, t, device=, mode='one_vs_all')``."""
+        not apply); no L2 term (weight decay is the optimizer's).  known (a KnownTriples): the other known answers of a
+        query leave its softmax (the filtered loss); candidates (unique entity ids, one side only): the softmax runs over
+        those entities alone.  Also ``model(h, r, t, device=, mode='one_vs_all')``, the plain call."""
         from .one_vs_all import one_vs_all_loss
-        return one_vs_all_loss(self, h, r, t, side=side, scale=scale, reduction=reduction, scoring=scoring, splits=splits)
+        return one_vs_all_loss(self, h, r, t, side=side, scale=scale, reduction=reduction, scoring=scoring, splits=splits,
+                               known=known, candidates=candidates)
 
     def _rows_only_projection_applies(self) -> bool:
         """A loss that reads a few rows of linear_gat's output and has to run the encoder anyway (a training step, or any call

@@ -13,9 +13,19 @@ pass).  P is the full table of the step, ``gat_embeddings()`` with its autograd 
 row is a candidate, so ``prune_to_batch`` does not apply here.  'transr' groups the triples by relation and scores each
 group against P_r = P W_r; every P_r (N x relation_dim floats) stays alive until the backward pass has used it.
 
-There is no L2 term (lkg_adam_step_f32 carries weight decay), no ``known`` filter in the denominator (other true answers
-stay negatives, as in plain 1vsAll), no ``candidates`` subset and no label smoothing.  Under ``torch.no_grad()`` in eval
-mode the table is the cached inference table and ``reduction='none'`` gives the per-triple negative log-likelihood.
+Filtered loss.  ``known`` (a KnownTriples) drops from the row of (h, r, ?) every candidate c != t with
+(h, r, c) known -- from the row of (?, r, t) every c != h with (c, r, t) known; 'dot' ignores r and drops the entities
+known under ANY relation -- so the other true answers of a query are no longer its negatives, which is what filtered MRR
+measures.  The truth is exempt: ``known`` may or may not hold the trained triples.  The mask is applied inside the tile,
+before the running (max, sum) sees the logit (ops.softmax_excluded builds the lists, the masked kernels of lkg_softmax.hip
+apply them).  ``candidates`` (unique entity ids, sorted internally: the result has the same bits for any order) restricts
+the softmax to those rows -- type-constrained training; one side at a time, every truth must be a candidate, the table's
+gradient reaches only candidate and query rows, and 'transr' projects the gathered rows, not the N-row table.
+
+There is no L2 term (lkg_adam_step_f32 carries weight decay), no label smoothing (its extra term eps (z_t - mean z) has a
+closed form in column sums and would bring its own accuracy contract) and no multi-hot (KvsAll) targets.  Under
+``torch.no_grad()`` in eval mode the table is the cached inference table and ``reduction='none'`` gives the per-triple
+negative log-likelihood.
 """
 from __future__ import annotations
 
@@ -37,56 +47,94 @@ def check_reduction(reduction: str) -> str:
     return reduction
 
 
-def _side_losses(scoring: str, side: str, p, relemb, h, r, t, scale, splits):
-    """float32[len(h)]: per triple the loss of the side (the mean of the two sides' for 'both') against the rows p."""
+def _side_losses(model, scoring: str, side: str, table, rows, w, h, r, t, scale, splits, known, pos):
+    """float32[len(h)]: per triple the loss of the side (the mean of the two sides' for 'both').  rows: the candidate rows
+    -- the table itself, or (pos given: the entity -> position map) the gathered rows of the candidates -- projected by w
+    for 'transr'; with candidates the query rows are gathered from the table and projected on their own.  known / pos:
+    the exclusion lists of ops.softmax_excluded per side."""
+    relemb = model.relation_embed.weight
+    p = rows if w is None else ops.matmul(rows, w)              # alive until the backward pass (transr: N x relation_dim)
     total = None
     for s_ in Q.rank_sides(side):
         ent, truth = (h, t) if s_ == "tail" else (t, h)
-        q = pruned.gather_rows(p, ent)
+        if pos is None:
+            q = pruned.gather_rows(p, ent)
+        else:
+            q = pruned.gather_rows(table, ent)
+            q = q if w is None else ops.matmul(q, w)
+            truth = pos[truth].long()                          # (every truth is a candidate: checked by the caller)
         if scoring != "dot":
             q = ops.axpby(q, pruned.gather_rows(relemb, r), 1.0, Q.side_alpha(s_))
-        loss = ops.softmax_all_loss(q, p, truth, distance=scoring != "dot", scale=scale, splits=splits)
+        exclude = None
+        if known is not None:
+            frel = r if scoring != "dot" else torch.full_like(r, -1)
+            exclude = ops.softmax_excluded(known.for_side(s_), ent, frel, truth, p.shape[0], pos)
+        loss = ops.softmax_all_loss(q, p, truth, distance=scoring != "dot", scale=scale, splits=splits, exclude=exclude)
         total = loss if total is None else total + loss
     return total if side != "both" else 0.5 * total
 
 
 def one_vs_all_loss(model, h: torch.Tensor, r: torch.Tensor, t: torch.Tensor, side: str = "tail", scale: float = 1.0,
-                    reduction: str = "mean", scoring: Optional[str] = None, splits: Optional[int] = None) -> torch.Tensor:
+                    reduction: str = "mean", scoring: Optional[str] = None, splits: Optional[int] = None,
+                    known=None, candidates: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The 1-vs-all loss of the triples (h, r, t) under the model (see the module docstring): side 'tail' / 'head' / 'both'
     (the mean of the two sides), scale > 0 a temperature on the logits, reduction 'mean' / 'sum' / 'none' (float32[B]),
     scoring 'transr' / 'transe' / 'dot' (default: model.scoring), splits the candidate splits of the forward kernel (None:
-    automatic; the last bits of the loss may depend on it, for a given value they repeat from run to run).
-    Differentiable in every parameter the table, the relation embeddings and (transr) gat_trans_M depend on."""
+    automatic; the last bits of the loss may depend on it, for a given value they repeat from run to run).  known: a
+    KnownTriples whose other answers of each query leave its softmax; candidates: the unique entity ids the softmax runs
+    over (one side only; every truth among them).  Differentiable in every parameter the table, the relation embeddings
+    and (transr) gat_trans_M depend on."""
     side = Q.check_side(side)
     scoring = Q.resolve_scoring(model, scoring, MLP_MESSAGE)
     reduction = check_reduction(reduction)
     scale, splits, _ = ops.check_softmax_args(scale, splits)
     Q.check_triple_lists(h, r, t)
     Q.check_transr_model(model, scoring)
+    Q.check_known_entities(known, model)
+    if candidates is not None:
+        Q.check_ids("candidates", candidates)
+        if side == "both":
+            raise ValueError("candidates restrict one side's answers: side must be 'tail' or 'head' with candidates, got "
+                             "'both'")
     dev = model.entity_embed.weight.device
     b = h.numel()
     if b == 0:
         return torch.zeros((0,) if reduction == "none" else (), dtype=torch.float32, device=dev)
     h, t = ops.checked_ids(model.n_entities, h.to(dev), t.to(dev))          # (out-of-range ids never reach a kernel)
     (r,) = ops.checked_ids(model.n_relations, r.to(dev), what="relation")
+    Q.check_known_device(known, dev)
+    cand = pos = None
+    if candidates is not None:                  # sorted: pos is increasing over the candidates, the bits ignore the order
+        (cand,) = ops.checked_ids(model.n_entities, candidates.to(dev), what="candidate entity")
+        ops.check_deferred_errors()
+        Q.check_unique(cand)
+        if cand.numel() == 0:
+            raise ValueError("candidates must hold at least one entity id")
+        cand = torch.sort(cand).values
+        pos = torch.full((model.n_entities,), -1, dtype=torch.int32, device=dev)
+        pos[cand] = torch.arange(cand.numel(), dtype=torch.int32, device=dev)
+        missing = int((pos[t if side == "tail" else h] < 0).sum())
+        if missing:
+            raise ValueError(f"{missing} of the {b} true {'tails' if side == 'tail' else 'heads'} are not among the "
+                             "candidates: every truth must be a candidate")
     model.device = dev
     table = model._table_for_inference()       # training or grad enabled: gat_embeddings() with its graph; else the kept table
     Q.check_table_shape(model, scoring, table)
-    relemb = model.relation_embed.weight
+    rows = table if cand is None else pruned.gather_rows(table, cand)      # gathered once for every relation group
     if scoring == "transr":
         perm, seg = ops.group_by_key(r, model.n_relations)
         perm, seg = perm.long(), seg.tolist()
         parts = []
         for rr in range(model.n_relations):
             if seg[rr + 1] > seg[rr]:
-                pos = perm[seg[rr]:seg[rr + 1]]
-                p_r = ops.matmul(table, model.gat_trans_M[rr])             # alive until the backward pass (N x relation_dim)
-                parts.append(_side_losses(scoring, side, p_r, relemb, h[pos], r[pos], t[pos], scale, splits))
+                at = perm[seg[rr]:seg[rr + 1]]
+                parts.append(_side_losses(model, scoring, side, table, rows, model.gat_trans_M[rr], h[at], r[at], t[at],
+                                          scale, splits, known, pos))
         back = torch.empty_like(perm)
         back[perm] = torch.arange(b, device=dev)
         loss = torch.cat(parts)[back]
     else:
-        loss = _side_losses(scoring, side, table, relemb, h, r, t, scale, splits)
+        loss = _side_losses(model, scoring, side, table, rows, None, h, r, t, scale, splits, known, pos)
     if reduction == "mean":
         return loss.mean()
     return loss.sum() if reduction == "sum" else loss

@@ -2958,14 +2958,66 @@ def _softmax_operands(what: str, q, p, truth, pn=None):
     return q, p, truth
 
 
+def softmax_excluded(filt, filter_row: torch.Tensor, filter_rel: torch.Tensor, truth: torch.Tensor, n_cand: int,
+                     pos: Optional[torch.Tensor] = None):
+    """(xptr int32[B + 1], xcol int32[M]): per query the ascending, duplicate-free candidate positions the filtered loss
+    drops (lkg_softmax_excluded: a count pass, a cumulative sum, a fill pass).  filt = (rowptr, col, eptr, rel) of
+    csr_build_device (KnownTriples.for_side); query i drops the cols of row filter_row[i] known under relation
+    filter_rel[i] (-1: under any relation) that are candidates and are not truth[i].  A candidate's position is pos[entity]
+    (pos int32[entities], -1 = not a candidate, increasing over the candidates), or the entity id itself without pos;
+    truth holds positions.  The truth is exempt, so the lists are the same whether or not the trained triples are known.
+    M must stay below 2^31 (ValueError).  Waits for the device once (M sizes xcol)."""
+    _need_gpu(*filt, filter_row, filter_rel, truth, pos)
+    row, rel, truth = _i64(filter_row.reshape(-1)), _i64(filter_rel.reshape(-1)), _i64(truth.reshape(-1))
+    b, n_rows, dev = row.numel(), filt[0].numel() - 1, row.device
+    if rel.numel() != b or truth.numel() != b:
+        raise ValueError(f"softmax_excluded: {b} filter rows, {rel.numel()} filter relations, {truth.numel()} truths")
+    if int(n_cand) <= 0 or n_rows <= 0:
+        raise ValueError(f"softmax_excluded: {n_cand} candidates, a filter over {n_rows} entities")
+    if pos is not None:
+        if pos.dtype != torch.int32 or pos.numel() != n_rows:
+            raise ValueError(f"softmax_excluded: pos must be int32[{n_rows}] (one position per entity of the filter)")
+        pos = pos.contiguous()
+    xptr = torch.zeros(b + 1, dtype=torch.int64, device=dev)
+    if b == 0:
+        return xptr.int(), torch.empty(0, dtype=torch.int32, device=dev)
+    cnt = torch.empty(b, dtype=torch.int32, device=dev)
+    fargs = [N.ptr(row), N.ptr(rel), N.ptr(truth), *map(N.ptr, filt), N.ptr(pos)]
+    N.call("lkg_softmax_excluded", b, n_rows, int(n_cand), *fargs, N.ptr(cnt), None, None, _stream())
+    torch.cumsum(cnt, 0, dtype=torch.int64, out=xptr[1:])
+    m = int(xptr[-1])
+    if m >= 2 ** 31:
+        raise ValueError(f"softmax_excluded: {m} excluded candidates in all, the lists hold fewer than 2^31 (fewer queries "
+                         "per call)")
+    xptr = xptr.int()
+    xcol = torch.empty(m, dtype=torch.int32, device=dev)
+    if m:
+        N.call("lkg_softmax_excluded", b, n_rows, int(n_cand), *fargs, None, N.ptr(xptr), N.ptr(xcol), _stream())
+    return xptr, xcol
+
+
+def _softmax_exclude(what: str, exclude, b: int):
+    """(xptr, xcol) of an ``exclude`` argument, checked: int32 device tensors, xptr with one entry per query and one more"""
+    xptr, xcol = exclude
+    _need_gpu(xptr, xcol)
+    if xptr.dtype != torch.int32 or xcol.dtype != torch.int32 or xptr.dim() != 1 or xcol.dim() != 1 or \
+            xptr.numel() != b + 1:
+        raise ValueError(f"{what}: exclude must be (xptr int32[{b + 1}], xcol int32[M]) as softmax_excluded returns them")
+    return xptr.contiguous(), xcol.contiguous()
+
+
 def softmax_all_forward(q: torch.Tensor, p: torch.Tensor, pn: Optional[torch.Tensor], truth: torch.Tensor,
-                        scale: float = 1.0, splits: Optional[int] = None):
+                        scale: float = 1.0, splits: Optional[int] = None, exclude=None):
     """(lse float32[2, B], loss float32[B]) of lkg_softmax_all_partial_f32 + lkg_softmax_all_finish_f32, no autograd: the
     logits are z = -scale (pn[c] - 2 q.p_c) with pn = rank_sqnorm(p), or scale q.p_c with pn None; lse[0] = logsumexp_c z
     rounded once, lse[1] what that rounding dropped (softmax_all_weights takes both), loss = logsumexp - z at truth.
-    truth outside [0, N) is clamped (callers hand in checked ids)."""
+    truth outside [0, N) is clamped (callers hand in checked ids).  exclude = (xptr, xcol) of softmax_excluded: query i
+    drops the candidates xcol[xptr[i] : xptr[i + 1]] before the running (max, sum) sees them
+    (lkg_softmax_all_partial_masked_f32); its truth must not be among them.  None: the unmasked launch."""
     q, p, truth = _softmax_operands("softmax_all_forward", q, p, truth, pn)
     scale, splits, _ = check_softmax_args(scale, splits)
+    if exclude is not None:
+        exclude = _softmax_exclude("softmax_all_forward", exclude, q.shape[0])
     (b, k), n, dev = q.shape, p.shape[0], q.device
     lse = torch.empty((2, b), dtype=torch.float32, device=dev)
     loss = torch.empty(b, dtype=torch.float32, device=dev)
@@ -2973,8 +3025,12 @@ def softmax_all_forward(q: torch.Tensor, p: torch.Tensor, pn: Optional[torch.Ten
         return lse, loss
     s_ = softmax_all_splits(b, n, splits)
     ws = torch.empty((2, s_, b), dtype=torch.float32, device=dev)
-    N.call("lkg_softmax_all_partial_f32", b, n, k, N.ptr(q), _ld(q), N.ptr(p), _ld(p), N.ptr(pn), scale, s_, N.ptr(ws[0]),
-           N.ptr(ws[1]), _stream())
+    if exclude is None:
+        N.call("lkg_softmax_all_partial_f32", b, n, k, N.ptr(q), _ld(q), N.ptr(p), _ld(p), N.ptr(pn), scale, s_,
+               N.ptr(ws[0]), N.ptr(ws[1]), _stream())
+    else:
+        N.call("lkg_softmax_all_partial_masked_f32", b, n, k, N.ptr(q), _ld(q), N.ptr(p), _ld(p), N.ptr(pn), scale, s_,
+               N.ptr(exclude[0]), N.ptr(exclude[1]), exclude[1].numel(), N.ptr(ws[0]), N.ptr(ws[1]), _stream())
     N.call("lkg_softmax_all_finish_f32", b, n, k, N.ptr(q), _ld(q), N.ptr(p), _ld(p), N.ptr(pn), N.ptr(truth), scale, s_,
            N.ptr(ws[0]), N.ptr(ws[1]), N.ptr(lse[0]), N.ptr(lse[1]), N.ptr(loss), _stream())
     return lse, loss
@@ -2982,11 +3038,14 @@ def softmax_all_forward(q: torch.Tensor, p: torch.Tensor, pn: Optional[torch.Ten
 
 def softmax_all_weights(q: torch.Tensor, p: torch.Tensor, pn: Optional[torch.Tensor], truth: torch.Tensor,
                         lse: torch.Tensor, g: torch.Tensor, scale: float = 1.0, c0: int = 0, c1: Optional[int] = None,
-                        out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                        out: Optional[torch.Tensor] = None, exclude=None) -> torch.Tensor:
     """V[:, c0:c1] of lkg_softmax_all_weights_f32 (B x (c1 - c0), into ``out`` when given, whose row stride is free):
     V[i, c] = scale beta g[i] (exp(z_ic - lse[i]) - [c == truth[i]]), beta = 1 with pn, 1/2 without.  lse: float32[2, B]
-    as softmax_all_forward returns it (the rounded value and its remainder), or float32[B] (no remainder)."""
+    as softmax_all_forward returns it (the rounded value and its remainder), or float32[B] (no remainder).  exclude as in
+    softmax_all_forward (positions of the whole table): a dropped candidate's weight is exactly 0."""
     q, p, truth = _softmax_operands("softmax_all_weights", q, p, truth, pn)
+    if exclude is not None:
+        exclude = _softmax_exclude("softmax_all_weights", exclude, q.shape[0])
     _need_gpu(lse, g, out)
     scale = check_softmax_args(scale, 0)[0]
     (b, k), n = q.shape, p.shape[0]
@@ -3005,9 +3064,13 @@ def softmax_all_weights(q: torch.Tensor, p: torch.Tensor, pn: Optional[torch.Ten
             (b > 1 and out.stride(0) < c1 - c0):
         raise ValueError(f"softmax_all_weights: out must be a float32 {b} x {c1 - c0} tensor with unit column stride")
     pc = p[c0:c1]
-    N.call("lkg_softmax_all_weights_f32", b, c1 - c0, k, N.ptr(q), _ld(q), N.ptr(pc), _ld(p), N.ptr(pn[c0:c1]) if pn is not None
-           else None, c0, N.ptr(truth), N.ptr(lse[0]), N.ptr(lse[1]) if lse.shape[0] == 2 else None, N.ptr(g), scale,
-           N.ptr(out), max(_ld(out), c1 - c0), _stream())
+    head = [b, c1 - c0, k, N.ptr(q), _ld(q), N.ptr(pc), _ld(p), N.ptr(pn[c0:c1]) if pn is not None else None, c0,
+            N.ptr(truth), N.ptr(lse[0]), N.ptr(lse[1]) if lse.shape[0] == 2 else None, N.ptr(g), scale]
+    if exclude is None:
+        N.call("lkg_softmax_all_weights_f32", *head, N.ptr(out), max(_ld(out), c1 - c0), _stream())
+    else:
+        N.call("lkg_softmax_all_weights_masked_f32", *head, N.ptr(exclude[0]), N.ptr(exclude[1]), exclude[1].numel(),
+               N.ptr(out), max(_ld(out), c1 - c0), _stream())
     return out
 
 
@@ -3016,27 +3079,30 @@ class _SoftmaxAllLoss(Function):
     per chunk of candidates the weights V (lkg_softmax_all_weights_f32), then dQ += 2 V P_chunk and dP_chunk = 2 V^T Q -
     2 diag(colsum V) P_chunk on ops.gemm.  Both products run with beta = 1 onto an initialised output: lkg_gemm_f32 splits
     a beta = 0 product with a long reduction over float atomics, whose sum changes from run to run; for the same reason
-    the column sums come out of the second product (a column of ones next to Q), not from ops.colsum."""
+    the column sums come out of the second product (a column of ones next to Q), not from ops.colsum.  With exclusion
+    lists (xptr, xcol) the masked kernels run instead: V has exact zeros at the dropped positions, the products are the same."""
 
     @staticmethod
-    def forward(ctx, q, p, truth, distance, scale, splits, chunk_bytes):
+    def forward(ctx, q, p, truth, distance, scale, splits, chunk_bytes, xptr=None, xcol=None):
         q_, p_, truth = _softmax_operands("softmax_all_loss", q, p, truth)
         pn = rank_sqnorm(p_) if distance else None
-        lse, loss = softmax_all_forward(q_, p_, pn, truth, scale, splits)
-        ctx.save_for_backward(q_, p_, pn, truth, lse)
+        exclude = (xptr, xcol) if xptr is not None else None
+        lse, loss = softmax_all_forward(q_, p_, pn, truth, scale, splits, exclude)
+        ctx.save_for_backward(q_, p_, pn, truth, lse, xptr, xcol)
         ctx.meta = (scale, chunk_bytes)
         return loss
 
     @staticmethod
     def backward(ctx, g):
-        q, p, pn, truth, lse = ctx.saved_tensors
+        q, p, pn, truth, lse, xptr, xcol = ctx.saved_tensors
+        exclude = (xptr, xcol) if xptr is not None else None
         scale, chunk_bytes = ctx.meta
         want_q, want_p = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         (b, k), n, dev = q.shape, p.shape[0], q.device
         dq = torch.zeros((b, k), dtype=torch.float32, device=dev) if want_q else None
         dp = torch.empty((n, k), dtype=torch.float32, device=dev) if want_p else None
         if b == 0:
-            return dq, dp.zero_() if want_p else None, None, None, None, None, None
+            return dq, dp.zero_() if want_p else None, None, None, None, None, None, None, None
         g = g.reshape(-1).float().contiguous()
         width = softmax_chunk_width(b, n, chunk_bytes)
         vbuf = torch.empty((b, width), dtype=torch.float32, device=dev)
@@ -3047,7 +3113,7 @@ class _SoftmaxAllLoss(Function):
             tmp = torch.empty((width, k + 1), dtype=torch.float32, device=dev)
         for c0 in range(0, n, width):                  # a fixed order: dQ accumulates slice after slice, chunk after chunk
             c1 = min(n, c0 + width)
-            v = softmax_all_weights(q, p, pn, truth, lse, g, scale, c0, c1, out=vbuf[:, :c1 - c0])
+            v = softmax_all_weights(q, p, pn, truth, lse, g, scale, c0, c1, out=vbuf[:, :c1 - c0], exclude=exclude)
             pc = p[c0:c1]
             if want_q:
                 for s0 in range(0, c1 - c0, SOFTMAX_DQ_SLICE):
@@ -3061,17 +3127,20 @@ class _SoftmaxAllLoss(Function):
                     torch.addcmul(t[:, :k], t[:, k:], pc, value=-1.0, out=dpc)
                 else:
                     gemm(v, q, trans_a=True, alpha=2.0, beta=1.0, out=dpc.zero_())
-        return dq, dp, None, None, None, None, None
+        return dq, dp, None, None, None, None, None, None, None
 
 
 def softmax_all_loss(q: torch.Tensor, p: torch.Tensor, truth: torch.Tensor, distance: bool = True, scale: float = 1.0,
-                     splits: Optional[int] = None, chunk_bytes: int = SOFTMAX_CHUNK_BYTES) -> torch.Tensor:
+                     splits: Optional[int] = None, chunk_bytes: int = SOFTMAX_CHUNK_BYTES, exclude=None) -> torch.Tensor:
     """float32[B]: the cross-entropy of truth[i] against the softmax over ALL N rows of p for query row q[i] (1-vs-all).
     distance True: logits z = -scale ||q - p_c||^2 (||q||^2 cancels; ||p_c||^2 is computed here, so the gradient of p is
     complete); False: z = scale q.p_c.  Differentiable in q and p; the gradient of p is a dense N x k table (no RowSet
     tag: every row is reached).  splits: candidate splits of the forward pass (None: automatic) -- the last bits of the
     loss may depend on it, for a given value they do not change from run to run.  chunk_bytes bounds the backward's B x Nc
-    weights.  No L2 term: weight decay belongs to the optimizer (lkg_adam_step_f32)."""
+    weights.  No L2 term: weight decay belongs to the optimizer (lkg_adam_step_f32).  exclude = (xptr, xcol) of
+    softmax_excluded: row i's softmax runs over the candidates NOT in xcol[xptr[i] : xptr[i + 1]] (the filtered loss; the
+    truth must not be listed) and those rows of p get no gradient from row i.  None: the unfiltered launches, bit for bit."""
     _need_gpu(q, p, truth)
     scale, splits, chunk_bytes = check_softmax_args(scale, splits, chunk_bytes)
-    return _SoftmaxAllLoss.apply(q, p, truth, bool(distance), scale, splits, chunk_bytes)
+    xptr, xcol = _softmax_exclude("softmax_all_loss", exclude, truth.numel()) if exclude is not None else (None, None)
+    return _SoftmaxAllLoss.apply(q, p, truth, bool(distance), scale, splits, chunk_bytes, xptr, xcol)
