@@ -1662,7 +1662,8 @@ class _FusedGate(Function):
     the result written straight into ``out`` (a column slot of the concatenated table).  Inputs are read once; for the
     backward only tanh(g) and sigmoid(z) are kept.
     Backward: one blend kernel (g_x direct term, g_gpre, g_zpre side by side), ONE tall GEMM for the data gradient
-    [g_gpre | g_zpre] . [W_g[:, :d] ; W_e] accumulated onto the direct term, the weight gradients as long-k products."""
+    [g_gpre | g_zpre] . [W_g[:, :d] ; W_e] accumulated onto the direct term, the weight gradients as long-k products.  A literal
+    table that requires a gradient (the model's are constants) gets [g_gpre | g_zpre] . [W_g's panel ; gate_*_lit.weight]."""
 
     @staticmethod
     def forward(ctx, out, bg, bz, n_lit, grad_mode, x, *rest):
@@ -1768,7 +1769,10 @@ class _FusedGate(Function):
         g_wz = [gws[i][d:] if need[base + nl + 1 + i] else None for i in range(nl + 1)]
         gb_g = gb[:d] if (gb is not None and need[1]) else None
         gb_z = gb[d:] if (gb is not None and need[2]) else None
-        return (None, gb_g, gb_z, None, None, g_x, *([None] * nl), *g_wg, *g_wz)
+        # a literal table that requires a gradient (a trainable table; the model's are constants): g_gpre wg_i + g_zpre wz_i,
+        # one [n, 2d] x [2d, k_i] product over the side-by-side buffer
+        g_lits = [gemm(gpz, torch.cat((wgs[i + 1], wzs[i + 1]), 0)) if need[6 + i] else None for i in range(nl)]
+        return (None, gb_g, gb_z, None, None, g_x, *g_lits, *g_wg, *g_wz)
 
 
 def _fused_gate_backward_on_rows(ctx, go, rows: RowSet, x, g, z, lits, wgs, wzs):
@@ -1804,7 +1808,17 @@ def _fused_gate_backward_on_rows(ctx, go, rows: RowSet, x, g, z, lits, wgs, wzs)
     g_wz = [gws[i][d:] if need[base + nl + 1 + i] else None for i in range(nl + 1)]
     gb_g = gb[:d] if (gb is not None and need[1]) else None
     gb_z = gb[d:] if (gb is not None and need[2]) else None
-    return (None, gb_g, gb_z, None, None, g_x, *([None] * nl), *g_wg, *g_wz)
+    g_lits = []
+    for i in range(nl):                   # trainable literal tables: the same product on the listed rows, scattered like g_x
+        if not need[6 + i]:
+            g_lits.append(None)
+            continue
+        k_i = lits[i].shape[1]
+        g_lit = zero_table_for(rows, n, k_i, x.device, f"g_gate_lit{i}")
+        N.call("lkg_scatter_add_rows_range_f32", nc, k_i, N.ptr(gemm(gpz, torch.cat((wgs[i + 1], wzs[i + 1]), 0))), k_i, N.ptr(ids),
+               0, n, N.ptr(g_lit), _ld(g_lit), _stream())
+        g_lits.append(g_lit)
+    return (None, gb_g, gb_z, None, None, g_x, *g_lits, *g_wg, *g_wz)
 
 
 _FusedGate._backward_on_rows = staticmethod(_fused_gate_backward_on_rows)
