@@ -21,7 +21,7 @@ import __graft_entry__ as ge  # noqa: E402
 
 ge.build()
 from literalkg_amd import LiteralKG                      # noqa: E402  (the one-line change vs `from model import LiteralKG`)
-from literalkg_amd import KnownTriples                   # noqa: E402  (--filtered)
+from literalkg_amd import KnownTriples, distinct_queries   # noqa: E402  (--filtered, --objective kvs_all)
 from literalkg_amd.synth import make_batch, make_kg      # noqa: E402
 
 
@@ -45,10 +45,15 @@ def main():
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--batch-groups", type=int, default=683)
     ap.add_argument("--lr", type=float, default=1e-4)
-    ap.add_argument("--objective", choices=("sampled", "one_vs_all"), default="sampled",
+    ap.add_argument("--objective", choices=("sampled", "one_vs_all", "kvs_all"), default="sampled",
                     help="sampled: the reference's loss over pre_training_neg_rate sampled negatives (mode='pre_training'); "
                          "one_vs_all: cross-entropy of the true tail against the softmax over every entity "
-                         "(mode='one_vs_all'; the sampled negatives of the batch are not used)")
+                         "(mode='one_vs_all'; the sampled negatives of the batch are not used); "
+                         "kvs_all: one row per DISTINCT query (h, r, ?) of the batch against every entity, binary "
+                         "cross-entropy against all its known tails among the training triples (calc_kvs_all_loss)")
+    ap.add_argument("--label-smoothing", type=float, default=0.1, help="with --objective kvs_all")
+    ap.add_argument("--margin", type=float, default=8.0,
+                    help="with --objective kvs_all: the logits are margin - ||q - p||^2")
     ap.add_argument("--filtered", action="store_true",
                     help="with --objective one_vs_all: the other known tails of (h, r, ?) among the training triples leave "
                          "the row's softmax (calc_one_vs_all_loss(known=...)), as filtered MRR drops them")
@@ -70,7 +75,8 @@ def main():
     model.to(device)
     h_list, t_list, r_list = (torch.from_numpy(x).to(device) for x in (h, t, r))
     relations = list(range(16))
-    known = KnownTriples(h_list, r_list, t_list, a.entities, 16) if a.filtered else None
+    need_known = a.filtered or a.objective == "kvs_all"
+    known = KnownTriples(h_list, r_list, t_list, a.entities, 16) if need_known else None
     for epoch in range(1, a.epochs + 1):
         model.train()
         t0, total = time.time(), 0.0
@@ -78,7 +84,10 @@ def main():
             bh, br, bp, bn = (torch.from_numpy(x).to(device)
                               for x in make_batch(a.entities, a.batch_groups, 3, seed=epoch * 10_000 + it))
             optimizer.zero_grad()
-            if a.filtered:
+            if a.objective == "kvs_all":
+                ent, rel = distinct_queries(bh[::3], br[::3])
+                loss = model.calc_kvs_all_loss(ent, rel, known, margin=a.margin, label_smoothing=a.label_smoothing)
+            elif a.filtered:
                 loss = model.calc_one_vs_all_loss(bh[::3], br[::3], bp[::3], known=known)
             elif a.objective == "one_vs_all":
                 loss = model(bh[::3], br[::3], bp[::3], device=device, mode="one_vs_all")   # one triple per group

@@ -21,10 +21,12 @@ from .triples import (TripleThresholds, evaluate_triple_classification, fit_trip
 from .relations import (RelationTopK, evaluate_relation_prediction, predict_relations, rank_relations,   # noqa: F401
                         score_relations)
 from .one_vs_all import one_vs_all_loss   # noqa: F401
+from .kvs_all import distinct_queries, kvs_all_loss, sigmoid_all_loss   # noqa: F401
 
 __all__ = ["LiteralKG", "Aggregator", "Gate", "GateMul", "KGStructure", "KnownTriples", "RankResult", "evaluate_ranking",
            "TopKResult", "predict_topk", "FoldedMLPHead", "fold_mlp_head", "mlp_scores", "rank_pairs_mlp",
            "evaluate_mlp_ranking", "score_pairs_mlp", "evaluate_mlp_classification", "TripleThresholds", "score_triples",
            "fit_triple_thresholds", "evaluate_triple_classification", "RelationTopK", "score_relations", "rank_relations",
            "predict_relations", "evaluate_relation_prediction", "AcceptedResult", "predict_accepted", "count_accepted",
-           "AnswerRanks", "rank_answers", "evaluate_retrieval", "one_vs_all_loss"]
+           "AnswerRanks", "rank_answers", "evaluate_retrieval", "one_vs_all_loss", "kvs_all_loss",
+           "sigmoid_all_loss", "distinct_queries"]

@@ -133,6 +133,14 @@ PROTOTYPES = {
     "lkg_softmax_all_weights_masked_f32": [i64, i64, i32, vp, i64, vp, i64, vp, i64, vp, vp, vp, vp, f32, vp, vp, i64, vp,
                                            i64, vp],
 }
+# the second table: include/literalkg_hip_ext.h, mirrored the same way (load() types both)
+f64 = C.c_double
+EXTRA_PROTOTYPES = {
+    "lkg_sigmoid_all_partial_f32": [i64, i64, i32, vp, i64, vp, i64, vp, vp, f32, f64, i32, vp, vp, i64, vp, vp],
+    "lkg_sigmoid_all_finish_f32": [i64, i32, vp, vp, vp],
+    "lkg_sigmoid_all_weights_f32": [i64, i64, i32, vp, i64, vp, i64, vp, vp, i64, i64, vp, f32, f64, vp, vp, i64, vp, i64,
+                                    vp, vp],
+}
 _RESTYPE = {"lkg_last_error": C.c_char_p, "lkg_csr_build_device_workspace": C.c_int64,
             "lkg_gemm_tall_workspace": C.c_int64, "lkg_gemm_workspace": C.c_int64,
             "lkg_linear_act_layernorm_workspace": C.c_int64, "lkg_narrow_layer_bwd_workspace": C.c_int64,
@@ -159,7 +167,7 @@ def load():
             "`python -c 'import __graft_entry__ as g; g.build()'` (or `python -m literalkg_amd.build`). "
             "literalkg_amd has no CPU fallback.")
     lib = C.CDLL(_LIB_PATH)
-    for name, argtypes in PROTOTYPES.items():
+    for name, argtypes in list(PROTOTYPES.items()) + list(EXTRA_PROTOTYPES.items()):
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
         fn.argtypes = argtypes
         fn.restype = _RESTYPE.get(name, C.c_int)

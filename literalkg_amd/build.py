@@ -16,13 +16,13 @@ OBJ = os.path.join(HERE, "lib", "obj")
 SOURCES = ["lkg_graph_host.cpp", "lkg_spmm.hip", "lkg_attention.hip", "lkg_score.hip", "lkg_rowwise.hip",
            "lkg_gemm.hip", "lkg_batch.hip", "lkg_csr_device.hip", "lkg_gemm_tall.hip", "lkg_gemm_wgrad.hip", "lkg_layer.hip",
            "lkg_rank.hip", "lkg_topk.hip", "lkg_pairmlp.hip", "lkg_triples.hip", "lkg_relations.hip",
-           "lkg_accept.hip", "lkg_retrieval.hip", "lkg_softmax.hip"]
+           "lkg_accept.hip", "lkg_retrieval.hip", "lkg_softmax.hip", "lkg_kvsall.hip"]
 FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17"]
 
 
 def _headers():
     return [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith(".h")] + \
-           [os.path.join(HERE, "..", "include", "literalkg_hip.h")]
+           [os.path.join(HERE, "..", "include", h) for h in ("literalkg_hip.h", "literalkg_hip_ext.h")]
 
 
 TAG_FILE = os.path.join(HERE, "lib", "flags.tag")
@@ -34,7 +34,7 @@ def _stale(tag):
     if os.path.exists(TAG_FILE) and open(TAG_FILE).read().strip() != tag:     # linked from objects of other flags
         return True
     t = os.path.getmtime(LIB)
-    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(HERE, "..", "include", "literalkg_hip.h")]
+    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + _headers()
     return any(os.path.getmtime(d) > t for d in deps)
 
 

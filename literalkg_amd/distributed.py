@@ -622,6 +622,10 @@ class ShardedLiteralKG(nn.Module):
         # pre_training / fine_tuning / predict / mlp: the module's own code over the gathered rows (unknown modes: None)
         return self.local(*input, device=device, mode=mode)
 
+    def calc_kvs_all_loss(self, *args, **kwargs):
+        from .kvs_all import SHARDED_MESSAGE
+        raise NotImplementedError(SHARDED_MESSAGE)
+
     # ------------------------------------------------------------------ gradients / checkpoints
     def partial_grad_parameters(self) -> List[nn.Parameter]:
         """Replicated weights whose gradient is a partial sum over this rank's rows (a FIXED list: the same on every rank

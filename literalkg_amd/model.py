@@ -573,6 +573,18 @@ class LiteralKG(nn.Module):
         return one_vs_all_loss(self, h, r, t, side=side, scale=scale, reduction=reduction, scoring=scoring, splits=splits,
                                known=known, candidates=candidates)
 
+    def calc_kvs_all_loss(self, ent, r, known, side: str = "tail", margin: float = 0.0, scale: float = 1.0,
+                          label_smoothing: float = 0.0, reduction: str = "mean", scoring: Optional[str] = None,
+                          splits: Optional[int] = None, candidates=None):
+        """KvsAll training loss of the queries (ent, r) (literalkg_amd/kvs_all.py): one row per query scored against EVERY
+        entity, binary cross-entropy with logits against the multi-hot vector of the query's answers in known (a
+        KnownTriples), summed over the candidates; side 'tail' ((ent, r, ?)) or 'head' ((?, r, ent)), logits
+        scale (margin - ||q - p||^2) ('dot': scale (margin + q.p)), optional label smoothing.  Always on the full table of
+        the step (prune_to_batch does not apply).  There is no mode= string for it."""
+        from .kvs_all import kvs_all_loss
+        return kvs_all_loss(self, ent, r, known, side=side, margin=margin, scale=scale, label_smoothing=label_smoothing,
+                            reduction=reduction, scoring=scoring, splits=splits, candidates=candidates)
+
     def _rows_only_projection_applies(self) -> bool:
         """A loss that reads a few rows of linear_gat's output and has to run the encoder anyway (a training step, or any call
         with autograd on: the inference heads' kept table is for eval mode under no_grad)."""

@@ -22,8 +22,9 @@ apply them).  ``candidates`` (unique entity ids, sorted internally: the result h
 the softmax to those rows -- type-constrained training; one side at a time, every truth must be a candidate, the table's
 gradient reaches only candidate and query rows, and 'transr' projects the gathered rows, not the N-row table.
 
-There is no L2 term (lkg_adam_step_f32 carries weight decay), no label smoothing (its extra term eps (z_t - mean z) has a
-closed form in column sums and would bring its own accuracy contract) and no multi-hot (KvsAll) targets.  Under
+There is no L2 term (lkg_adam_step_f32 carries weight decay) and no label smoothing of the softmax (its extra term
+eps (z_t - mean z) has a closed form in column sums and would bring its own accuracy contract); multi-hot (KvsAll) targets,
+with label smoothing of their own, are literalkg_amd/kvs_all.py.  Under
 ``torch.no_grad()`` in eval mode the table is the cached inference table and ``reduction='none'`` gives the per-triple
 negative log-likelihood.
 """
