@@ -22,6 +22,7 @@ import __graft_entry__ as ge  # noqa: E402
 ge.build()
 from literalkg_amd import LiteralKG                      # noqa: E402  (the one-line change vs `from model import LiteralKG`)
 from literalkg_amd import KnownTriples, distinct_queries   # noqa: E402  (--filtered, --objective kvs_all)
+from literalkg_amd import group_sampled_batch            # noqa: E402  (--objective self_adversarial)
 from literalkg_amd.synth import make_batch, make_kg      # noqa: E402
 
 
@@ -45,15 +46,21 @@ def main():
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--batch-groups", type=int, default=683)
     ap.add_argument("--lr", type=float, default=1e-4)
-    ap.add_argument("--objective", choices=("sampled", "one_vs_all", "kvs_all"), default="sampled",
+    ap.add_argument("--objective", choices=("sampled", "one_vs_all", "kvs_all", "self_adversarial"), default="sampled",
                     help="sampled: the reference's loss over pre_training_neg_rate sampled negatives (mode='pre_training'); "
                          "one_vs_all: cross-entropy of the true tail against the softmax over every entity "
                          "(mode='one_vs_all'; the sampled negatives of the batch are not used); "
                          "kvs_all: one row per DISTINCT query (h, r, ?) of the batch against every entity, binary "
-                         "cross-entropy against all its known tails among the training triples (calc_kvs_all_loss)")
+                         "cross-entropy against all its known tails among the training triples (calc_kvs_all_loss); "
+                         "self_adversarial: each positive against its --neg-rate sampled negatives, weighted by the model's "
+                         "own softmax over the group at --temperature (calc_self_adversarial_loss)")
+    ap.add_argument("--neg-rate", type=int, default=3, help="sampled negatives per positive (the reference's "
+                                                            "pre_training_neg_rate)")
+    ap.add_argument("--temperature", type=float, default=1.0,
+                    help="with --objective self_adversarial: the weights are softmax(temperature * logits); 0: uniform")
     ap.add_argument("--label-smoothing", type=float, default=0.1, help="with --objective kvs_all")
     ap.add_argument("--margin", type=float, default=8.0,
-                    help="with --objective kvs_all: the logits are margin - ||q - p||^2")
+                    help="with --objective kvs_all or self_adversarial: the logits are margin - ||q - p||^2")
     ap.add_argument("--filtered", action="store_true",
                     help="with --objective one_vs_all: the other known tails of (h, r, ?) among the training triples leave "
                          "the row's softmax (calc_one_vs_all_loss(known=...)), as filtered MRR drops them")
@@ -64,7 +71,7 @@ def main():
     args = SimpleNamespace(use_pretrain=0, device=device, embed_dim=a.dim, relation_dim=a.dim, scale_gat_dim=None,
                            use_residual=False, alpha=0.1, lamda=0.5, aggregation_type="gcn", n_conv_layers=a.layers,
                            conv_dim=a.dim, mess_dropout=0.1, kg_l2loss_lambda=1e-5, fine_tuning_l2loss_lambda=1e-5,
-                           pre_training_neg_rate=3, fine_tuning_neg_rate=3, num_lit_dim=2, txt_lit_dim=300,
+                           pre_training_neg_rate=a.neg_rate, fine_tuning_neg_rate=3, num_lit_dim=2, txt_lit_dim=300,
                            use_num_lit=True, use_txt_lit=False, milestone_score=0.5, n_mlp_layers=2,
                            mlp_hidden_dim=64)
     torch.manual_seed(2022)
@@ -82,15 +89,19 @@ def main():
         t0, total = time.time(), 0.0
         for it in range(a.iters):
             bh, br, bp, bn = (torch.from_numpy(x).to(device)
-                              for x in make_batch(a.entities, a.batch_groups, 3, seed=epoch * 10_000 + it))
+                              for x in make_batch(a.entities, a.batch_groups, a.neg_rate, seed=epoch * 10_000 + it))
             optimizer.zero_grad()
-            if a.objective == "kvs_all":
-                ent, rel = distinct_queries(bh[::3], br[::3])
+            k = a.neg_rate
+            if a.objective == "self_adversarial":
+                loss = model.calc_self_adversarial_loss(*group_sampled_batch(bh, br, bp, bn, k), margin=a.margin,
+                                                        temperature=a.temperature)
+            elif a.objective == "kvs_all":
+                ent, rel = distinct_queries(bh[::k], br[::k])
                 loss = model.calc_kvs_all_loss(ent, rel, known, margin=a.margin, label_smoothing=a.label_smoothing)
             elif a.filtered:
-                loss = model.calc_one_vs_all_loss(bh[::3], br[::3], bp[::3], known=known)
+                loss = model.calc_one_vs_all_loss(bh[::k], br[::k], bp[::k], known=known)
             elif a.objective == "one_vs_all":
-                loss = model(bh[::3], br[::3], bp[::3], device=device, mode="one_vs_all")   # one triple per group
+                loss = model(bh[::k], br[::k], bp[::k], device=device, mode="one_vs_all")   # one triple per group
             else:
                 loss = model(bh, br, bp, bn, device=device, mode="pre_training")
             if np.isnan(loss.cpu().detach().numpy()):

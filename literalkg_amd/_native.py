@@ -141,6 +141,11 @@ EXTRA_PROTOTYPES = {
     "lkg_sigmoid_all_weights_f32": [i64, i64, i32, vp, i64, vp, i64, vp, vp, i64, i64, vp, f32, f64, vp, vp, i64, vp, i64,
                                     vp, vp],
 }
+# the third table: include/literalkg_hip_train.h (training objectives on sampled rows), mirrored the same way
+TRAIN_PROTOTYPES = {
+    "lkg_nssa_fwd_f32": [i64, i64, i32, vp, i64, vp, i64, vp, i64, i32, f32, f32, f32, vp, vp, vp, vp, vp],
+    "lkg_nssa_bwd_f32": [i64, i64, i32, vp, i64, vp, i64, vp, i64, i32, f32, vp, vp, vp, vp, vp, i64, vp, i64, vp, i64, vp],
+}
 _RESTYPE = {"lkg_last_error": C.c_char_p, "lkg_csr_build_device_workspace": C.c_int64,
             "lkg_gemm_tall_workspace": C.c_int64, "lkg_gemm_workspace": C.c_int64,
             "lkg_linear_act_layernorm_workspace": C.c_int64, "lkg_narrow_layer_bwd_workspace": C.c_int64,
@@ -167,7 +172,7 @@ def load():
             "`python -c 'import __graft_entry__ as g; g.build()'` (or `python -m literalkg_amd.build`). "
             "literalkg_amd has no CPU fallback.")
     lib = C.CDLL(_LIB_PATH)
-    for name, argtypes in list(PROTOTYPES.items()) + list(EXTRA_PROTOTYPES.items()):
+    for name, argtypes in list(PROTOTYPES.items()) + list(EXTRA_PROTOTYPES.items()) + list(TRAIN_PROTOTYPES.items()):
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
         fn.argtypes = argtypes
         fn.restype = _RESTYPE.get(name, C.c_int)

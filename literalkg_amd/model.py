@@ -585,6 +585,17 @@ class LiteralKG(nn.Module):
         return kvs_all_loss(self, ent, r, known, side=side, margin=margin, scale=scale, label_smoothing=label_smoothing,
                             reduction=reduction, scoring=scoring, splits=splits, candidates=candidates)
 
+    def calc_self_adversarial_loss(self, h, r, t, neg, side: str = "tail", margin: float = 0.0, scale: float = 1.0,
+                                   temperature: float = 1.0, reduction: str = "mean", scoring: Optional[str] = None):
+        """Self-adversarial negative-sampling loss of the triples (h, r, t) against their K sampled negatives neg[G, K]
+        (literalkg_amd/self_adversarial.py): softplus(-z+) + sum_j w_j softplus(z_j) with the logits
+        scale (margin - ||q - x||^2) ('dot': scale (margin + q.x)) and the constant weights softmax_j(temperature z_j);
+        side 'tail' (the negatives replace the tail) or 'head'.  Reads only the (2 + K) G rows it scores, so
+        prune_to_batch applies; no L2 term.  There is no mode= string for it."""
+        from .self_adversarial import self_adversarial_loss
+        return self_adversarial_loss(self, h, r, t, neg, side=side, margin=margin, scale=scale, temperature=temperature,
+                                     reduction=reduction, scoring=scoring)
+
     def _rows_only_projection_applies(self) -> bool:
         """A loss that reads a few rows of linear_gat's output and has to run the encoder anyway (a training step, or any call
         with autograd on: the inference heads' kept table is for eval mode under no_grad)."""
