@@ -23,6 +23,7 @@ ge.build()
 from literalkg_amd import LiteralKG                      # noqa: E402  (the one-line change vs `from model import LiteralKG`)
 from literalkg_amd import KnownTriples, distinct_queries   # noqa: E402  (--filtered, --objective kvs_all)
 from literalkg_amd import group_sampled_batch            # noqa: E402  (--objective self_adversarial)
+from literalkg_amd import NegativeSampler, TripleEpoch, subsampling_weights   # noqa: E402  (--sampler triples)
 from literalkg_amd.synth import make_batch, make_kg      # noqa: E402
 
 
@@ -64,9 +65,23 @@ def main():
     ap.add_argument("--filtered", action="store_true",
                     help="with --objective one_vs_all: the other known tails of (h, r, ?) among the training triples leave "
                          "the row's softmax (calc_one_vs_all_loss(known=...)), as filtered MRR drops them")
+    ap.add_argument("--sampler", choices=("batch", "triples"), default="batch",
+                    help="batch: the synthetic generate_kg_batch stand-in (tail negatives, made on the host); triples: with "
+                         "--objective self_adversarial, an epoch over the shuffled training triples (TripleEpoch) with the "
+                         "negatives drawn on the device (NegativeSampler, calc_sampled_negative_loss)")
+    ap.add_argument("--corrupt", choices=("tail", "head", "both", "bernoulli"), default="tail",
+                    help="with --sampler triples: the side the negatives replace")
+    ap.add_argument("--filter-negatives", action="store_true",
+                    help="with --sampler triples: reject a negative that forms a training triple")
+    ap.add_argument("--subsampling", action="store_true",
+                    help="with --sampler triples: weight every triple by 1 / sqrt(4 + its known tails + its known heads)")
     a = ap.parse_args()
     if a.filtered and a.objective != "one_vs_all":
         ap.error("--filtered goes with --objective one_vs_all")
+    if a.sampler == "triples" and a.objective != "self_adversarial":
+        ap.error("--sampler triples goes with --objective self_adversarial")
+    if a.sampler != "triples" and (a.corrupt != "tail" or a.filter_negatives or a.subsampling):
+        ap.error("--corrupt, --filter-negatives and --subsampling go with --sampler triples")
     device = torch.device("cuda:0")
     args = SimpleNamespace(use_pretrain=0, device=device, embed_dim=a.dim, relation_dim=a.dim, scale_gat_dim=None,
                            use_residual=False, alpha=0.1, lamda=0.5, aggregation_type="gcn", n_conv_layers=a.layers,
@@ -82,17 +97,29 @@ def main():
     model.to(device)
     h_list, t_list, r_list = (torch.from_numpy(x).to(device) for x in (h, t, r))
     relations = list(range(16))
-    need_known = a.filtered or a.objective == "kvs_all"
+    need_known = a.filtered or a.objective == "kvs_all" or a.filter_negatives or a.subsampling or a.corrupt == "bernoulli"
     known = KnownTriples(h_list, r_list, t_list, a.entities, 16) if need_known else None
+    sampler = None
+    if a.sampler == "triples":
+        sampler = NegativeSampler(a.entities, known, corrupt=a.corrupt, filtered=a.filter_negatives)
     for epoch in range(1, a.epochs + 1):
         model.train()
         t0, total = time.time(), 0.0
+        batches = iter(TripleEpoch(h_list, r_list, t_list, a.batch_groups, seed=epoch)) if sampler is not None else None
         for it in range(a.iters):
-            bh, br, bp, bn = (torch.from_numpy(x).to(device)
-                              for x in make_batch(a.entities, a.batch_groups, a.neg_rate, seed=epoch * 10_000 + it))
-            optimizer.zero_grad()
             k = a.neg_rate
-            if a.objective == "self_adversarial":
+            if sampler is not None:
+                bh, br, bp, offset = next(batches)
+                batch = sampler.sample(bh, br, bp, k, seed=epoch, group_offset=offset)
+                weights = subsampling_weights(known, bh, br, bp) if a.subsampling else None
+            else:
+                bh, br, bp, bn = (torch.from_numpy(x).to(device)
+                                  for x in make_batch(a.entities, a.batch_groups, a.neg_rate, seed=epoch * 10_000 + it))
+            optimizer.zero_grad()
+            if sampler is not None:
+                loss = model.calc_sampled_negative_loss(bh, br, bp, batch, weights=weights, margin=a.margin,
+                                                        temperature=a.temperature)
+            elif a.objective == "self_adversarial":
                 loss = model.calc_self_adversarial_loss(*group_sampled_batch(bh, br, bp, bn, k), margin=a.margin,
                                                         temperature=a.temperature)
             elif a.objective == "kvs_all":

@@ -23,6 +23,8 @@ from .relations import (RelationTopK, evaluate_relation_prediction, predict_rela
 from .one_vs_all import one_vs_all_loss   # noqa: F401
 from .kvs_all import distinct_queries, kvs_all_loss, sigmoid_all_loss   # noqa: F401
 from .self_adversarial import group_sampled_batch, sampled_sigmoid_loss, self_adversarial_loss   # noqa: F401
+from .negatives import (NegativeBatch, NegativeSampler, RelationCardinalities, TripleEpoch, answer_counts,   # noqa: F401
+                        relation_cardinalities, sampled_negative_loss, subsampling_weights)
 
 __all__ = ["LiteralKG", "Aggregator", "Gate", "GateMul", "KGStructure", "KnownTriples", "RankResult", "evaluate_ranking",
            "TopKResult", "predict_topk", "FoldedMLPHead", "fold_mlp_head", "mlp_scores", "rank_pairs_mlp",
@@ -30,4 +32,6 @@ __all__ = ["LiteralKG", "Aggregator", "Gate", "GateMul", "KGStructure", "KnownTr
            "fit_triple_thresholds", "evaluate_triple_classification", "RelationTopK", "score_relations", "rank_relations",
            "predict_relations", "evaluate_relation_prediction", "AcceptedResult", "predict_accepted", "count_accepted",
            "AnswerRanks", "rank_answers", "evaluate_retrieval", "one_vs_all_loss", "kvs_all_loss",
-           "sigmoid_all_loss", "distinct_queries", "self_adversarial_loss", "sampled_sigmoid_loss", "group_sampled_batch"]
+           "sigmoid_all_loss", "distinct_queries", "self_adversarial_loss", "sampled_sigmoid_loss", "group_sampled_batch",
+           "NegativeSampler", "NegativeBatch", "TripleEpoch", "RelationCardinalities", "relation_cardinalities",
+           "answer_counts", "subsampling_weights", "sampled_negative_loss"]

@@ -146,6 +146,13 @@ TRAIN_PROTOTYPES = {
     "lkg_nssa_fwd_f32": [i64, i64, i32, vp, i64, vp, i64, vp, i64, i32, f32, f32, f32, vp, vp, vp, vp, vp],
     "lkg_nssa_bwd_f32": [i64, i64, i32, vp, i64, vp, i64, vp, i64, i32, f32, vp, vp, vp, vp, vp, i64, vp, i64, vp, i64, vp],
 }
+# the fourth table: include/literalkg_hip_sample.h (negative sampling for given positives), mirrored the same way
+SAMPLE_PROTOTYPES = {
+    "lkg_sample_negatives": [i64, i64, u64, i64, vp, vp, vp, i64, i64, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                             vp, i64, vp, i64, vp, vp, vp, vp],
+    "lkg_relation_cardinality": [i64, i64, i64, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp],
+    "lkg_answer_counts": [i64, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+}
 _RESTYPE = {"lkg_last_error": C.c_char_p, "lkg_csr_build_device_workspace": C.c_int64,
             "lkg_gemm_tall_workspace": C.c_int64, "lkg_gemm_workspace": C.c_int64,
             "lkg_linear_act_layernorm_workspace": C.c_int64, "lkg_narrow_layer_bwd_workspace": C.c_int64,
@@ -172,7 +179,8 @@ def load():
             "`python -c 'import __graft_entry__ as g; g.build()'` (or `python -m literalkg_amd.build`). "
             "literalkg_amd has no CPU fallback.")
     lib = C.CDLL(_LIB_PATH)
-    for name, argtypes in list(PROTOTYPES.items()) + list(EXTRA_PROTOTYPES.items()) + list(TRAIN_PROTOTYPES.items()):
+    for name, argtypes in list(PROTOTYPES.items()) + list(EXTRA_PROTOTYPES.items()) + list(TRAIN_PROTOTYPES.items()) + \
+            list(SAMPLE_PROTOTYPES.items()):
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
         fn.argtypes = argtypes
         fn.restype = _RESTYPE.get(name, C.c_int)

@@ -596,6 +596,16 @@ class LiteralKG(nn.Module):
         return self_adversarial_loss(self, h, r, t, neg, side=side, margin=margin, scale=scale, temperature=temperature,
                                      reduction=reduction, scoring=scoring)
 
+    def calc_sampled_negative_loss(self, h, r, t, batch, weights=None, margin: float = 0.0, scale: float = 1.0,
+                                   temperature: float = 1.0, reduction: str = "mean", scoring: Optional[str] = None):
+        """The self-adversarial loss of the triples (h, r, t) against a NegativeBatch of NegativeSampler.sample, whose groups
+        may be corrupted on either side (literalkg_amd/negatives.py): each side's groups scored as
+        calc_self_adversarial_loss scores them alone (one table for both), the per-group losses back in group order,
+        weighted by ``weights`` (e.g. subsampling_weights): 'mean' is sum(w L) / sum(w)."""
+        from .negatives import sampled_negative_loss
+        return sampled_negative_loss(self, h, r, t, batch, weights=weights, margin=margin, scale=scale,
+                                     temperature=temperature, reduction=reduction, scoring=scoring)
+
     def _rows_only_projection_applies(self) -> bool:
         """A loss that reads a few rows of linear_gat's output and has to run the encoder anyway (a training step, or any call
         with autograd on: the inference heads' kept table is for eval mode under no_grad)."""

@@ -148,36 +148,10 @@ def _group_losses(scoring: str, side: str, w, rows, gr: int, e, margin, scale, t
     return sampled_sigmoid_loss(q, p, n, distance=distance, margin=margin, scale=scale, temperature=temperature)
 
 
-def self_adversarial_loss(model, h: torch.Tensor, r: torch.Tensor, t: torch.Tensor, neg: torch.Tensor, side: str = "tail",
-                          margin: float = 0.0, scale: float = 1.0, temperature: float = 1.0, reduction: str = "mean",
-                          scoring: Optional[str] = None) -> torch.Tensor:
-    """The self-adversarial negative-sampling loss of the triples (h, r, t) (int64[G]) against their sampled negatives
-    neg (int64[G, K], K >= 1) under the model (see the module docstring): side 'tail' (the negatives replace the tail) or
-    'head' (they replace the head), margin any finite number, scale > 0, temperature >= 0, reduction 'mean' / 'sum' /
-    'none' over the groups, scoring 'transr' / 'transe' / 'dot' (default: model.scoring).  Differentiable in every
-    parameter the table, the relation embeddings and (transr) gat_trans_M depend on."""
-    if not hasattr(model, "_table_for_inference"):          # (ShardedLiteralKG: its table is a block per rank)
-        raise NotImplementedError(SHARDED_MESSAGE)
-    side = Q.check_one_side(side, "the negatives replace one side of the triple")
-    scoring = Q.resolve_scoring(model, scoring, MLP_MESSAGE)
-    reduction = check_reduction(reduction)
-    scale = ops.check_softmax_args(scale, None)[0]
-    margin, temperature = check_margin(margin), check_temperature(temperature)
-    Q.check_triple_lists(h, r, t)
-    if not isinstance(neg, torch.Tensor) or neg.dim() != 2 or neg.dtype.is_floating_point or neg.dtype == torch.bool or \
-            neg.shape[0] != h.numel() or (h.numel() > 0 and neg.shape[1] < 1):
-        raise ValueError(f"neg must be a 2-D tensor of integer ids with one row of K >= 1 negatives per triple "
-                         f"({h.numel()} rows)")
-    Q.check_transr_model(model, scoring)
-    dev = model.entity_embed.weight.device
-    g = h.numel()
-    if g == 0:
-        return torch.zeros((0,) if reduction == "none" else (), dtype=torch.float32, device=dev)
-    h, t, neg = ops.checked_ids(model.n_entities, h.to(dev), t.to(dev), neg.to(dev))    # (out-of-range ids never reach a kernel)
-    (r,) = ops.checked_ids(model.n_relations, r.to(dev), what="relation")
-    model.device = dev
-    table, (h, t, neg) = model._embeddings_and_ids(h, t, neg)        # the pruned table with positions, or the full one
-    Q.check_table_shape(model, scoring, table)
+def _side_losses(model, scoring: str, side: str, table, h, r, t, neg, margin, scale, temperature):
+    """float32[G], in the caller's order: the losses of the groups (h, r, t, neg) -- ids already checked and relabelled for
+    ``table`` -- corrupted on ``side``."""
+    dev, g = table.device, h.numel()
     anchor, pos = (h, t) if side == "tail" else (t, h)
     kn = neg.shape[1]
     if scoring == "transr":                     # the groups in relation order: a relation's rows are ONE slice of the gather
@@ -200,9 +174,50 @@ def self_adversarial_loss(model, h: torch.Tensor, r: torch.Tensor, t: torch.Tens
     if scoring == "transr":
         back = torch.empty_like(perm)
         back[perm] = torch.arange(g, device=dev)
-        loss = torch.cat(parts)[back]
-    else:
-        loss = parts[0]
+        return torch.cat(parts)[back]
+    return parts[0]
+
+
+def losses_by_side(model, scoring: str, h, r, t, neg, parts, margin, scale, temperature):
+    """[float32[G_i]]: the per-group losses of the G > 0 groups (h, r, t, neg[G, K]) in parts -- ``parts`` lists
+    (side, positions) with positions an index tensor into the groups (None: all of them) -- on ONE table: the ids are
+    checked and the table is taken once (the encoder runs once, prune_to_batch sees every id), each part is gathered and
+    scored for itself.  Arguments already validated (self_adversarial_loss, negatives.sampled_negative_loss)."""
+    dev = model.entity_embed.weight.device
+    h, t, neg = ops.checked_ids(model.n_entities, h.to(dev), t.to(dev), neg.to(dev))    # (out-of-range ids never reach a kernel)
+    (r,) = ops.checked_ids(model.n_relations, r.to(dev), what="relation")
+    model.device = dev
+    table, (h, t, neg) = model._embeddings_and_ids(h, t, neg)        # the pruned table with positions, or the full one
+    Q.check_table_shape(model, scoring, table)
+    return [_side_losses(model, scoring, side, table, *((x if at is None else x[at]) for x in (h, r, t, neg)),
+                         margin, scale, temperature) for side, at in parts]
+
+
+def self_adversarial_loss(model, h: torch.Tensor, r: torch.Tensor, t: torch.Tensor, neg: torch.Tensor, side: str = "tail",
+                          margin: float = 0.0, scale: float = 1.0, temperature: float = 1.0, reduction: str = "mean",
+                          scoring: Optional[str] = None) -> torch.Tensor:
+    """The self-adversarial negative-sampling loss of the triples (h, r, t) (int64[G]) against their sampled negatives
+    neg (int64[G, K], K >= 1) under the model (see the module docstring): side 'tail' (the negatives replace the tail) or
+    'head' (they replace the head), margin any finite number, scale > 0, temperature >= 0, reduction 'mean' / 'sum' /
+    'none' over the groups, scoring 'transr' / 'transe' / 'dot' (default: model.scoring).  Differentiable in every
+    parameter the table, the relation embeddings and (transr) gat_trans_M depend on."""
+    if not hasattr(model, "_table_for_inference"):          # (ShardedLiteralKG: its table is a block per rank)
+        raise NotImplementedError(SHARDED_MESSAGE)
+    side = Q.check_one_side(side, "the negatives replace one side of the triple")
+    scoring = Q.resolve_scoring(model, scoring, MLP_MESSAGE)
+    reduction = check_reduction(reduction)
+    scale = ops.check_softmax_args(scale, None)[0]
+    margin, temperature = check_margin(margin), check_temperature(temperature)
+    Q.check_triple_lists(h, r, t)
+    if not isinstance(neg, torch.Tensor) or neg.dim() != 2 or neg.dtype.is_floating_point or neg.dtype == torch.bool or \
+            neg.shape[0] != h.numel() or (h.numel() > 0 and neg.shape[1] < 1):
+        raise ValueError(f"neg must be a 2-D tensor of integer ids with one row of K >= 1 negatives per triple "
+                         f"({h.numel()} rows)")
+    Q.check_transr_model(model, scoring)
+    if h.numel() == 0:
+        dev = model.entity_embed.weight.device
+        return torch.zeros((0,) if reduction == "none" else (), dtype=torch.float32, device=dev)
+    loss = losses_by_side(model, scoring, h, r, t, neg, [(side, None)], margin, scale, temperature)[0]
     if reduction == "mean":
         return loss.mean()
     return loss.sum() if reduction == "sum" else loss
