@@ -126,10 +126,6 @@ __global__ __launch_bounds__(TK_THREADS) void accept_kernel(
     }
 }
 
-bool vec_ok(const void *a, long lda, const void *b, long ldb) {
-    return lkg_aligned16(a) && lkg_aligned16(b) && lda % 4 == 0 && ldb % 4 == 0;
-}
-
 template <bool EMIT>
 int launch_accept(const char *name, int64_t n_q, int64_t n_cand, int32_t k, const float *q, int64_t ldq, const float *p,
                   int64_t ldp, const float *pn, const float *qn, const float *thr, int32_t higher,

@@ -23,12 +23,11 @@
 // truth = -1 builds them).  Lane = row of the wave's 64 walks its row's list with a cursor, turns the entries inside the
 // wave's 64 columns into a 64-bit mask and leaves it in LDS for the lanes that hold the row's logits (wave-local: no
 // workgroup barrier); a wave none of whose rows has a positive in the tile skips all of it.  The cursor and mask helpers
-// are those of lkg_softmax.hip, copied: that file's kernels keep their text and their registers.
-#include "lkg_rank_common.h"
+// are lkg_all_entity_common.h's, shared with lkg_softmax.hip; a call without lists (yptr NULL) seeks with no rows, so
+// every list is empty and yptr is never read.
+#include "lkg_all_entity_common.h"
 
 #include "../../include/literalkg_hip_ext.h"
-
-#include <climits>
 
 #pragma clang fp contract(off)
 
@@ -37,59 +36,6 @@ namespace {
 constexpr int KV_THREADS = 256;
 constexpr int KV_ROWS = 64;           // queries per workgroup
 constexpr int KV_COLS = 256;          // candidates per tile (64 per wave)
-
-// A row's walk through its list of positives: entries [cur, end) of ycol are still ahead, next = ycol[cur] (INT_MAX when
-// none is left: positions are < n_c < INT32_MAX).  yptr is clamped into [0, m_total], so a bad list cannot be read past.
-struct ListCursor {
-    int cur, end, next;
-};
-
-// the list of query `row` (empty past n_q, or without lists) from its first entry >= first (binary search)
-__device__ __forceinline__ ListCursor list_seek(const int *__restrict__ yptr, const int *__restrict__ ycol, int m_total,
-                                                long row, long n_q, long first) {
-    ListCursor x{0, 0, INT_MAX};
-    if (yptr && row < n_q) {
-        x.cur = min(max(yptr[row], 0), m_total);
-        x.end = min(max(yptr[row + 1], x.cur), m_total);
-    }
-    int lo = x.cur, hi = x.end;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (ycol[mid] < first) lo = mid + 1;
-        else hi = mid;
-    }
-    x.cur = lo;
-    if (x.cur < x.end) x.next = ycol[x.cur];
-    return x;
-}
-
-// bit b set: position c0 + b is in the list; the cursor moves past every entry below c0 + 64
-__device__ __forceinline__ unsigned long long list_tile_mask(ListCursor &x, const int *__restrict__ ycol, long c0) {
-    unsigned long long mk = 0ull;
-    while ((long)x.next < c0 + 64) {
-        if ((long)x.next >= c0) mk |= 1ull << ((long)x.next - c0);
-        ++x.cur;
-        x.next = x.cur < x.end ? ycol[x.cur] : INT_MAX;
-    }
-    return mk;
-}
-
-// The wave's masks of one tile: lane = row computes its row's, the wave leaves them in sm (its own 64 words) when any is
-// non-zero.  Returns that wave-uniform "any".  LDS operations of one wave complete in order, so the rows' readers need no
-// workgroup barrier; the wave barriers keep the compiler from moving the accesses across each other.
-__device__ __forceinline__ bool list_publish(ListCursor &x, const int *__restrict__ ycol, long c0, unsigned long long *sm,
-                                             int lane) {
-    const unsigned long long mk = list_tile_mask(x, ycol, c0);
-    const bool any = __ballot(mk != 0ull) != 0ull;
-    if (any) {
-        __builtin_amdgcn_wave_barrier();            // the previous tile's reads come first
-        sm[lane] = mk;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    }
-    return any;
-}
 
 // softplus(x) without cancellation; NaN in, NaN out (fmaxf drops it, the logarithm keeps it)
 __device__ __forceinline__ float softplus_f(float x) { return fmaxf(x, 0.f) + log1pf(expf(-fabsf(x))); }
@@ -125,7 +71,7 @@ __global__ __launch_bounds__(KV_THREADS, 2) void sigmoid_partial_kernel(
     for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int v = 0; v < 4; ++v) l[i][v] = 0.f;
-    ListCursor x = list_seek(yptr, ycol, m_total, q0 + lane, n_q, t_lo * KV_COLS);
+    ListCursor x = list_seek(yptr, ycol, m_total, q0 + lane, yptr ? n_q : 0, t_lo * KV_COLS);
 
     for (long t = t_lo; t < t_hi; ++t) {
         const long c0 = t * KV_COLS + wave * 64;
@@ -218,7 +164,7 @@ __global__ __launch_bounds__(KV_THREADS) void sigmoid_weights_kernel(
     }
     f32x4 acc[4][4];
     rank_tile_dots<VEC>(acc, qrow, prow, k, s);
-    ListCursor x = list_seek(yptr, ycol, m_total, q0 + lane, n_q, c_base + c0);
+    ListCursor x = list_seek(yptr, ycol, m_total, q0 + lane, yptr ? n_q : 0, c_base + c0);
     const bool any = list_publish(x, ycol, c_base + c0, sm_y[wave], lane);
     float pnv[4];
     long cid[4];
@@ -259,16 +205,7 @@ __global__ __launch_bounds__(KV_THREADS) void sigmoid_weights_kernel(
     }
 }
 
-bool vec_ok(const void *a, long lda, const void *b, long ldb) {
-    return lkg_aligned16(a) && lkg_aligned16(b) && lda % 4 == 0 && ldb % 4 == 0;
-}
-
-bool scale_ok(float scale) { return scale > 0.f && scale < __builtin_inff(); }
-
 bool eps_ok(double eps) { return eps >= 0.0 && eps < 1.0; }
-
-// -scale * beta: beta = 1 with squared norms (minus the squared distance), 1/2 without (the dot product); exact
-float neg_scale_beta(float scale, const float *pn) { return pn ? -scale : -0.5f * scale; }
 
 // the smoothing coefficients of a positive and of a negative column, in double, rounded once
 float ce_pos(double eps, int64_t n) { return (float)(eps * (1.0 - 1.0 / (double)n)); }

@@ -188,10 +188,6 @@ __global__ __launch_bounds__(256) void rank_queries_kernel(long n, int k, const 
     for (int c = lane; c < k; c += 64) y[c] = er ? __builtin_fmaf(alpha, er[c], x[c]) : x[c];
 }
 
-bool vec_ok(const void *a, long lda, const void *b, long ldb) {
-    return lkg_aligned16(a) && lkg_aligned16(b) && lda % 4 == 0 && ldb % 4 == 0;
-}
-
 }  // namespace
 
 extern "C" int lkg_rank_sqnorm_f32(int64_t n, int32_t k, const float *p, int64_t ldp, float *out, void *stream) {

@@ -10,6 +10,11 @@
 
 using f32x4 = __attribute__((ext_vector_type(4))) float;
 
+// host side: may the kernels be launched with VEC (16-byte loads of both operands' rows)?
+static inline bool vec_ok(const void *a, long lda, const void *b, long ldb) {
+    return lkg_aligned16(a) && lkg_aligned16(b) && lda % 4 == 0 && ldb % 4 == 0;
+}
+
 template <bool VEC>
 __device__ __forceinline__ float4 load4(const float *__restrict__ row, int kk, int k) {
     if (VEC && kk + 4 <= k) return *reinterpret_cast<const float4 *>(row + kk);

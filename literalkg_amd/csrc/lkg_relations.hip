@@ -210,10 +210,6 @@ __global__ __launch_bounds__(RO_THREADS) void relation_order_kernel(
     }
 }
 
-bool vec_ok(const void *a, long lda, const void *b, long ldb) {
-    return lkg_aligned16(a) && lkg_aligned16(b) && lda % 4 == 0 && ldb % 4 == 0;
-}
-
 }  // namespace
 
 extern "C" int lkg_relation_scores_f32(int64_t n, int32_t k, int32_t n_rel, const float *p, int64_t ldp,

@@ -292,10 +292,6 @@ __global__ __launch_bounds__(256) void retrieval_finish_kernel(
     }
 }
 
-bool vec_ok(const void *a, long lda, const void *b, long ldb) {
-    return lkg_aligned16(a) && lkg_aligned16(b) && lda % 4 == 0 && ldb % 4 == 0;
-}
-
 }  // namespace
 
 extern "C" int lkg_retrieval_prepare_f32(int64_t n_rows, int64_t n_cand, int32_t k, const float *q, int64_t ldq,

@@ -24,9 +24,7 @@
 // row's list with a cursor, turns the entries inside the wave's 64 columns into a 64-bit mask and leaves it in LDS for the
 // lanes that hold the row's logits (wave-local: no workgroup barrier); a wave none of whose rows drops a column of the
 // tile skips all of it.  The truth is never in a list (softmax_excluded_kernel), so the finish kernel serves both.
-#include "lkg_rank_common.h"
-
-#include <climits>
+#include "lkg_all_entity_common.h"
 
 #pragma clang fp contract(off)
 
@@ -39,59 +37,6 @@ constexpr int SM_MAX_SPLITS = LKG_SOFTMAX_MAX_SPLITS;
 
 // exp(z - m) must not see inf - inf: a pair that has met no candidate yet is (-inf, 0) and takes 0 as its reference
 __device__ __forceinline__ float safe_ref(float m) { return m == -__builtin_inff() ? 0.f : m; }
-
-// A row's walk through its exclusion list: entries [cur, end) of xcol are still ahead, next = xcol[cur] (INT_MAX when
-// none is left: positions are < n_c < INT32_MAX).  xptr is clamped into [0, m_total], so a bad list cannot be read past.
-struct ExclCursor {
-    int cur, end, next;
-};
-
-// the list of query `row` (empty past n_q) from its first entry >= first (binary search)
-__device__ __forceinline__ ExclCursor excl_seek(const int *__restrict__ xptr, const int *__restrict__ xcol, int m_total,
-                                                long row, long n_q, long first) {
-    ExclCursor x{0, 0, INT_MAX};
-    if (row < n_q) {
-        x.cur = min(max(xptr[row], 0), m_total);
-        x.end = min(max(xptr[row + 1], x.cur), m_total);
-    }
-    int lo = x.cur, hi = x.end;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (xcol[mid] < first) lo = mid + 1;
-        else hi = mid;
-    }
-    x.cur = lo;
-    if (x.cur < x.end) x.next = xcol[x.cur];
-    return x;
-}
-
-// bit b set: position c0 + b is excluded; the cursor moves past every entry below c0 + 64
-__device__ __forceinline__ unsigned long long excl_tile_mask(ExclCursor &x, const int *__restrict__ xcol, long c0) {
-    unsigned long long mk = 0ull;
-    while ((long)x.next < c0 + 64) {
-        if ((long)x.next >= c0) mk |= 1ull << ((long)x.next - c0);
-        ++x.cur;
-        x.next = x.cur < x.end ? xcol[x.cur] : INT_MAX;
-    }
-    return mk;
-}
-
-// The wave's masks of one tile: lane = row computes its row's, the wave leaves them in sm (its own 64 words) when any is
-// non-zero.  Returns that wave-uniform "any".  LDS operations of one wave complete in order, so the rows' readers need no
-// workgroup barrier; the wave barriers keep the compiler from moving the accesses across each other.
-__device__ __forceinline__ bool excl_publish(ExclCursor &x, const int *__restrict__ xcol, long c0,
-                                             unsigned long long *sm, int lane) {
-    const unsigned long long mk = excl_tile_mask(x, xcol, c0);
-    const bool any = __ballot(mk != 0ull) != 0ull;
-    if (any) {
-        __builtin_amdgcn_wave_barrier();            // the previous tile's reads come first
-        sm[lane] = mk;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    }
-    return any;
-}
 
 template <bool VEC>
 __global__ __launch_bounds__(SM_THREADS) void softmax_partial_kernel(long n_q, long n_c, int k, const float *__restrict__ q,
@@ -204,7 +149,7 @@ __global__ __launch_bounds__(SM_THREADS) void softmax_partial_masked_kernel(
             m[i][v] = -__builtin_inff();
             l[i][v] = 0.f;
         }
-    ExclCursor x = excl_seek(xptr, xcol, m_total, q0 + lane, n_q, t_lo * SM_COLS);
+    ListCursor x = list_seek(xptr, xcol, m_total, q0 + lane, n_q, t_lo * SM_COLS);
 
     for (long t = t_lo; t < t_hi; ++t) {
         const long c0 = t * SM_COLS + wave * 64;
@@ -214,7 +159,7 @@ __global__ __launch_bounds__(SM_THREADS) void softmax_partial_masked_kernel(
         f32x4 acc[4][4];
         rank_tile_dots<VEC>(acc, qrow, prow, k, s);
         // acc[i][j][v]: query row 16 i + 4 s + v, candidate c0 + 16 j + r
-        const bool any = excl_publish(x, xcol, c0, sm_x[wave], lane);      // wave-uniform: some row drops a column here
+        const bool any = list_publish(x, xcol, c0, sm_x[wave], lane);      // wave-uniform: some row drops a column here
         float pnv[4];
         bool ok[4];
 #pragma unroll
@@ -375,8 +320,8 @@ __global__ __launch_bounds__(SM_THREADS) void softmax_weights_masked_kernel(
     f32x4 acc[4][4];
     rank_tile_dots<VEC>(acc, qrow, prow, k, s);
     // as in the forward pass; the lists hold table positions: c_base + the chunk's column
-    ExclCursor x = excl_seek(xptr, xcol, m_total, q0 + lane, n_q, c_base + c0);
-    const bool any = excl_publish(x, xcol, c_base + c0, sm_x[wave], lane);
+    ListCursor x = list_seek(xptr, xcol, m_total, q0 + lane, n_q, c_base + c0);
+    const bool any = list_publish(x, xcol, c_base + c0, sm_x[wave], lane);
     float pnv[4];
     long cid[4];
 #pragma unroll
@@ -449,15 +394,6 @@ __global__ __launch_bounds__(SM_THREADS) void softmax_excluded_kernel(
     }
     if (!FILL && lane == 0) cnt[i] = base;
 }
-
-bool vec_ok(const void *a, long lda, const void *b, long ldb) {
-    return lkg_aligned16(a) && lkg_aligned16(b) && lda % 4 == 0 && ldb % 4 == 0;
-}
-
-bool scale_ok(float scale) { return scale > 0.f && scale < __builtin_inff(); }
-
-// -scale * beta: beta = 1 with squared norms (minus the squared distance), 1/2 without (the dot product); exact
-float neg_scale_beta(float scale, const float *pn) { return pn ? -scale : -0.5f * scale; }
 
 }  // namespace
 

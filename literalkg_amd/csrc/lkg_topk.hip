@@ -196,10 +196,6 @@ __global__ __launch_bounds__(256) void topk_merge_kernel(long n_q, int kk, int s
     }
 }
 
-bool vec_ok(const void *a, long lda, const void *b, long ldb) {
-    return lkg_aligned16(a) && lkg_aligned16(b) && lda % 4 == 0 && ldb % 4 == 0;
-}
-
 template <bool VEC, int KC>
 void launch_select(dim3 grid, hipStream_t st, long n_q, long n_c, int k, const float *q, long ldq, const float *p,
                    long ldp, const float *pn, const long *cand, const long *frow, const long *frel, const int *rowptr,

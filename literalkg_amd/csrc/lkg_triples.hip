@@ -120,10 +120,6 @@ __global__ __launch_bounds__(TS_THREADS) void triple_scores_kernel(
     if (tid < 5 && cnt[tid]) atomicAdd(counts + tid, (unsigned long long)cnt[tid]);
 }
 
-bool vec_ok(const void *a, long lda, const void *b, long ldb) {
-    return lkg_aligned16(a) && lkg_aligned16(b) && lda % 4 == 0 && ldb % 4 == 0;
-}
-
 }  // namespace
 
 extern "C" int lkg_triple_scores_f32(int64_t n, int32_t k, const float *p, int64_t ldp, const int64_t *q_idx,

@@ -29,9 +29,10 @@ import torch
 from torch.autograd import Function
 
 from . import _native as N
+from . import _objectives as O
 from . import _queries as Q
-from . import ops, pruned
-from .one_vs_all import check_reduction
+from . import ops
+from ._objectives import check_margin      # noqa: F401  (its home before _objectives.py)
 
 MLP_MESSAGE = ("scoring='mlp' has no KvsAll loss: the pair head is trained by train_MLP on labelled pairs -- use 'transr', "
                "'transe' or 'dot'")
@@ -45,43 +46,17 @@ def check_label_smoothing(eps) -> float:
     return float(eps)
 
 
-def _positives(what: str, positives, b: int):
-    """(yptr, ycol) of a ``positives`` argument, checked (None: no list at all -- the bits of empty lists)"""
-    if positives is None:
-        return None, None
-    yptr, ycol = positives
-    ops._need_gpu(yptr, ycol)
-    if yptr.dtype != torch.int32 or ycol.dtype != torch.int32 or yptr.dim() != 1 or ycol.dim() != 1 or \
-            yptr.numel() != b + 1:
-        raise ValueError(f"{what}: positives must be (yptr int32[{b + 1}], ycol int32[M]) as ops.softmax_excluded returns "
-                         "them")
-    return yptr.contiguous(), ycol.contiguous()
-
-
-def _operands(what: str, q, p, bias, pn=None):
-    ops._need_gpu(q, p, bias, pn)
-    q, p = ops._f32_rows(q), ops._f32_rows(p)
-    if p.shape[1] != q.shape[1] or q.shape[1] == 0 or p.shape[0] == 0 or (pn is not None and pn.numel() != p.shape[0]):
-        raise ValueError(f"{what}: queries {tuple(q.shape)}, candidates {tuple(p.shape)}")
-    if bias is not None:
-        if bias.dtype != torch.float32 or bias.numel() != q.shape[0]:
-            raise ValueError(f"{what}: bias must be float32[{q.shape[0]}] (one per query), got {bias.dtype} "
-                             f"{tuple(bias.shape)}")
-        bias = bias.reshape(-1).contiguous()
-    return q, p, bias
-
-
 def sigmoid_all_forward(q: torch.Tensor, p: torch.Tensor, pn: Optional[torch.Tensor], bias: Optional[torch.Tensor],
                         positives=None, scale: float = 1.0, label_smoothing: float = 0.0,
                         splits: Optional[int] = None) -> torch.Tensor:
     """loss float32[B] of lkg_sigmoid_all_partial_f32 + lkg_sigmoid_all_finish_f32, no autograd: the logits are
     z = -scale (pn[c] - 2 q.p_c) + bias with pn = ops.rank_sqnorm(p), or scale q.p_c + bias with pn None (bias None: 0);
     loss_i = sum_c softplus(z) - y' z with y = 1 on the positions positives = (yptr, ycol) list for row i."""
-    q, p, bias = _operands("sigmoid_all_forward", q, p, bias, pn)
+    q, p, _, bias = ops.all_entity_operands("sigmoid_all_forward", q, p, pn, bias=bias)
     scale, splits, _ = ops.check_softmax_args(scale, splits)
     eps = check_label_smoothing(label_smoothing)
     (b, k), n, dev = q.shape, p.shape[0], q.device
-    yptr, ycol = _positives("sigmoid_all_forward", positives, b)
+    yptr, ycol = ops.list_pair("sigmoid_all_forward", "positives", positives, b)
     loss = torch.empty(b, dtype=torch.float32, device=dev)
     if b == 0:
         return loss
@@ -101,26 +76,19 @@ def sigmoid_all_weights(q: torch.Tensor, p: torch.Tensor, pn: Optional[torch.Ten
     V[i, c] = scale beta g[i] (sigma(z_ic) - y'_ic), beta = 1 with pn, 1/2 without.  The lists hold positions of the whole
     table and the n of the smoothing is the whole table's, whatever the chunk.  rowsum (optional, contiguous float32
     [ceil((c1 - c0) / 256), B]): receives per 256-candidate tile of the chunk the sum of V's row over that tile."""
-    q, p, bias = _operands("sigmoid_all_weights", q, p, bias, pn)
+    q, p, _, bias = ops.all_entity_operands("sigmoid_all_weights", q, p, pn, bias=bias)
     ops._need_gpu(g, out)
     scale = ops.check_softmax_args(scale, 0)[0]
     eps = check_label_smoothing(label_smoothing)
     (b, k), n = q.shape, p.shape[0]
-    yptr, ycol = _positives("sigmoid_all_weights", positives, b)
-    c1 = n if c1 is None else int(c1)
-    c0 = int(c0)
-    if not 0 <= c0 <= c1 <= n:
-        raise ValueError(f"sigmoid_all_weights: the chunk [{c0}, {c1}) does not lie in [0, {n}]")
+    yptr, ycol = ops.list_pair("sigmoid_all_weights", "positives", positives, b)
+    c0, c1 = ops.chunk_range("sigmoid_all_weights", c0, c1, n)
     g = g.reshape(-1).contiguous()
     if g.numel() != b or g.dtype != torch.float32:
         raise ValueError(f"sigmoid_all_weights: g must be float32[{b}]")
+    out = ops.weights_out("sigmoid_all_weights", out, b, c1 - c0, q.device)
     if b == 0:
-        return out if out is not None else torch.empty((0, c1 - c0), dtype=torch.float32, device=q.device)
-    if out is None:
-        out = torch.empty((b, c1 - c0), dtype=torch.float32, device=q.device)
-    elif tuple(out.shape) != (b, c1 - c0) or out.dtype != torch.float32 or (out.numel() and out.stride(1) != 1) or \
-            (b > 1 and out.stride(0) < c1 - c0):
-        raise ValueError(f"sigmoid_all_weights: out must be a float32 {b} x {c1 - c0} tensor with unit column stride")
+        return out
     if rowsum is not None:
         ops._need_gpu(rowsum)
         if tuple(rowsum.shape) != ((c1 - c0 + 255) // 256, b) or rowsum.dtype != torch.float32 or not rowsum.is_contiguous():
@@ -134,10 +102,8 @@ def sigmoid_all_weights(q: torch.Tensor, p: torch.Tensor, pn: Optional[torch.Ten
 
 class _SigmoidAllLoss(Function):
     """loss_i = sum_c softplus(z_ic) - y'_ic z_ic over ALL rows of p.  Forward: two launches, nothing of size B x N.  Backward:
-    the loop of ops._SoftmaxAllLoss -- per chunk of candidates the weights V (lkg_sigmoid_all_weights_f32), then
-    dQ += 2 V P_chunk in slices of ops.SOFTMAX_DQ_SLICE candidates and dP_chunk = 2 V^T Q - 2 diag(colsum V) P_chunk on
-    ops.gemm, both with beta = 1 onto an initialised output (a beta = 0 product with a long reduction goes over float
-    atomics), colsum V as a column of ones next to Q.  Added: dbias = rowsum(V) / (scale beta).  The weights kernel leaves
+    ops.all_entity_backward, the loop of the softmax loss, with the weights V of lkg_sigmoid_all_weights_f32; its
+    per-chunk hook adds dbias = rowsum(V) / (scale beta).  The weights kernel leaves
     the row sums of its tiles as it stores them, lkg_sigmoid_all_finish_f32 adds a chunk's tiles in float64, the chunks are
     added in float64 (a column of ones next to P in the dQ product was tried first: away from the positives V has one
     sign, and the f32 MFMA chain's error grew with the chain's length).  V has the same bits with or without the row
@@ -146,7 +112,7 @@ class _SigmoidAllLoss(Function):
 
     @staticmethod
     def forward(ctx, q, p, bias, yptr, ycol, distance, scale, eps, splits, chunk_bytes):
-        q_, p_, bias_ = _operands("sigmoid_all_loss", q, p, bias)
+        q_, p_, _, bias_ = ops.all_entity_operands("sigmoid_all_loss", q, p, bias=bias)
         pn = ops.rank_sqnorm(p_) if distance else None
         positives = (yptr, ycol) if yptr is not None else None
         loss = sigmoid_all_forward(q_, p_, pn, bias_, positives, scale, eps, splits)
@@ -161,48 +127,26 @@ class _SigmoidAllLoss(Function):
         scale, eps, chunk_bytes, bias_shape = ctx.meta
         want_q, want_p = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         want_b = bias is not None and ctx.needs_input_grad[2]
-        (b, k), n, dev = q.shape, p.shape[0], q.device
-        nothing = (None,) * 7
-        if b == 0:
-            return (torch.zeros((0, k), dtype=torch.float32, device=dev) if want_q else None,
-                    torch.zeros((n, k), dtype=torch.float32, device=dev) if want_p else None,
-                    torch.zeros(bias_shape, dtype=torch.float32, device=dev) if want_b else None) + nothing
-        sb = scale if pn is not None else 0.5 * scale
+        b, dev = q.shape[0], q.device
         g = g.reshape(-1).float().contiguous()
-        width = ops.softmax_chunk_width(b, n, chunk_bytes)
-        vbuf = torch.empty((b, width), dtype=torch.float32, device=dev)
-        dq = torch.zeros((b, k), dtype=torch.float32, device=dev) if want_q else None
-        dp = torch.empty((n, k), dtype=torch.float32, device=dev) if want_p else None
+        width = ops.softmax_chunk_width(b, p.shape[0], chunk_bytes)
         if want_b:
+            rows = torch.zeros(b, dtype=torch.float64, device=dev)
             tiles = torch.empty(((width + 255) // 256, b), dtype=torch.float32, device=dev)
             part = torch.empty(b, dtype=torch.float32, device=dev)
-            rows = torch.zeros(b, dtype=torch.float64, device=dev)
-        if want_p and pn is not None:
-            q1 = torch.cat((q, torch.ones((b, 1), dtype=torch.float32, device=dev)), dim=1)
-            tmp = torch.empty((width, k + 1), dtype=torch.float32, device=dev)
-        for c0 in range(0, n, width):                  # a fixed order: dQ accumulates slice after slice, chunk after chunk
-            c1 = min(n, c0 + width)
-            n_tiles = (c1 - c0 + 255) // 256
-            v = sigmoid_all_weights(q, p, pn, bias, g, positives, scale, eps, c0, c1, out=vbuf[:, :c1 - c0],
-                                    rowsum=tiles[:n_tiles] if want_b else None)
-            pc = p[c0:c1]
-            if want_b:
-                N.call("lkg_sigmoid_all_finish_f32", b, n_tiles, N.ptr(tiles), N.ptr(part), ops._stream())
-                rows += part
-            if want_q:
-                for s0 in range(0, c1 - c0, ops.SOFTMAX_DQ_SLICE):
-                    s1 = min(c1 - c0, s0 + ops.SOFTMAX_DQ_SLICE)
-                    ops.gemm(v[:, s0:s1], pc[s0:s1], alpha=2.0, beta=1.0, out=dq)
-            if want_p:
-                dpc = dp[c0:c1]                        # written once
-                if pn is not None:
-                    t = tmp[:c1 - c0].zero_()
-                    ops.gemm(v, q1, trans_a=True, alpha=2.0, beta=1.0, out=t)      # [2 V^T Q | 2 colsum V]
-                    torch.addcmul(t[:, :k], t[:, k:], pc, value=-1.0, out=dpc)
-                else:
-                    ops.gemm(v, q, trans_a=True, alpha=2.0, beta=1.0, out=dpc.zero_())
+
+        def fill(c0, c1, out):
+            return sigmoid_all_weights(q, p, pn, bias, g, positives, scale, eps, c0, c1, out=out,
+                                       rowsum=tiles[:(c1 - c0 + 255) // 256] if want_b else None)
+
+        def add_row_sums(c0, c1):
+            N.call("lkg_sigmoid_all_finish_f32", b, (c1 - c0 + 255) // 256, N.ptr(tiles), N.ptr(part), ops._stream())
+            rows.add_(part)
+
+        dq, dp = ops.all_entity_backward(q, p, pn, width, want_q, want_p, fill, add_row_sums if want_b else None)
+        sb = scale if pn is not None else 0.5 * scale
         dbias = (rows / sb).float().reshape(bias_shape) if want_b else None
-        return (dq, dp, dbias) + nothing
+        return (dq, dp, dbias) + (None,) * 7
 
 
 def sigmoid_all_loss(q: torch.Tensor, p: torch.Tensor, bias: Optional[torch.Tensor], positives=None, distance: bool = True,
@@ -219,7 +163,7 @@ def sigmoid_all_loss(q: torch.Tensor, p: torch.Tensor, bias: Optional[torch.Tens
     scale, splits, chunk_bytes = ops.check_softmax_args(scale, splits, chunk_bytes)
     eps = check_label_smoothing(label_smoothing)
     ops._need_gpu(q, p, bias)
-    yptr, ycol = _positives("sigmoid_all_loss", positives, q.shape[0])
+    yptr, ycol = ops.list_pair("sigmoid_all_loss", "positives", positives, q.shape[0])
     return _SigmoidAllLoss.apply(q, p, bias, yptr, ycol, bool(distance), scale, eps, splits, chunk_bytes)
 
 
@@ -229,34 +173,6 @@ def distinct_queries(ent: torch.Tensor, r: torch.Tensor):
     Q.check_id_pair(ent, r, ("ent", "r"))
     pairs = torch.unique(torch.stack((r.long(), ent.long()), dim=1), dim=0)
     return pairs[:, 1].contiguous(), pairs[:, 0].contiguous()
-
-
-def check_margin(margin) -> float:
-    if isinstance(margin, bool) or not isinstance(margin, (int, float)) or not abs(float(margin)) < float("inf"):
-        raise ValueError(f"margin must be a finite number, got {margin!r}")
-    return float(margin)
-
-
-def _group_losses(model, scoring: str, side: str, table, rows, w, ent, r, margin, scale, eps, splits, known, pos):
-    """float32[len(ent)]: the loss of the queries (ent, r) of one projection.  rows: the candidate rows -- the table itself,
-    or (pos given: the entity -> position map) the gathered rows of the candidates -- projected by w for 'transr'; with
-    candidates the query rows are gathered from the table and projected on their own."""
-    p = rows if w is None else ops.matmul(rows, w)              # alive until the backward pass (transr: N x relation_dim)
-    if pos is None:
-        q = pruned.gather_rows(p, ent)
-    else:
-        q = pruned.gather_rows(table, ent)
-        q = q if w is None else ops.matmul(q, w)
-    distance = scoring != "dot"
-    if distance:
-        q = ops.axpby(q, pruned.gather_rows(model.relation_embed.weight, r), 1.0, Q.side_alpha(side))
-        bias = scale * (margin - (q * q).sum(1))                # ||q||^2 does not cancel under a sigmoid: differentiable
-    else:
-        bias = torch.full((ent.numel(),), scale * margin, dtype=torch.float32, device=ent.device)
-    frel = r if distance else torch.full_like(r, -1)
-    none = torch.full_like(ent, -1)                              # no truth to exempt: every known answer is listed
-    positives = ops.softmax_excluded(known.for_side(side), ent, frel, none, p.shape[0], pos)
-    return sigmoid_all_loss(q, p, bias, positives, distance=distance, scale=scale, label_smoothing=eps, splits=splits)
 
 
 def kvs_all_loss(model, ent: torch.Tensor, r: torch.Tensor, known, side: str = "tail", margin: float = 0.0,
@@ -269,11 +185,10 @@ def kvs_all_loss(model, ent: torch.Tensor, r: torch.Tensor, known, side: str = "
     'transe' / 'dot' (default: model.scoring), splits as in one_vs_all_loss.  known: the KnownTriples the positives are
     read from.  candidates: the unique entity ids scored (n = their number; a positive that is not among them is simply
     absent).  Differentiable in every parameter the table, the relation embeddings and (transr) gat_trans_M depend on."""
-    if not hasattr(model, "_table_for_inference"):          # (ShardedLiteralKG: its table is a block per rank)
-        raise NotImplementedError(SHARDED_MESSAGE)
+    O.check_single_device(model, SHARDED_MESSAGE)
     side = Q.check_one_side(side, "a KvsAll row is one side's query")
     scoring = Q.resolve_scoring(model, scoring, MLP_MESSAGE)
-    reduction = check_reduction(reduction)
+    reduction = O.check_reduction(reduction)
     scale, splits, _ = ops.check_softmax_args(scale, splits)
     margin, eps = check_margin(margin), check_label_smoothing(label_smoothing)
     Q.check_id_pair(ent, r, ("ent", "r"))
@@ -284,40 +199,24 @@ def kvs_all_loss(model, ent: torch.Tensor, r: torch.Tensor, known, side: str = "
     if candidates is not None:
         Q.check_ids("candidates", candidates)
     dev = model.entity_embed.weight.device
-    b = ent.numel()
-    if b == 0:
-        return torch.zeros((0,) if reduction == "none" else (), dtype=torch.float32, device=dev)
+    if ent.numel() == 0:
+        return O.empty_loss(model, reduction)
     (ent,) = ops.checked_ids(model.n_entities, ent.to(dev))                 # (out-of-range ids never reach a kernel)
     (r,) = ops.checked_ids(model.n_relations, r.to(dev), what="relation")
     Q.check_known_device(known, dev)
-    cand = pos = None
-    if candidates is not None:                  # sorted: pos is increasing over the candidates, the bits ignore the order
-        (cand,) = ops.checked_ids(model.n_entities, candidates.to(dev), what="candidate entity")
-        ops.check_deferred_errors()
-        Q.check_unique(cand)
-        if cand.numel() == 0:
-            raise ValueError("candidates must hold at least one entity id")
-        cand = torch.sort(cand).values
-        pos = torch.full((model.n_entities,), -1, dtype=torch.int32, device=dev)
-        pos[cand] = torch.arange(cand.numel(), dtype=torch.int32, device=dev)
-    model.device = dev
-    table = model._table_for_inference()       # training or grad enabled: gat_embeddings() with its graph; else the kept table
-    Q.check_table_shape(model, scoring, table)
-    rows = table if cand is None else pruned.gather_rows(table, cand)      # gathered once for every relation group
-    if scoring == "transr":
-        perm, seg = ops.group_by_key(r, model.n_relations)
-        perm, seg = perm.long(), seg.tolist()
-        parts = []
-        for rr in range(model.n_relations):
-            if seg[rr + 1] > seg[rr]:
-                at = perm[seg[rr]:seg[rr + 1]]
-                parts.append(_group_losses(model, scoring, side, table, rows, model.gat_trans_M[rr], ent[at], r[at], margin,
-                                           scale, eps, splits, known, pos))
-        back = torch.empty_like(perm)
-        back[perm] = torch.arange(b, device=dev)
-        loss = torch.cat(parts)[back]
-    else:
-        loss = _group_losses(model, scoring, side, table, rows, None, ent, r, margin, scale, eps, splits, known, pos)
-    if reduction == "mean":
-        return loss.mean()
-    return loss.sum() if reduction == "sum" else loss
+    cand, pos = O.candidate_block(model, candidates, dev)
+    distance = scoring != "dot"
+
+    def score_group(table, rows, w, r, ent):
+        """the loss of the queries (ent, r) of one projection"""
+        p = O.projected(rows, w)                                # alive until the backward pass (transr: N x relation_dim)
+        q = O.query_rows(model, scoring, side, table, p, w, ent, r, pos)
+        if distance:
+            bias = scale * (margin - (q * q).sum(1))            # ||q||^2 does not cancel under a sigmoid: differentiable
+        else:
+            bias = torch.full((ent.numel(),), scale * margin, dtype=torch.float32, device=ent.device)
+        none = torch.full_like(ent, -1)                          # no truth to exempt: every known answer is listed
+        positives = ops.softmax_excluded(known.for_side(side), ent, O.known_relations(scoring, r), none, p.shape[0], pos)
+        return sigmoid_all_loss(q, p, bias, positives, distance=distance, scale=scale, label_smoothing=eps, splits=splits)
+
+    return O.all_entity_loss(model, scoring, r, (ent,), cand, reduction, score_group)

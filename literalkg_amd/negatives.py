@@ -26,7 +26,7 @@ import torch
 from . import _native as N
 from . import _queries as Q
 from . import ops
-from .one_vs_all import check_reduction
+from ._objectives import check_margin, check_reduction, check_single_device
 from .ranking import KnownTriples
 
 MAX_TRIES = 64                                     # LKG_SAMPLE_MAX_TRIES
@@ -258,11 +258,9 @@ def sampled_negative_loss(model, h: torch.Tensor, r: torch.Tensor, t: torch.Tens
     subsampling_weights; None: all 1): 'none' returns the unweighted float32[G], 'sum' is sum(w L), 'mean' is
     sum(w L) / sum(w).  margin, scale, temperature, scoring and the refusals ('mlp', ShardedLiteralKG) are
     self_adversarial_loss's."""
-    from .kvs_all import check_margin
     from .self_adversarial import (MLP_MESSAGE, SHARDED_MESSAGE, check_temperature, losses_by_side,
                                    self_adversarial_loss)
-    if not hasattr(model, "_table_for_inference"):
-        raise NotImplementedError(SHARDED_MESSAGE)
+    check_single_device(model, SHARDED_MESSAGE)
     scoring = Q.resolve_scoring(model, scoring, MLP_MESSAGE)
     Q.check_transr_model(model, scoring)
     reduction = check_reduction(reduction)

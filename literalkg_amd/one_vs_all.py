@@ -34,45 +34,13 @@ from typing import Optional
 
 import torch
 
+from . import _objectives as O
 from . import _queries as Q
-from . import ops, pruned
+from . import ops
+from ._objectives import REDUCTIONS, check_reduction      # noqa: F401  (their home before _objectives.py)
 
-REDUCTIONS = ("mean", "sum", "none")
 MLP_MESSAGE = ("scoring='mlp' has no 1-vs-all loss: the pair head is trained by train_MLP on labelled pairs -- use "
                "'transr', 'transe' or 'dot'")
-
-
-def check_reduction(reduction: str) -> str:
-    if reduction not in REDUCTIONS:
-        raise ValueError(f"reduction must be one of {REDUCTIONS}, got {reduction!r}")
-    return reduction
-
-
-def _side_losses(model, scoring: str, side: str, table, rows, w, h, r, t, scale, splits, known, pos):
-    """float32[len(h)]: per triple the loss of the side (the mean of the two sides' for 'both').  rows: the candidate rows
-    -- the table itself, or (pos given: the entity -> position map) the gathered rows of the candidates -- projected by w
-    for 'transr'; with candidates the query rows are gathered from the table and projected on their own.  known / pos:
-    the exclusion lists of ops.softmax_excluded per side."""
-    relemb = model.relation_embed.weight
-    p = rows if w is None else ops.matmul(rows, w)              # alive until the backward pass (transr: N x relation_dim)
-    total = None
-    for s_ in Q.rank_sides(side):
-        ent, truth = (h, t) if s_ == "tail" else (t, h)
-        if pos is None:
-            q = pruned.gather_rows(p, ent)
-        else:
-            q = pruned.gather_rows(table, ent)
-            q = q if w is None else ops.matmul(q, w)
-            truth = pos[truth].long()                          # (every truth is a candidate: checked by the caller)
-        if scoring != "dot":
-            q = ops.axpby(q, pruned.gather_rows(relemb, r), 1.0, Q.side_alpha(s_))
-        exclude = None
-        if known is not None:
-            frel = r if scoring != "dot" else torch.full_like(r, -1)
-            exclude = ops.softmax_excluded(known.for_side(s_), ent, frel, truth, p.shape[0], pos)
-        loss = ops.softmax_all_loss(q, p, truth, distance=scoring != "dot", scale=scale, splits=splits, exclude=exclude)
-        total = loss if total is None else total + loss
-    return total if side != "both" else 0.5 * total
 
 
 def one_vs_all_loss(model, h: torch.Tensor, r: torch.Tensor, t: torch.Tensor, side: str = "tail", scale: float = 1.0,
@@ -100,42 +68,34 @@ def one_vs_all_loss(model, h: torch.Tensor, r: torch.Tensor, t: torch.Tensor, si
     dev = model.entity_embed.weight.device
     b = h.numel()
     if b == 0:
-        return torch.zeros((0,) if reduction == "none" else (), dtype=torch.float32, device=dev)
+        return O.empty_loss(model, reduction)
     h, t = ops.checked_ids(model.n_entities, h.to(dev), t.to(dev))          # (out-of-range ids never reach a kernel)
     (r,) = ops.checked_ids(model.n_relations, r.to(dev), what="relation")
     Q.check_known_device(known, dev)
-    cand = pos = None
-    if candidates is not None:                  # sorted: pos is increasing over the candidates, the bits ignore the order
-        (cand,) = ops.checked_ids(model.n_entities, candidates.to(dev), what="candidate entity")
-        ops.check_deferred_errors()
-        Q.check_unique(cand)
-        if cand.numel() == 0:
-            raise ValueError("candidates must hold at least one entity id")
-        cand = torch.sort(cand).values
-        pos = torch.full((model.n_entities,), -1, dtype=torch.int32, device=dev)
-        pos[cand] = torch.arange(cand.numel(), dtype=torch.int32, device=dev)
+    cand, pos = O.candidate_block(model, candidates, dev)
+    if pos is not None:
         missing = int((pos[t if side == "tail" else h] < 0).sum())
         if missing:
             raise ValueError(f"{missing} of the {b} true {'tails' if side == 'tail' else 'heads'} are not among the "
                              "candidates: every truth must be a candidate")
-    model.device = dev
-    table = model._table_for_inference()       # training or grad enabled: gat_embeddings() with its graph; else the kept table
-    Q.check_table_shape(model, scoring, table)
-    rows = table if cand is None else pruned.gather_rows(table, cand)      # gathered once for every relation group
-    if scoring == "transr":
-        perm, seg = ops.group_by_key(r, model.n_relations)
-        perm, seg = perm.long(), seg.tolist()
-        parts = []
-        for rr in range(model.n_relations):
-            if seg[rr + 1] > seg[rr]:
-                at = perm[seg[rr]:seg[rr + 1]]
-                parts.append(_side_losses(model, scoring, side, table, rows, model.gat_trans_M[rr], h[at], r[at], t[at],
-                                          scale, splits, known, pos))
-        back = torch.empty_like(perm)
-        back[perm] = torch.arange(b, device=dev)
-        loss = torch.cat(parts)[back]
-    else:
-        loss = _side_losses(model, scoring, side, table, rows, None, h, r, t, scale, splits, known, pos)
-    if reduction == "mean":
-        return loss.mean()
-    return loss.sum() if reduction == "sum" else loss
+
+    def score_group(table, rows, w, r, h, t):
+        """per triple of one projection the loss of the side (the mean of the two sides' for 'both'); known / pos: the
+        exclusion lists of ops.softmax_excluded per side"""
+        p = O.projected(rows, w)                                # alive until the backward pass (transr: N x relation_dim)
+        total = None
+        for s_ in Q.rank_sides(side):
+            ent, truth = (h, t) if s_ == "tail" else (t, h)
+            q = O.query_rows(model, scoring, s_, table, p, w, ent, r, pos)
+            if pos is not None:
+                truth = pos[truth].long()                       # (every truth is a candidate: checked above)
+            exclude = None
+            if known is not None:
+                exclude = ops.softmax_excluded(known.for_side(s_), ent, O.known_relations(scoring, r), truth, p.shape[0],
+                                               pos)
+            loss = ops.softmax_all_loss(q, p, truth, distance=scoring != "dot", scale=scale, splits=splits,
+                                        exclude=exclude)
+            total = loss if total is None else total + loss
+        return total if side != "both" else 0.5 * total
+
+    return O.all_entity_loss(model, scoring, r, (h, t), cand, reduction, score_group)

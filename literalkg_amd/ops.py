@@ -2963,13 +2963,23 @@ def softmax_chunk_width(n_q: int, n_c: int, chunk_bytes: int = SOFTMAX_CHUNK_BYT
     return min(max(n_c, 1), max(256, int(chunk_bytes) // (4 * max(n_q, 1)) // 256 * 256))
 
 
-def _softmax_operands(what: str, q, p, truth, pn=None):
-    _need_gpu(q, p, truth, pn)
-    q, p, truth = _f32_rows(q), _f32_rows(p), _i64(truth.reshape(-1))
-    if p.shape[1] != q.shape[1] or q.shape[1] == 0 or p.shape[0] == 0 or truth.numel() != q.shape[0] or \
-            (pn is not None and pn.numel() != p.shape[0]):
-        raise ValueError(f"{what}: queries {tuple(q.shape)}, candidates {tuple(p.shape)}, {truth.numel()} truths")
-    return q, p, truth
+def all_entity_operands(what: str, q, p, pn=None, truth=None, bias=None):
+    """(q, p, truth, bias) of a loss over every row of p (the softmax's and the sigmoid's), checked: float32 rows of one
+    width on the device, one squared norm per candidate, and per query one truth (int64) / one bias (float32) where the
+    loss has them (None stays None)."""
+    _need_gpu(q, p, truth, bias, pn)
+    q, p = _f32_rows(q), _f32_rows(p)
+    truth = _i64(truth.reshape(-1)) if truth is not None else None
+    if p.shape[1] != q.shape[1] or q.shape[1] == 0 or p.shape[0] == 0 or (pn is not None and pn.numel() != p.shape[0]) or \
+            (truth is not None and truth.numel() != q.shape[0]):
+        raise ValueError(f"{what}: queries {tuple(q.shape)}, candidates {tuple(p.shape)}" +
+                         (f", {truth.numel()} truths" if truth is not None else ""))
+    if bias is not None:
+        if bias.dtype != torch.float32 or bias.numel() != q.shape[0]:
+            raise ValueError(f"{what}: bias must be float32[{q.shape[0]}] (one per query), got {bias.dtype} "
+                             f"{tuple(bias.shape)}")
+        bias = bias.reshape(-1).contiguous()
+    return q, p, truth, bias
 
 
 def softmax_excluded(filt, filter_row: torch.Tensor, filter_rel: torch.Tensor, truth: torch.Tensor, n_cand: int,
@@ -3010,14 +3020,34 @@ def softmax_excluded(filt, filter_row: torch.Tensor, filter_rel: torch.Tensor, t
     return xptr, xcol
 
 
-def _softmax_exclude(what: str, exclude, b: int):
-    """(xptr, xcol) of an ``exclude`` argument, checked: int32 device tensors, xptr with one entry per query and one more"""
-    xptr, xcol = exclude
-    _need_gpu(xptr, xcol)
-    if xptr.dtype != torch.int32 or xcol.dtype != torch.int32 or xptr.dim() != 1 or xcol.dim() != 1 or \
-            xptr.numel() != b + 1:
-        raise ValueError(f"{what}: exclude must be (xptr int32[{b + 1}], xcol int32[M]) as softmax_excluded returns them")
-    return xptr.contiguous(), xcol.contiguous()
+def list_pair(what: str, name: str, lists, b: int):
+    """(ptr, col) of an ``exclude`` or ``positives`` argument ``name``, checked: int32 device tensors as softmax_excluded
+    returns them, ptr with one entry per query and one more.  None: (None, None), no lists at all."""
+    if lists is None:
+        return None, None
+    ptr, col = lists
+    _need_gpu(ptr, col)
+    if ptr.dtype != torch.int32 or col.dtype != torch.int32 or ptr.dim() != 1 or col.dim() != 1 or ptr.numel() != b + 1:
+        raise ValueError(f"{what}: {name} must be (ptr int32[{b + 1}], col int32[M]) as softmax_excluded returns them")
+    return ptr.contiguous(), col.contiguous()
+
+
+def chunk_range(what: str, c0, c1, n: int):
+    """(c0, c1) of a weights call as ints (c1 None: n), within the table's n candidates"""
+    c0, c1 = int(c0), n if c1 is None else int(c1)
+    if not 0 <= c0 <= c1 <= n:
+        raise ValueError(f"{what}: the chunk [{c0}, {c1}) does not lie in [0, {n}]")
+    return c0, c1
+
+
+def weights_out(what: str, out: Optional[torch.Tensor], b: int, width: int, dev) -> torch.Tensor:
+    """The b x width output of a weights call: ``out`` (its row stride is free), or a new tensor without one"""
+    if out is None:
+        return torch.empty((b, width), dtype=torch.float32, device=dev)
+    if b and (tuple(out.shape) != (b, width) or out.dtype != torch.float32 or (out.numel() and out.stride(1) != 1) or
+              (b > 1 and out.stride(0) < width)):
+        raise ValueError(f"{what}: out must be a float32 {b} x {width} tensor with unit column stride")
+    return out
 
 
 def softmax_all_forward(q: torch.Tensor, p: torch.Tensor, pn: Optional[torch.Tensor], truth: torch.Tensor,
@@ -3028,10 +3058,9 @@ def softmax_all_forward(q: torch.Tensor, p: torch.Tensor, pn: Optional[torch.Ten
     truth outside [0, N) is clamped (callers hand in checked ids).  exclude = (xptr, xcol) of softmax_excluded: query i
     drops the candidates xcol[xptr[i] : xptr[i + 1]] before the running (max, sum) sees them
     (lkg_softmax_all_partial_masked_f32); its truth must not be among them.  None: the unmasked launch."""
-    q, p, truth = _softmax_operands("softmax_all_forward", q, p, truth, pn)
+    q, p, truth, _ = all_entity_operands("softmax_all_forward", q, p, pn, truth)
     scale, splits, _ = check_softmax_args(scale, splits)
-    if exclude is not None:
-        exclude = _softmax_exclude("softmax_all_forward", exclude, q.shape[0])
+    xptr, xcol = list_pair("softmax_all_forward", "exclude", exclude, q.shape[0])
     (b, k), n, dev = q.shape, p.shape[0], q.device
     lse = torch.empty((2, b), dtype=torch.float32, device=dev)
     loss = torch.empty(b, dtype=torch.float32, device=dev)
@@ -3039,12 +3068,12 @@ def softmax_all_forward(q: torch.Tensor, p: torch.Tensor, pn: Optional[torch.Ten
         return lse, loss
     s_ = softmax_all_splits(b, n, splits)
     ws = torch.empty((2, s_, b), dtype=torch.float32, device=dev)
-    if exclude is None:
+    if xptr is None:
         N.call("lkg_softmax_all_partial_f32", b, n, k, N.ptr(q), _ld(q), N.ptr(p), _ld(p), N.ptr(pn), scale, s_,
                N.ptr(ws[0]), N.ptr(ws[1]), _stream())
     else:
         N.call("lkg_softmax_all_partial_masked_f32", b, n, k, N.ptr(q), _ld(q), N.ptr(p), _ld(p), N.ptr(pn), scale, s_,
-               N.ptr(exclude[0]), N.ptr(exclude[1]), exclude[1].numel(), N.ptr(ws[0]), N.ptr(ws[1]), _stream())
+               N.ptr(xptr), N.ptr(xcol), xcol.numel(), N.ptr(ws[0]), N.ptr(ws[1]), _stream())
     N.call("lkg_softmax_all_finish_f32", b, n, k, N.ptr(q), _ld(q), N.ptr(p), _ld(p), N.ptr(pn), N.ptr(truth), scale, s_,
            N.ptr(ws[0]), N.ptr(ws[1]), N.ptr(lse[0]), N.ptr(lse[1]), N.ptr(loss), _stream())
     return lse, loss
@@ -3057,48 +3086,80 @@ def softmax_all_weights(q: torch.Tensor, p: torch.Tensor, pn: Optional[torch.Ten
     V[i, c] = scale beta g[i] (exp(z_ic - lse[i]) - [c == truth[i]]), beta = 1 with pn, 1/2 without.  lse: float32[2, B]
     as softmax_all_forward returns it (the rounded value and its remainder), or float32[B] (no remainder).  exclude as in
     softmax_all_forward (positions of the whole table): a dropped candidate's weight is exactly 0."""
-    q, p, truth = _softmax_operands("softmax_all_weights", q, p, truth, pn)
-    if exclude is not None:
-        exclude = _softmax_exclude("softmax_all_weights", exclude, q.shape[0])
+    q, p, truth, _ = all_entity_operands("softmax_all_weights", q, p, pn, truth)
+    xptr, xcol = list_pair("softmax_all_weights", "exclude", exclude, q.shape[0])
     _need_gpu(lse, g, out)
     scale = check_softmax_args(scale, 0)[0]
     (b, k), n = q.shape, p.shape[0]
-    c1 = n if c1 is None else int(c1)
-    c0 = int(c0)
-    if not 0 <= c0 <= c1 <= n:
-        raise ValueError(f"softmax_all_weights: the chunk [{c0}, {c1}) does not lie in [0, {n}]")
+    c0, c1 = chunk_range("softmax_all_weights", c0, c1, n)
     lse, g = lse.reshape(-1, b).contiguous() if b else lse.reshape(-1, 0), g.reshape(-1).contiguous()
     if lse.shape[0] not in (1, 2) or g.numel() != b or lse.dtype != torch.float32 or g.dtype != torch.float32:
         raise ValueError(f"softmax_all_weights: lse must be float32[{b}] or [2, {b}], g float32[{b}]")
+    out = weights_out("softmax_all_weights", out, b, c1 - c0, q.device)
     if b == 0:
-        return out if out is not None else torch.empty((0, c1 - c0), dtype=torch.float32, device=q.device)
-    if out is None:
-        out = torch.empty((b, c1 - c0), dtype=torch.float32, device=q.device)
-    elif tuple(out.shape) != (b, c1 - c0) or out.dtype != torch.float32 or (out.numel() and out.stride(1) != 1) or \
-            (b > 1 and out.stride(0) < c1 - c0):
-        raise ValueError(f"softmax_all_weights: out must be a float32 {b} x {c1 - c0} tensor with unit column stride")
+        return out
     pc = p[c0:c1]
     head = [b, c1 - c0, k, N.ptr(q), _ld(q), N.ptr(pc), _ld(p), N.ptr(pn[c0:c1]) if pn is not None else None, c0,
             N.ptr(truth), N.ptr(lse[0]), N.ptr(lse[1]) if lse.shape[0] == 2 else None, N.ptr(g), scale]
-    if exclude is None:
+    if xptr is None:
         N.call("lkg_softmax_all_weights_f32", *head, N.ptr(out), max(_ld(out), c1 - c0), _stream())
     else:
-        N.call("lkg_softmax_all_weights_masked_f32", *head, N.ptr(exclude[0]), N.ptr(exclude[1]), exclude[1].numel(),
-               N.ptr(out), max(_ld(out), c1 - c0), _stream())
+        N.call("lkg_softmax_all_weights_masked_f32", *head, N.ptr(xptr), N.ptr(xcol), xcol.numel(), N.ptr(out),
+               max(_ld(out), c1 - c0), _stream())
     return out
+
+
+def all_entity_backward(q: torch.Tensor, p: torch.Tensor, pn: Optional[torch.Tensor], width: int, want_q: bool,
+                        want_p: bool, fill_v, after_v=None):
+    """(dq, dp) of a loss over ALL rows of p whose logits are those of softmax_all_forward (None for a gradient nobody
+    wants, whose product is not launched): per chunk of ``width`` candidates fill_v(c0, c1, out) stores the weights
+    V[:, c0:c1] = dL/dz (times scale beta) into ``out`` and returns it, after_v(c0, c1) (optional) does what else the loss
+    needs of them, then dQ += 2 V P_chunk in slices of SOFTMAX_DQ_SLICE candidates and dP_chunk = 2 V^T Q -
+    2 diag(colsum V) P_chunk (pn None, the dot product: 2 V^T Q) on ops.gemm.  Both products run with beta = 1 onto an
+    initialised output: lkg_gemm_f32 splits a beta = 0 product with a long reduction over float atomics, whose sum changes
+    from run to run."""
+    (b, k), n, dev = q.shape, p.shape[0], q.device
+    if b == 0:
+        return (torch.zeros((0, k), dtype=torch.float32, device=dev) if want_q else None,
+                torch.zeros((n, k), dtype=torch.float32, device=dev) if want_p else None)
+    vbuf = torch.empty((b, width), dtype=torch.float32, device=dev)
+    dq = torch.zeros((b, k), dtype=torch.float32, device=dev) if want_q else None
+    dp = torch.empty((n, k), dtype=torch.float32, device=dev) if want_p else None
+    if want_p and pn is not None:
+        # colsum V rides in the product as a column of ones next to Q (k + 1 columns fill the same 128-wide tiles as
+        # k = 300): lkg_colsum_f32 adds its partial sums with float atomics, whose order changes from run to run
+        q1 = torch.cat((q, torch.ones((b, 1), dtype=torch.float32, device=dev)), dim=1)
+        tmp = torch.empty((width, k + 1), dtype=torch.float32, device=dev)
+    for c0 in range(0, n, width):                  # a fixed order: dQ accumulates slice after slice, chunk after chunk
+        c1 = min(n, c0 + width)
+        v = fill_v(c0, c1, vbuf[:, :c1 - c0])
+        if after_v is not None:
+            after_v(c0, c1)
+        pc = p[c0:c1]
+        if want_q:
+            for s0 in range(0, c1 - c0, SOFTMAX_DQ_SLICE):
+                s1 = min(c1 - c0, s0 + SOFTMAX_DQ_SLICE)
+                gemm(v[:, s0:s1], pc[s0:s1], alpha=2.0, beta=1.0, out=dq)
+        if want_p:
+            dpc = dp[c0:c1]                        # written once
+            if pn is not None:
+                t = tmp[:c1 - c0].zero_()
+                gemm(v, q1, trans_a=True, alpha=2.0, beta=1.0, out=t)          # [2 V^T Q | 2 colsum V]
+                torch.addcmul(t[:, :k], t[:, k:], pc, value=-1.0, out=dpc)
+            else:
+                gemm(v, q, trans_a=True, alpha=2.0, beta=1.0, out=dpc.zero_())
+    return dq, dp
 
 
 class _SoftmaxAllLoss(Function):
     """loss_i = logsumexp_c z_ic - z_i,truth_i over ALL rows of p.  Forward: two launches, nothing of size B x N.  Backward:
-    per chunk of candidates the weights V (lkg_softmax_all_weights_f32), then dQ += 2 V P_chunk and dP_chunk = 2 V^T Q -
-    2 diag(colsum V) P_chunk on ops.gemm.  Both products run with beta = 1 onto an initialised output: lkg_gemm_f32 splits
-    a beta = 0 product with a long reduction over float atomics, whose sum changes from run to run; for the same reason
-    the column sums come out of the second product (a column of ones next to Q), not from ops.colsum.  With exclusion
-    lists (xptr, xcol) the masked kernels run instead: V has exact zeros at the dropped positions, the products are the same."""
+    all_entity_backward with the weights V of lkg_softmax_all_weights_f32; the column sums come out of its second product
+    for the reason its products run with beta = 1.  With exclusion lists (xptr, xcol) the masked kernels run instead: V has
+    exact zeros at the dropped positions, the products are the same."""
 
     @staticmethod
     def forward(ctx, q, p, truth, distance, scale, splits, chunk_bytes, xptr=None, xcol=None):
-        q_, p_, truth = _softmax_operands("softmax_all_loss", q, p, truth)
+        q_, p_, truth, _ = all_entity_operands("softmax_all_loss", q, p, None, truth)
         pn = rank_sqnorm(p_) if distance else None
         exclude = (xptr, xcol) if xptr is not None else None
         lse, loss = softmax_all_forward(q_, p_, pn, truth, scale, splits, exclude)
@@ -3112,36 +3173,13 @@ class _SoftmaxAllLoss(Function):
         exclude = (xptr, xcol) if xptr is not None else None
         scale, chunk_bytes = ctx.meta
         want_q, want_p = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        (b, k), n, dev = q.shape, p.shape[0], q.device
-        dq = torch.zeros((b, k), dtype=torch.float32, device=dev) if want_q else None
-        dp = torch.empty((n, k), dtype=torch.float32, device=dev) if want_p else None
-        if b == 0:
-            return dq, dp.zero_() if want_p else None, None, None, None, None, None, None, None
         g = g.reshape(-1).float().contiguous()
-        width = softmax_chunk_width(b, n, chunk_bytes)
-        vbuf = torch.empty((b, width), dtype=torch.float32, device=dev)
-        if want_p and pn is not None:
-            # colsum V rides in the product as a column of ones next to Q (k + 1 columns fill the same 128-wide tiles as
-            # k = 300): lkg_colsum_f32 adds its partial sums with float atomics, whose order changes from run to run
-            q1 = torch.cat((q, torch.ones((b, 1), dtype=torch.float32, device=dev)), dim=1)
-            tmp = torch.empty((width, k + 1), dtype=torch.float32, device=dev)
-        for c0 in range(0, n, width):                  # a fixed order: dQ accumulates slice after slice, chunk after chunk
-            c1 = min(n, c0 + width)
-            v = softmax_all_weights(q, p, pn, truth, lse, g, scale, c0, c1, out=vbuf[:, :c1 - c0], exclude=exclude)
-            pc = p[c0:c1]
-            if want_q:
-                for s0 in range(0, c1 - c0, SOFTMAX_DQ_SLICE):
-                    s1 = min(c1 - c0, s0 + SOFTMAX_DQ_SLICE)
-                    gemm(v[:, s0:s1], pc[s0:s1], alpha=2.0, beta=1.0, out=dq)
-            if want_p:
-                dpc = dp[c0:c1]                        # written once
-                if pn is not None:
-                    t = tmp[:c1 - c0].zero_()
-                    gemm(v, q1, trans_a=True, alpha=2.0, beta=1.0, out=t)          # [2 V^T Q | 2 colsum V]
-                    torch.addcmul(t[:, :k], t[:, k:], pc, value=-1.0, out=dpc)
-                else:
-                    gemm(v, q, trans_a=True, alpha=2.0, beta=1.0, out=dpc.zero_())
-        return dq, dp, None, None, None, None, None, None, None
+
+        def fill(c0, c1, out):
+            return softmax_all_weights(q, p, pn, truth, lse, g, scale, c0, c1, out=out, exclude=exclude)
+
+        width = softmax_chunk_width(q.shape[0], p.shape[0], chunk_bytes)
+        return all_entity_backward(q, p, pn, width, want_q, want_p, fill) + (None,) * 7
 
 
 def softmax_all_loss(q: torch.Tensor, p: torch.Tensor, truth: torch.Tensor, distance: bool = True, scale: float = 1.0,
@@ -3156,5 +3194,5 @@ def softmax_all_loss(q: torch.Tensor, p: torch.Tensor, truth: torch.Tensor, dist
     truth must not be listed) and those rows of p get no gradient from row i.  None: the unfiltered launches, bit for bit."""
     _need_gpu(q, p, truth)
     scale, splits, chunk_bytes = check_softmax_args(scale, splits, chunk_bytes)
-    xptr, xcol = _softmax_exclude("softmax_all_loss", exclude, truth.numel()) if exclude is not None else (None, None)
+    xptr, xcol = list_pair("softmax_all_loss", "exclude", exclude, truth.numel())
     return _SoftmaxAllLoss.apply(q, p, truth, bool(distance), scale, splits, chunk_bytes, xptr, xcol)

@@ -29,10 +29,10 @@ import torch
 from torch.autograd import Function
 
 from . import _native as N
+from . import _objectives as O
 from . import _queries as Q
 from . import ops, pruned
-from .kvs_all import check_margin
-from .one_vs_all import check_reduction
+from ._objectives import check_margin, check_reduction
 
 MLP_MESSAGE = ("scoring='mlp' has no self-adversarial loss: the pair head is trained by train_MLP on labelled pairs -- use "
                "'transr', 'transe' or 'dot'")
@@ -139,8 +139,7 @@ def _group_losses(scoring: str, side: str, w, rows, gr: int, e, margin, scale, t
     """float32[gr]: the losses of the gr groups of one projection.  rows: their gathered table rows, the gr anchors, then the
     gr positives, then the gr K negatives; e: their relation rows (None for 'dot'); w: gat_trans_M[r] for 'transr' (ONE
     product projects the anchors, the positives and the negatives), else None."""
-    if w is not None:
-        rows = ops.matmul(rows, w)
+    rows = O.projected(rows, w)
     q, p, n = rows[:gr], rows[gr:2 * gr], rows[2 * gr:]
     distance = scoring != "dot"
     if distance:
@@ -151,16 +150,10 @@ def _group_losses(scoring: str, side: str, w, rows, gr: int, e, margin, scale, t
 def _side_losses(model, scoring: str, side: str, table, h, r, t, neg, margin, scale, temperature):
     """float32[G], in the caller's order: the losses of the groups (h, r, t, neg) -- ids already checked and relabelled for
     ``table`` -- corrupted on ``side``."""
-    dev, g = table.device, h.numel()
     anchor, pos = (h, t) if side == "tail" else (t, h)
     kn = neg.shape[1]
-    if scoring == "transr":                     # the groups in relation order: a relation's rows are ONE slice of the gather
-        perm, seg = ops.group_by_key(r, model.n_relations)
-        perm, seg = perm.long(), seg.tolist()
-        anchor, pos, neg, r = anchor[perm], pos[perm], neg[perm], r[perm]
-        spans = [(seg[rr], seg[rr + 1], rr) for rr in range(model.n_relations) if seg[rr + 1] > seg[rr]]
-    else:
-        spans = [(0, g, None)]
+    perm, spans = O.relation_groups(model, scoring, r)      # relation order: a relation's rows are ONE slice of the gather
+    anchor, pos, neg, r = O.in_group_order(perm, anchor, pos, neg, r)
     ids = [x for s0, s1, _ in spans for x in (anchor[s0:s1], pos[s0:s1], neg[s0:s1].reshape(-1))]
     # ONE gather of the (2 + K) G rows: its backward is one scatter into a table-sized gradient, not one per operand
     rows = pruned.gather_rows(table, torch.cat(ids))
@@ -171,11 +164,7 @@ def _side_losses(model, scoring: str, side: str, table, h, r, t, neg, margin, sc
         parts.append(_group_losses(scoring, side, w, rows[s0 * (2 + kn):s1 * (2 + kn)], s1 - s0,
                                    e[s0:s1] if e is not None else None,
                                    margin, scale, temperature))
-    if scoring == "transr":
-        back = torch.empty_like(perm)
-        back[perm] = torch.arange(g, device=dev)
-        return torch.cat(parts)[back]
-    return parts[0]
+    return O.in_caller_order(perm, parts)
 
 
 def losses_by_side(model, scoring: str, h, r, t, neg, parts, margin, scale, temperature):
@@ -201,8 +190,7 @@ def self_adversarial_loss(model, h: torch.Tensor, r: torch.Tensor, t: torch.Tens
     'head' (they replace the head), margin any finite number, scale > 0, temperature >= 0, reduction 'mean' / 'sum' /
     'none' over the groups, scoring 'transr' / 'transe' / 'dot' (default: model.scoring).  Differentiable in every
     parameter the table, the relation embeddings and (transr) gat_trans_M depend on."""
-    if not hasattr(model, "_table_for_inference"):          # (ShardedLiteralKG: its table is a block per rank)
-        raise NotImplementedError(SHARDED_MESSAGE)
+    O.check_single_device(model, SHARDED_MESSAGE)
     side = Q.check_one_side(side, "the negatives replace one side of the triple")
     scoring = Q.resolve_scoring(model, scoring, MLP_MESSAGE)
     reduction = check_reduction(reduction)
@@ -215,9 +203,5 @@ def self_adversarial_loss(model, h: torch.Tensor, r: torch.Tensor, t: torch.Tens
                          f"({h.numel()} rows)")
     Q.check_transr_model(model, scoring)
     if h.numel() == 0:
-        dev = model.entity_embed.weight.device
-        return torch.zeros((0,) if reduction == "none" else (), dtype=torch.float32, device=dev)
-    loss = losses_by_side(model, scoring, h, r, t, neg, [(side, None)], margin, scale, temperature)[0]
-    if reduction == "mean":
-        return loss.mean()
-    return loss.sum() if reduction == "sum" else loss
+        return O.empty_loss(model, reduction)
+    return O.reduce(losses_by_side(model, scoring, h, r, t, neg, [(side, None)], margin, scale, temperature)[0], reduction)
