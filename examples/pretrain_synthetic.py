@@ -47,14 +47,17 @@ def main():
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--batch-groups", type=int, default=683)
     ap.add_argument("--lr", type=float, default=1e-4)
-    ap.add_argument("--objective", choices=("sampled", "one_vs_all", "kvs_all", "self_adversarial"), default="sampled",
+    ap.add_argument("--objective", choices=("sampled", "one_vs_all", "kvs_all", "self_adversarial", "relation"),
+                    default="sampled",
                     help="sampled: the reference's loss over pre_training_neg_rate sampled negatives (mode='pre_training'); "
                          "one_vs_all: cross-entropy of the true tail against the softmax over every entity "
                          "(mode='one_vs_all'; the sampled negatives of the batch are not used); "
                          "kvs_all: one row per DISTINCT query (h, r, ?) of the batch against every entity, binary "
                          "cross-entropy against all its known tails among the training triples (calc_kvs_all_loss); "
                          "self_adversarial: each positive against its --neg-rate sampled negatives, weighted by the model's "
-                         "own softmax over the group at --temperature (calc_self_adversarial_loss)")
+                         "own softmax over the group at --temperature (calc_self_adversarial_loss); "
+                         "relation: cross-entropy of the true relation of (h, ?, t) against the softmax over every relation "
+                         "(calc_relation_loss; one triple per group, the sampled negatives are not used)")
     ap.add_argument("--neg-rate", type=int, default=3, help="sampled negatives per positive (the reference's "
                                                             "pre_training_neg_rate)")
     ap.add_argument("--temperature", type=float, default=1.0,
@@ -64,7 +67,8 @@ def main():
                     help="with --objective kvs_all or self_adversarial: the logits are margin - ||q - p||^2")
     ap.add_argument("--filtered", action="store_true",
                     help="with --objective one_vs_all: the other known tails of (h, r, ?) among the training triples leave "
-                         "the row's softmax (calc_one_vs_all_loss(known=...)), as filtered MRR drops them")
+                         "the row's softmax (calc_one_vs_all_loss(known=...)), as filtered MRR drops them; with --objective "
+                         "relation: the other known relations of (h, ?, t) do (calc_relation_loss(known=...))")
     ap.add_argument("--sampler", choices=("batch", "triples"), default="batch",
                     help="batch: the synthetic generate_kg_batch stand-in (tail negatives, made on the host); triples: with "
                          "--objective self_adversarial, an epoch over the shuffled training triples (TripleEpoch) with the "
@@ -76,8 +80,8 @@ def main():
     ap.add_argument("--subsampling", action="store_true",
                     help="with --sampler triples: weight every triple by 1 / sqrt(4 + its known tails + its known heads)")
     a = ap.parse_args()
-    if a.filtered and a.objective != "one_vs_all":
-        ap.error("--filtered goes with --objective one_vs_all")
+    if a.filtered and a.objective not in ("one_vs_all", "relation"):
+        ap.error("--filtered goes with --objective one_vs_all or relation")
     if a.sampler == "triples" and a.objective != "self_adversarial":
         ap.error("--sampler triples goes with --objective self_adversarial")
     if a.sampler != "triples" and (a.corrupt != "tail" or a.filter_negatives or a.subsampling):
@@ -125,6 +129,8 @@ def main():
             elif a.objective == "kvs_all":
                 ent, rel = distinct_queries(bh[::k], br[::k])
                 loss = model.calc_kvs_all_loss(ent, rel, known, margin=a.margin, label_smoothing=a.label_smoothing)
+            elif a.objective == "relation":
+                loss = model.calc_relation_loss(bh[::k], br[::k], bp[::k], known=known)    # (known is None without --filtered)
             elif a.filtered:
                 loss = model.calc_one_vs_all_loss(bh[::k], br[::k], bp[::k], known=known)
             elif a.objective == "one_vs_all":

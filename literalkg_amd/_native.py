@@ -153,6 +153,11 @@ SAMPLE_PROTOTYPES = {
     "lkg_relation_cardinality": [i64, i64, i64, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp],
     "lkg_answer_counts": [i64, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp],
 }
+# the fifth table: include/literalkg_hip_relation_train.h (the relation-slot training objective), mirrored the same way
+RELATION_TRAIN_PROTOTYPES = {
+    "lkg_relation_loss_fwd_f32": [i64, i32, i32, vp, i64, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, f32, vp, i64, vp, vp, vp],
+    "lkg_relation_loss_bwd_f32": [i64, i32, i32, vp, i64, i64, vp, i64, vp, f32, vp, vp, i64, vp, i64, vp, i64, vp],
+}
 _RESTYPE = {"lkg_last_error": C.c_char_p, "lkg_csr_build_device_workspace": C.c_int64,
             "lkg_gemm_tall_workspace": C.c_int64, "lkg_gemm_workspace": C.c_int64,
             "lkg_linear_act_layernorm_workspace": C.c_int64, "lkg_narrow_layer_bwd_workspace": C.c_int64,
@@ -180,7 +185,7 @@ def load():
             "literalkg_amd has no CPU fallback.")
     lib = C.CDLL(_LIB_PATH)
     for name, argtypes in list(PROTOTYPES.items()) + list(EXTRA_PROTOTYPES.items()) + list(TRAIN_PROTOTYPES.items()) + \
-            list(SAMPLE_PROTOTYPES.items()):
+            list(SAMPLE_PROTOTYPES.items()) + list(RELATION_TRAIN_PROTOTYPES.items()):
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
         fn.argtypes = argtypes
         fn.restype = _RESTYPE.get(name, C.c_int)

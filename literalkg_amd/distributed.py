@@ -634,6 +634,10 @@ class ShardedLiteralKG(nn.Module):
         from .self_adversarial import SHARDED_MESSAGE
         raise NotImplementedError(SHARDED_MESSAGE)
 
+    def calc_relation_loss(self, *args, **kwargs):
+        from .relation_loss import SHARDED_MESSAGE
+        raise NotImplementedError(SHARDED_MESSAGE)
+
     # ------------------------------------------------------------------ gradients / checkpoints
     def partial_grad_parameters(self) -> List[nn.Parameter]:
         """Replicated weights whose gradient is a partial sum over this rank's rows (a FIXED list: the same on every rank

@@ -606,6 +606,17 @@ class LiteralKG(nn.Module):
         return sampled_negative_loss(self, h, r, t, batch, weights=weights, margin=margin, scale=scale,
                                      temperature=temperature, reduction=reduction, scoring=scoring)
 
+    def calc_relation_loss(self, h, r, t, known=None, scoring: Optional[str] = None, scale: float = 1.0,
+                           reduction: str = "mean", chunk_bytes: int = 256 << 20):
+        """Relation-slot loss of the triples (h, r, t) (literalkg_amd/relation_loss.py): the cross-entropy of r against the
+        softmax over every relation of (h, ?, t), logits -scale ||(T[h] - T[t]) W_j + e_j||^2 ('transe': no W_j), with
+        ``known`` (a KnownTriples) the pair's other known relations left out -- the objective of
+        evaluate_relation_prediction's filtered metric.  Reads two table rows per pair, so prune_to_batch applies; no L2
+        term.  There is no mode= string for it."""
+        from .relation_loss import relation_loss
+        return relation_loss(self, h, r, t, known=known, scoring=scoring, scale=scale, reduction=reduction,
+                             chunk_bytes=chunk_bytes)
+
     def _rows_only_projection_applies(self) -> bool:
         """A loss that reads a few rows of linear_gat's output and has to run the encoder anyway (a training step, or any call
         with autograd on: the inference heads' kept table is for eval mode under no_grad)."""
