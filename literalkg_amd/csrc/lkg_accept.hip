@@ -11,7 +11,7 @@
 // Two passes over the same loop.  A 256-thread workgroup owns 64 query rows and a contiguous range of
 // 256-candidate tiles (split `split` of S).  After each tile's MFMAs every lane forms its 64 values and compares them
 // with the thresholds of their rows (staged in LDS with qn); only a lane with a pass goes on to the filter check
-// (tk_known of lkg_topk_common.h: binary search in the row's ascending col list, then the entry's relations).
+// (known_lookup of lkg_known.h).
 //   count: the lane adds its passes to the row's LDS counter; the workgroup leaves with one global add per row.
 //   emit : the lane takes a slot from the row's global cursor and writes (id, s, v) at base[row] + slot.  The slot is
 //          checked against the row's counted length first: a slot at or past it is NOT written and a flag is raised.
@@ -100,7 +100,7 @@ __global__ __launch_bounds__(TK_THREADS) void accept_kernel(
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
                         if (!((pass >> j) & 1u)) continue;
-                        if (rowptr && tk_known(rowptr, col, eptr, rel, frow[grow], (int)frel[grow], cid[j])) continue;
+                        if (rowptr && known_lookup(rowptr, col, eptr, rel, frow[grow], (int)frel[grow], cid[j])) continue;
                         if (EMIT) {
                             const int slot = atomicAdd(cursor + grow, 1);
                             if (slot >= 0 && slot < counts[grow]) {
@@ -140,7 +140,7 @@ int launch_accept(const char *name, int64_t n_q, int64_t n_cand, int32_t k, cons
     LKG_REQUIRE(q && p && thr && counts, "%s: null pointer", name);
     LKG_REQUIRE((pn == nullptr) == (qn == nullptr), "%s: pn and qn go together (both NULL: dot scoring)", name);
     LKG_REQUIRE(!EMIT || (base && cursor && out_ids && out_s && out_v && flag), "%s: null pointer", name);
-    LKG_REQUIRE(!rowptr || (filter_row && filter_rel && col && eptr && rel), "%s: incomplete filter", name);
+    LKG_REQUIRE(known_filter_complete(rowptr, filter_row, filter_rel, col, eptr, rel), "%s: incomplete filter", name);
     const int s_ = lkg_topk_splits(n_q, n_cand, splits);          // the same split policy as the top-k launch
     LKG_REQUIRE(s_ >= 1, "%s: no split count for these sizes", name);
     const long tiles_q = (n_q + TK_ROWS - 1) / TK_ROWS, tiles_c = (n_cand + TK_COLS - 1) / TK_COLS;

@@ -2,6 +2,7 @@
 // per-row walk through a sorted list of candidate positions -- the exclusion list of a filtered softmax row, the positives
 // of a KvsAll row -- and the host-side checks of the temperature.  The tile arithmetic is lkg_rank_common.h's.
 #pragma once
+#include "lkg_known.h"
 #include "lkg_rank_common.h"
 
 #include <climits>
@@ -21,13 +22,7 @@ __device__ __forceinline__ ListCursor list_seek(const int *__restrict__ ptr, con
         x.cur = min(max(ptr[row], 0), m_total);
         x.end = min(max(ptr[row + 1], x.cur), m_total);
     }
-    int lo = x.cur, hi = x.end;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (col[mid] < first) lo = mid + 1;
-        else hi = mid;
-    }
-    x.cur = lo;
+    x.cur = known_lower_bound(col, x.cur, x.end, first);
     if (x.cur < x.end) x.next = col[x.cur];
     return x;
 }

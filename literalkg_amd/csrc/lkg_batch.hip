@@ -4,6 +4,7 @@
 #include <algorithm>
 
 #include "lkg_common.h"
+#include "lkg_known.h"
 
 namespace {
 
@@ -336,12 +337,6 @@ extern "C" int lkg_gather_i64(int64_t n, const int64_t *src, const int32_t *perm
 // graphs with more than neg_rate + out-degree distinct tails).
 namespace {
 
-__device__ __forceinline__ unsigned long long mix64(unsigned long long z) {
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
 struct Draw {   // counter-based stream: value i of stream (seed, group)
     unsigned long long key;
     unsigned ctr;
@@ -349,17 +344,7 @@ struct Draw {   // counter-based stream: value i of stream (seed, group)
     __device__ long below(long n) { return (long)(next() % (unsigned long long)n); }
 };
 
-// entry holding raw edge k (eptr == nullptr: identity)
-__device__ __forceinline__ int entry_of_raw(const int *eptr, int nnz, int k) {
-    if (!eptr) return k;
-    int lo = 0, hi = nnz;   // last j with eptr[j] <= k
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (eptr[mid] <= k) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
+// (eptr == nullptr: every entry is one raw edge)
 __global__ void sample_kg_batch_kernel(long n_groups, int neg_rate, unsigned long long seed,
                                        const long *__restrict__ heads, long n_ent,
                                        const int *__restrict__ rowptr,
@@ -383,23 +368,16 @@ __global__ void sample_kg_batch_kernel(long n_groups, int neg_rate, unsigned lon
     // positive: uniform over the head's raw triples
     const int ep = e0 + (int)d.below(e1 - e0);
     const long r = rel[ep];
-    const long tp = col[entry_of_raw(eptr, nnz, ep)];
+    const long tp = col[eptr ? known_entry_of_raw(eptr, nnz, ep) : ep];
     long *ng = out_n + g * neg_rate;
     for (int k = 0; k < neg_rate; ++k) {
         long cand = 0;
         for (int tries = 0; tries < MAX_TRIES; ++tries) {
-            cand = col[entry_of_raw(eptr, nnz, (int)d.below(n_raw))];
-            bool reject = false;
-            // is (cand, r) a positive of h?  tails are ascending inside the row: binary search, then its relations
-            int lo = j0, hi = j1;
-            while (lo < hi) {
-                const int mid = (lo + hi) >> 1;
-                if (col[mid] < cand) lo = mid + 1; else hi = mid;
-            }
-            if (lo < j1 && col[lo] == cand) {
-                const int f0 = eptr ? eptr[lo] : lo, f1 = eptr ? eptr[lo + 1] : lo + 1;
-                for (int e = f0; e < f1; ++e) reject |= (rel[e] == r);
-            }
+            const int raw = (int)d.below(n_raw);
+            cand = col[eptr ? known_entry_of_raw(eptr, nnz, raw) : raw];
+            int en;   // is (cand, r) a positive of h?
+            bool reject = known_find(col, j0, j1, cand, en) &&
+                          known_among(rel, eptr ? eptr[en] : en, eptr ? eptr[en + 1] : en + 1, r);
             for (int q = 0; q < k && !reject; ++q) reject = (ng[q] == cand);
             if (!reject) break;
         }

@@ -296,13 +296,10 @@ __global__ __launch_bounds__(PM_THREADS) void pair_mlp_prepare_kernel(
                 long c = tr;
                 bool keep = false;
                 if (e < e1) {
-                    const int id = col[e];
-                    long cs = -1;
-                    if (id >= 0 && id < n_rows) cs = slot ? slot[id] : id;
+                    const long cs = known_slot<long>(slot, col[e], n_rows);
                     if (cs >= 0 && cs < n_c && cs != tr) {
                         c = cs;
-                        keep = want < 0;
-                        for (int x = eptr[e]; x < eptr[e + 1] && !keep; ++x) keep = rel[x] == want;
+                        keep = known_under(eptr, rel, e, want);
                     }
                 }
                 pm_load_v(vf, vt + c * ldv, s);
@@ -470,14 +467,12 @@ bool pm_operands_ok(const float *uq, long ldu, const float *v, long ldv, const f
            ldv >= PM_H1;
 }
 
-// What an entry point asks of its operands (`a`: its first table, `rest`: its other pointers that may not be null) and filter.
-// Statements of the entry point's body, which read its parameters v, w2, b2, w3, b3, ldu, ldv (and the filter's six) by name.
+// What an entry point asks of its operands (`a`: its first table, `rest`: its other pointers that may not be null).
+// Statements of the entry point's body, which read its parameters v, w2, b2, w3, b3, ldu, ldv by name.
 #define PM_REQUIRE_OPERANDS(name, a, rest)                                                                             \
     LKG_REQUIRE(a && v && w2 && b2 && w3 && b3 && rest, name ": null pointer");                                        \
     LKG_REQUIRE(pm_operands_ok(a, ldu, v, ldv, w2),                                                                    \
                 name ": " #a ", v and w2 must be 16-byte aligned with row strides that are multiples of 4 (at least 128)")
-#define PM_REQUIRE_FILTER(name) \
-    LKG_REQUIRE(!rowptr || (filter_row && filter_rel && col && eptr && rel), name ": incomplete filter")
 
 }  // namespace
 
@@ -518,7 +513,7 @@ extern "C" int lkg_pair_mlp_select_f32(int64_t n_q, int64_t n_cand, const float 
     LKG_REQUIRE(splits >= 1 && splits == lkg_pair_mlp_splits(n_q, n_cand, splits),
                 "lkg_pair_mlp_select_f32: splits must come from lkg_pair_mlp_splits");
     PM_REQUIRE_OPERANDS("lkg_pair_mlp_select_f32", uq, ws_s && ws_i);
-    PM_REQUIRE_FILTER("lkg_pair_mlp_select_f32");
+    LKG_REQUIRE(known_filter_complete(rowptr, filter_row, filter_rel, col, eptr, rel), "lkg_pair_mlp_select_f32: incomplete filter");
     const long qr = pm_select_rows(n_q);
     const long tiles_q = (n_q + qr - 1) / qr, tiles_c = (n_cand + PM_COLS - 1) / PM_COLS;
     LKG_REQUIRE(tiles_q * splits < INT32_MAX, "lkg_pair_mlp_select_f32: too many workgroups (split the queries)");
@@ -547,7 +542,7 @@ extern "C" int lkg_pair_mlp_prepare_f32(int64_t n_q, int64_t n_cand, const float
     LKG_REQUIRE(n_q >= 0 && n_cand > 0 && n_cand < INT32_MAX, "lkg_pair_mlp_prepare_f32: bad sizes");
     if (n_q == 0) return LKG_OK;
     PM_REQUIRE_OPERANDS("lkg_pair_mlp_prepare_f32", uq, truth && thr && better && equal);
-    PM_REQUIRE_FILTER("lkg_pair_mlp_prepare_f32");
+    LKG_REQUIRE(known_filter_complete(rowptr, filter_row, filter_rel, col, eptr, rel), "lkg_pair_mlp_prepare_f32: incomplete filter");
     LKG_REQUIRE(!rowptr || (n_rows > 0 && n_rows < INT32_MAX && (cand_slot || n_rows == n_cand)),
                 "lkg_pair_mlp_prepare_f32: the filter's rows must be the candidates, or come with cand_slot");
     const long blocks = (n_q + PM_PREP_WAVES - 1) / PM_PREP_WAVES;

@@ -16,6 +16,7 @@
 // operands come straight from global memory (the 4 waves share the query tile through L1, consecutive workgroups share
 // the candidate block through L2).  Per-row counts reduce in registers, across the 16 lanes of a row, across the waves
 // in LDS, and leave with one atomic per row per workgroup.  The B x N scores are never stored.
+#include "lkg_known.h"
 #include "lkg_rank_common.h"
 
 namespace {
@@ -141,11 +142,8 @@ __global__ __launch_bounds__(RK_THREADS) void rank_prepare_kernel(
             bool keep = false;
             if (e < e1) {
                 c = col[e];
-                if (c != tr && c >= 0 && c < n_c) {
-                    for (int x = eptr[e]; x < eptr[e + 1] && !keep; ++x) keep = rel[x] == want;
-                } else {
-                    c = tr;
-                }
+                if (c != tr && c >= 0 && c < n_c) keep = known_under_exact(eptr, rel, e, want);
+                else c = tr;
             }
             const float sc = rank_pair_scores<VEC>(qrow, p, ldp, pn, c, k);
             if (lane < 16 && keep) {
@@ -221,7 +219,7 @@ extern "C" int lkg_rank_prepare_f32(int64_t n_q, int64_t n_cand, int32_t k, cons
                 "lkg_rank_prepare_f32: bad sizes");
     if (n_q == 0) return LKG_OK;
     LKG_REQUIRE(q && p && truth && thr && better && equal, "lkg_rank_prepare_f32: null pointer");
-    LKG_REQUIRE(!rowptr || (filter_row && filter_rel && col && eptr && rel), "lkg_rank_prepare_f32: incomplete filter");
+    LKG_REQUIRE(known_filter_complete(rowptr, filter_row, filter_rel, col, eptr, rel), "lkg_rank_prepare_f32: incomplete filter");
     const dim3 grid((unsigned)((n_q + 3) / 4)), block(RK_THREADS);
     if (vec_ok(q, ldq, p, ldp))
         hipLaunchKernelGGL(rank_prepare_kernel<true>, grid, block, 0, (hipStream_t)stream, (long)n_q, (long)n_cand, k, q,

@@ -2,9 +2,8 @@
 // against the softmax over every relation.  With u_ij the pair's block under relation j (slab mode: u_ij = d_i W_j, row i
 // of the product D @ Wcat, block j at u + i * ldu + j * rel_stride; shared mode, rel_stride == 0: u_ij = d_i for every j)
 //     s_ij = sum_c (u_ijc + e_jc)^2,   z_ij = -scale s_ij,   loss_i = logsumexp_j z_ij - z_i,truth_i
-// over the eligible relations: with a filter (the CSR of lkg_csr_build_device, looked up as relation_order_kernel of
-// lkg_relations.hip does) every relation other than the truth under which the pair is known is stored as -inf.
-// DESIGN.md 3.6s.
+// over the eligible relations: with a filter (lkg_known.h) every relation other than the truth under which the pair is
+// known is stored as -inf.  DESIGN.md 3.6s.
 //
 // Tiling: one wave per pair, four waves per workgroup, a grid-stride loop under a grid cap.  A lane owns the 4-column units
 // lane, lane + 64, ... of a k-wide block (one 16-byte load each where k, the strides and the pointers allow it; four
@@ -29,6 +28,7 @@
 // on its own blocks, e, its truth and its filter entry alone.
 // Floating-point contraction is off in this file: every rounding is one the references count.
 #include "lkg_common.h"
+#include "lkg_known.h"
 
 #include "../../include/literalkg_hip_relation_train.h"
 
@@ -136,16 +136,10 @@ __global__ __launch_bounds__(RL_THREADS) void relation_loss_fwd_kernel(
         if (rowptr) {
             const long f = filter_row[i];
             const long want = filter_col[i];
-            const int end = rowptr[f + 1];
-            int lo = rowptr[f], hi = end;
-            while (lo < hi) {                                         // first entry with col >= want
-                const int mid = (lo + hi) >> 1;
-                if (col[mid] < want) lo = mid + 1;
-                else hi = mid;
-            }
-            if (lo < end && col[lo] == want) {
-                const int x1 = eptr[lo + 1];
-                for (int x = eptr[lo] + lane; x < x1; x += 64) {
+            int en;
+            if (known_find(col, rowptr[f], rowptr[f + 1], want, en)) {
+                const int x1 = eptr[en + 1];
+                for (int x = eptr[en] + lane; x < x1; x += 64) {
                     const int rr = rel[x];
                     if (rr >= 0 && rr < n_rel && rr != tj) zrow[rr] = -__builtin_inff();   // (duplicates write the same bits)
                 }
@@ -271,7 +265,7 @@ extern "C" int lkg_relation_loss_fwd_f32(int64_t n, int32_t n_rel, int32_t k, co
                 "lkg_relation_loss_fwd_f32: bad sizes (n >= 0, n_rel >= 1, k >= 1, lde >= k, ldz >= n_rel; rel_stride 0 with "
                 "ldu >= k, or rel_stride >= k with ldu >= (n_rel - 1) rel_stride + k)");
     LKG_REQUIRE(scale > 0.f && scale < __builtin_inff(), "lkg_relation_loss_fwd_f32: scale must be positive and finite");
-    LKG_REQUIRE(!rowptr || (filter_row && filter_col && col && eptr && rel),
+    LKG_REQUIRE(known_filter_complete(rowptr, filter_row, filter_col, col, eptr, rel),
                 "lkg_relation_loss_fwd_f32: a filter needs filter_row, filter_col, col, eptr and rel (null pointer)");
     if (n == 0) return LKG_OK;
     LKG_REQUIRE(u && e && truth && z && lse && loss, "lkg_relation_loss_fwd_f32: null pointer");

@@ -26,6 +26,7 @@
 // is read from the stored row, so a known truth keeps it, and the truth is skipped by id.  The selection is top_k rounds
 // of a wave arg-min over (score, id): every lane keeps the best of its own elements (j = lane, lane + 64, ...), the wave
 // reduces, the winner's slot becomes NaN and only its lane rescans.  Compares and integer adds only: no rounding enters.
+#include "lkg_known.h"
 #include "lkg_rank_common.h"
 
 #include <climits>
@@ -136,16 +137,10 @@ __global__ __launch_bounds__(RO_THREADS) void relation_order_kernel(
         if (rowptr) {
             const long f = filter_row[i];
             const long want = filter_col[i];
-            const int end = rowptr[f + 1];
-            int lo = rowptr[f], hi = end;
-            while (lo < hi) {                                         // first entry with col >= want
-                const int mid = (lo + hi) >> 1;
-                if (col[mid] < want) lo = mid + 1;
-                else hi = mid;
-            }
-            if (lo < end && col[lo] == want) {
-                const int x1 = eptr[lo + 1];
-                for (int x = eptr[lo] + lane; x < x1; x += 64) {
+            int en;
+            if (known_find(col, rowptr[f], rowptr[f + 1], want, en)) {
+                const int x1 = eptr[en + 1];
+                for (int x = eptr[en] + lane; x < x1; x += 64) {
                     const int rr = rel[x];
                     if (rr >= 0 && rr < n_rel) row[rr] = __builtin_nanf("");    // (duplicates write the same bits)
                 }
@@ -249,7 +244,7 @@ extern "C" int lkg_relation_order_f32(int64_t n, int32_t n_rel, const float *sco
     LKG_REQUIRE(truth || top_k > 0, "lkg_relation_order_f32: nothing to compute (no truth, top_k = 0)");
     LKG_REQUIRE(!truth || (better && equal), "lkg_relation_order_f32: a truth needs better and equal (null pointer)");
     LKG_REQUIRE(top_k == 0 || (top_ids && top_scores), "lkg_relation_order_f32: top_k needs top_ids and top_scores");
-    LKG_REQUIRE(!rowptr || (filter_row && filter_col && col && eptr && rel),
+    LKG_REQUIRE(known_filter_complete(rowptr, filter_row, filter_col, col, eptr, rel),
                 "lkg_relation_order_f32: a filter needs filter_row, filter_col, col, eptr and rel (null pointer)");
     if (n == 0) return LKG_OK;
     LKG_REQUIRE(scores, "lkg_relation_order_f32: null pointer");

@@ -199,8 +199,7 @@ __global__ __launch_bounds__(TK_THREADS) void retrieval_prepare_kernel(
                     const long sl = cand_slot ? cand_slot[id] : id;
                     if (sl >= 0 && sl < n_c) {
                         slot = sl;
-                        keep = want < 0;
-                        for (int x = eptr[e]; x < eptr[e + 1] && !keep; ++x) keep = rel[x] == want;
+                        keep = known_under(eptr, rel, e, want);
                     }
                 }
             }
@@ -308,7 +307,7 @@ extern "C" int lkg_retrieval_prepare_f32(int64_t n_rows, int64_t n_cand, int32_t
     LKG_REQUIRE(q && row_q && p && key_off && key_n && qkey_off && qkey_n && key_s && key_id && buckets,
                 "lkg_retrieval_prepare_f32: null pointer");
     LKG_REQUIRE(cand_slot || n_ids == n_cand, "lkg_retrieval_prepare_f32: without cand_slot the ids are the candidate rows");
-    LKG_REQUIRE(!rowptr || (filter_row && filter_rel && col && eptr && rel), "lkg_retrieval_prepare_f32: incomplete filter");
+    LKG_REQUIRE(known_filter_complete(rowptr, filter_row, filter_rel, col, eptr, rel), "lkg_retrieval_prepare_f32: incomplete filter");
     const dim3 grid((unsigned)((n_rows + 3) / 4)), block(TK_THREADS);
     const hipStream_t st = (hipStream_t)stream;
     if (vec_ok(q, ldq, p, ldp))

@@ -356,9 +356,8 @@ __global__ __launch_bounds__(SM_THREADS) void softmax_weights_masked_kernel(
 
 // The exclusion lists of the filtered loss, one wave per query and two passes (FILL false: cnt[i] = the length of query
 // i's list; a cumulative sum on the host side makes xptr; FILL true: the entries).  Query i walks the known row frow[i]
-// (rowptr / col / eptr / rel of lkg_csr_build_device: cols ascending and unique) 64 entries at a time and keeps an entry
-// iff it is known under relation frel[i] (< 0: under any), maps to a candidate (pos[entity], or the entity itself without
-// pos) and is not the row's truth.  pos is monotone where it is not -1, so the kept positions come out ascending.
+// (lkg_known.h) 64 entries at a time and keeps an entry iff it is known under relation frel[i], maps to a candidate through
+// pos and is not the row's truth.  pos is monotone where it is not -1, so the kept positions come out ascending.
 template <bool FILL>
 __global__ __launch_bounds__(SM_THREADS) void softmax_excluded_kernel(
     long n_q, long n_rows, long n_c, const long *__restrict__ frow, const long *__restrict__ frel,
@@ -378,12 +377,8 @@ __global__ __launch_bounds__(SM_THREADS) void softmax_excluded_kernel(
         bool keep = false;
         int c = -1;
         if (e < e1) {
-            const int ent = col[e];
-            if (ent >= 0 && ent < n_rows) c = pos ? pos[ent] : ent;
-            if (c >= 0 && c < n_c && c != tr) {
-                keep = want < 0;
-                for (int x = eptr[e]; x < eptr[e + 1] && !keep; ++x) keep = rel[x] == want;
-            }
+            c = known_slot<int>(pos, col[e], n_rows);
+            keep = c >= 0 && c < n_c && c != tr && known_under(eptr, rel, e, want);
         }
         const unsigned long long kept = __ballot(keep);
         if (FILL) {

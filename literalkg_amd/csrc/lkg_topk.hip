@@ -10,11 +10,10 @@
 // sentinel (+inf, INT32_MAX), which sorts after every real candidate -- and a queue of TQ candidates waiting to enter it.
 // The row's threshold is the list's last entry.  After each tile's MFMAs every lane compares its 64 scores with the
 // thresholds of their rows; only those that pass are pushed (an LDS atomic per push).  When a queue fills, the
-// workgroup merges every queue into its list: the filter check (binary search in the row's ascending col list, then a
-// scan of the entry's relations) and a merge by rank, one wave per row.  Candidates that did not fit are pushed again
-// against the tightened thresholds.  At the end each list goes to workspace [S][n_q][kk]; topk_merge_kernel merges the
-// S lists of a row into the final sorted, padded output.  The result is the kk smallest (s, id) of the whole candidate
-// set -- a unique set, whatever S, the query batch or the launch shape.
+// workgroup merges every queue into its list: the filter check (known_lookup of lkg_known.h) and a merge by rank, one wave
+// per row.  Candidates that did not fit are pushed again against the tightened thresholds.  At the end each list goes to
+// workspace [S][n_q][kk]; topk_merge_kernel merges the S lists of a row into the final sorted, padded output.  The result
+// is the kk smallest (s, id) of the whole candidate set -- a unique set, whatever S, the query batch or the launch shape.
 // The list, the queue and their merge live in lkg_topk_common.h (lkg_pairmlp.hip selects with them too).
 #include "lkg_rank_common.h"
 #include "lkg_topk_common.h"
@@ -243,7 +242,7 @@ extern "C" int lkg_topk_select_f32(int64_t n_q, int64_t n_cand, int32_t k, const
     LKG_REQUIRE(splits >= 1 && splits == lkg_topk_splits(n_q, n_cand, splits),
                 "lkg_topk_select_f32: splits must come from lkg_topk_splits");
     LKG_REQUIRE(q && p && ws_s && ws_i, "lkg_topk_select_f32: null pointer");
-    LKG_REQUIRE(!rowptr || (filter_row && filter_rel && col && eptr && rel), "lkg_topk_select_f32: incomplete filter");
+    LKG_REQUIRE(known_filter_complete(rowptr, filter_row, filter_rel, col, eptr, rel), "lkg_topk_select_f32: incomplete filter");
     const long tiles_q = (n_q + TK_ROWS - 1) / TK_ROWS, tiles_c = (n_cand + TK_COLS - 1) / TK_COLS;
     LKG_REQUIRE(tiles_q * splits < INT32_MAX, "lkg_topk_select_f32: too many workgroups (split the queries)");
     const dim3 grid((unsigned)(tiles_q * splits));

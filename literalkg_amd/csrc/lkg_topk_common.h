@@ -4,6 +4,7 @@
 // the smaller id, NaN never before anything; the sentinel (+inf, INT32_MAX) sorts after every real candidate.
 #pragma once
 #include "lkg_common.h"
+#include "lkg_known.h"
 
 #include <climits>
 
@@ -18,23 +19,6 @@ constexpr int TK_NONE = INT_MAX;     // the sentinel id
 
 // (a, ia) before (b, ib): float comparison of the scores, then the id; false whenever a is NaN
 __device__ __forceinline__ bool tk_before(float a, int ia, float b, int ib) { return a < b || (a == b && ia < ib); }
-
-// is (query row `f`, relation `want`, candidate id) a known triple?  want < 0: known under any relation
-__device__ __forceinline__ bool tk_known(const int *__restrict__ rowptr, const int *__restrict__ col,
-                                         const int *__restrict__ eptr, const int *__restrict__ rel, long f, int want,
-                                         int id) {
-    int lo = rowptr[f], hi = rowptr[f + 1];
-    while (lo < hi) {                          // first entry with col >= id
-        const int mid = (lo + hi) >> 1;
-        if (col[mid] < id) lo = mid + 1;
-        else hi = mid;
-    }
-    if (lo == rowptr[f + 1] || col[lo] != id) return false;
-    if (want < 0) return true;
-    for (int x = eptr[lo]; x < eptr[lo + 1]; ++x)
-        if (rel[x] == want) return true;
-    return false;
-}
 
 template <int KC>
 struct TopkSmem {
@@ -68,7 +52,7 @@ __device__ void topk_merge_queues(TopkSmem<KC> &sm, int kk, long q0, long n_q, c
             xi = sm.qi[row][lane];
             xv = true;
             if (rowptr && q0 + row < n_q)
-                xv = !tk_known(rowptr, col, eptr, rel, frow[q0 + row], (int)frel[q0 + row], xi);
+                xv = !known_lookup(rowptr, col, eptr, rel, frow[q0 + row], (int)frel[q0 + row], xi);
         }
         const unsigned long long kept = __ballot(xv);
         float y0s = __builtin_inff(), y1s = __builtin_inff();

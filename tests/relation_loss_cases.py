@@ -164,6 +164,14 @@ def triples_of_mask(mask, truth, n_entities_offset: int = 0):
     return kh, kr, kt, h, t
 
 
+def tails_around(h, t, n_entities: int):
+    """(kh, kt): rows that are not empty and do not hold (h_i, t_i).  Every row h_i holds the tail h_i (< t_i: the row's
+    last entry lies below the wanted one) and every second row also t_i + 1 where that is an entity (an entry above it)."""
+    up = t[::2] + 1
+    ok = up < n_entities
+    return torch.cat((h, h[::2][ok])), torch.cat((h, up[ok]))
+
+
 # ----------------------------------------------------------------------------- references
 def slab_of(d, w, n_rel: int, dtype=torch.float64):
     """u3[P, R, D] in dtype: d_i W_j, or d_i for every j without w"""

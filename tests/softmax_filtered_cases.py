@@ -145,6 +145,13 @@ def excluded_reference(filt, filter_row, filter_rel, truth, n_cand: int, pos=Non
     return out
 
 
+# The smallest structure that reaches every branch of a walk over a known row: 5 entities, 6 triples (h, r, t), the pair
+# (0, 1) under both relations, entity 4 in no triple.  On either side the queries (row, relation, truth) meet: an empty row;
+# a row with one entry under the wanted relation and one under the other only; any relation; the truth among the entries.
+TINY_TRIPLES = ([0, 0, 0, 2, 2, 3], [0, 1, 0, 1, 0, 1], [1, 1, 3, 3, 0, 2])
+TINY_QUERIES = ([4, 0, 2, 3], [0, 1, -1, 0], [0, 4, 0, 4])
+
+
 def shapes(ks=(1, 17, 300)):
     """(b, n, k): every b of {1, 65, 130}, n of {1, 255, 257, 1000, 70 001} and k of ks with every value of the other two
     lists in turn (a third of the product), the largest of all three together included"""

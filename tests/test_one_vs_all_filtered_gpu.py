@@ -248,6 +248,15 @@ def test_softmax_excluded_equals_the_double_loop(L, ops, gpu_device, side):
         assert torch.equal(xptr.cpu(), wp) and torch.equal(xcol.cpu(), wc), (side, b, "pos")
     empty = ops.softmax_excluded(filt, args[0][:0], args[1][:0], args[2][:0], n)
     assert empty[0].tolist() == [0] and empty[1].numel() == 0
+    # the tiny structure: an empty row, an entry under another relation only, any relation
+    th, tr, tt = (torch.tensor(x, device=gpu_device) for x in F.TINY_TRIPLES)
+    tiny = L.KnownTriples(th, tr, tt, 5, 2).for_side(side)
+    rows, rels, truth = (torch.tensor(x) for x in F.TINY_QUERIES)
+    xptr, xcol = ops.softmax_excluded(tiny, *(x.to(gpu_device) for x in (rows, rels, truth)), 5)
+    want = F.excluded_reference(tiny, rows, rels, truth, 5)
+    assert want == ([[], [1], [3], []] if side == "tail" else [[], [], [3], [0]])
+    wp, wc = F.to_lists(want)
+    assert torch.equal(xptr.cpu(), wp) and torch.equal(xcol.cpu(), wc), (side, "tiny")
 
 
 # ----------------------------------------------------------------------------- 5. model level

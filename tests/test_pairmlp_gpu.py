@@ -508,6 +508,11 @@ def test_filter_semantics(L, R, gpu_device):
     hres = L.predict_topk(model, best[:3], (r + 1)[:3] % n_rel, side="head", k=8, scoring="mlp", known=known)
     for i in range(3):
         assert int(q[i]) not in hres.ids[i].tolist()
+    # a query that is the head of no known triple (an empty filter row) keeps its free list
+    lone = torch.tensor([41], device=gpu_device)
+    assert not bool((kh == 41).any())
+    assert torch.equal(L.predict_topk(model, lone, r[:1], k=8, scoring="mlp", known=known).ids,
+                       L.predict_topk(model, lone, None, k=8, scoring="mlp").ids)
     # fewer candidates than k
     few = L.predict_topk(model, q, None, k=8, scoring="mlp", candidates=torch.tensor([7, 3, 250], device=gpu_device))
     assert bool((few.ids[:, 3:] == -1).all()) and sorted(few.ids[0, :3].tolist()) == [3, 7, 250]

@@ -395,6 +395,10 @@ def test_duplicated_rows_tie(L, gpu_device):
     assert int(L.rank_pairs_mlp(model, h[:1], t[:1], known=known).equal[0]) == int(full.equal[0]) - 1
     assert int(L.rank_pairs_mlp(model, h[:1], t[:1], zero, known=known).equal[0]) == int(full.equal[0]) - 1
     assert int(L.rank_pairs_mlp(model, h[:1], t[:1], one, known=known).equal[0]) == int(full.equal[0])
+    # a query that is the head of no known triple walks an empty filter row: the unfiltered counts
+    q = (h[:1] + 1) % n
+    lone, free = L.rank_pairs_mlp(model, q, t[:1], zero, known=known), L.rank_pairs_mlp(model, q, t[:1])
+    assert torch.equal(lone.better, free.better) and torch.equal(lone.equal, free.equal)
 
 
 def test_errors_on_the_device(L, R, gpu_device):

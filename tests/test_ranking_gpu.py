@@ -246,6 +246,16 @@ def test_random_table_parity(R, gpu_device, scoring, n, k, c):
     assert torch.equal(one.better, res.better[1]) and torch.equal(one.equal, res.equal[1])
 
 
+def test_tiny_filter_reaches_every_branch_of_the_row_walk(R, gpu_device):
+    """5 entities, 6 known triples, the pair (0, 1) under both relations, entity 4 in none.  On either side the queries
+    meet an empty filter row, a row with one entry under the wanted relation and one under the other only, and a row
+    whose entry under the wanted relation is the truth itself."""
+    model = random_model(torch.Generator().manual_seed(5), "transe", 5, 8, 8, 2, gpu_device)
+    known = tuple(torch.tensor(x, device=gpu_device) for x in ([0, 0, 0, 2, 2, 3], [0, 1, 0, 1, 0, 1], [1, 1, 3, 3, 0, 2]))
+    h, r, t = (torch.tensor(x, device=gpu_device) for x in ([4, 0, 2, 3, 0], [0, 1, 0, 0, 0], [0, 4, 0, 4, 3]))
+    run_and_check(R, model, "transe", h, r, t, known, what="tiny")
+
+
 # ----------------------------------------------------------------------------- 2. trained-like geometry
 @pytest.mark.parametrize("scoring", ["transe", "transr"])
 def test_trained_like_geometry(R, gpu_device, scoring):

@@ -165,13 +165,17 @@ def test_a_pair_alone_has_the_bits_it_has_in_a_batch_and_filters_that_drop_nothi
                              ("reversed", (kh.flip(0), kr.flip(0), kt.flip(0)))):
         other = ops.csr_build_device(2 * p, a.to(dev), c_.to(dev), b.to(dev))
         _same(full, run(f=(other, frow, fcol)), f"{name} filter")
-    # no filter, an empty one, one without an edge of these pairs, one that knows only the truths: the same bits
+    # no filter, an empty one, one without an edge of these pairs, one whose rows h_i hold other tails than t_i (h_i <
+    # t_i: the search ends past the row; every second row also t_i + 1: it ends on another entry), one that knows only
+    # the truths: the same bits
     plain = run(f=(None, None, None))
     z0 = torch.zeros(0, dtype=torch.int64, device=dev)
     empty = ops.csr_build_device(2 * p, z0, z0, z0)
     elsewhere = ops.csr_build_device(2 * p, (h + 1).to(dev) % (2 * p), h.to(dev), torch.zeros(p, dtype=torch.int64, device=dev))
+    ah, at = RC.tails_around(h, t, 2 * p)
+    around = ops.csr_build_device(2 * p, ah.to(dev), at.to(dev), torch.zeros(ah.numel(), dtype=torch.int64, device=dev))
     truths = ops.csr_build_device(2 * p, h.to(dev), t.to(dev), td)
-    for name, f in (("empty", empty), ("edge-less", elsewhere), ("truths only", truths)):
+    for name, f in (("empty", empty), ("edge-less", elsewhere), ("other tails", around), ("truths only", truths)):
         _same(plain, run(f=(f, frow, fcol)), f"{name} filter")
     assert not torch.equal(plain[2], full[2])                 # (the real filter does change the loss)
 

@@ -456,6 +456,11 @@ def test_any_relation(L, R, gpu_device):
     assert res_r.q_ids.numel() > res.q_ids.numel()
     out = L.evaluate_retrieval(model, hd, None, td, known=kt_, scoring="dot", ks=KS)
     check_aggregates(out, expected(h, None, t, "tail", n, dense, np.arange(n), known), "any relation")
+    # a filter that knows one triple elsewhere: every query of another head walks an empty row
+    lone = (torch.tensor([n - 1]), torch.tensor([0]), torch.tensor([n - 1]))
+    assert int((h != n - 1).sum()) > 0
+    res_l = L.rank_answers(model, hd, None, td, known=R.KnownTriples(*to(lone), n, n_rel), scoring="dot", ks=KS)
+    check(res_l, expected(h, None, t, "tail", n, dense, np.arange(n), lone), "a filter elsewhere")
 
 
 # ----------------------------------------------------------------------------- 9. NaN
