@@ -22,6 +22,7 @@ import __graft_entry__ as ge  # noqa: E402
 ge.build()
 from literalkg_amd import LiteralKG                      # noqa: E402  (the one-line change vs `from model import LiteralKG`)
 from literalkg_amd import KnownTriples, distinct_queries   # noqa: E402  (--filtered, --objective kvs_all)
+from literalkg_amd import product_route                  # noqa: E402  (--ordered-products)
 from literalkg_amd import group_sampled_batch            # noqa: E402  (--objective self_adversarial)
 from literalkg_amd import NegativeSampler, TripleEpoch, subsampling_weights   # noqa: E402  (--sampler triples)
 from literalkg_amd.synth import make_batch, make_kg      # noqa: E402
@@ -79,6 +80,9 @@ def main():
                     help="with --sampler triples: reject a negative that forms a training triple")
     ap.add_argument("--subsampling", action="store_true",
                     help="with --sampler triples: weight every triple by 1 / sqrt(4 + its known tails + its known heads)")
+    ap.add_argument("--ordered-products", action="store_true",
+                    help="with --objective one_vs_all, kvs_all or relation: the backward's long reductions run on the ordered "
+                         "split-K GEMM (literalkg_amd.product_route('ordered')); the other objectives have none")
     a = ap.parse_args()
     if a.filtered and a.objective not in ("one_vs_all", "relation"):
         ap.error("--filtered goes with --objective one_vs_all or relation")
@@ -120,23 +124,24 @@ def main():
                 bh, br, bp, bn = (torch.from_numpy(x).to(device)
                                   for x in make_batch(a.entities, a.batch_groups, a.neg_rate, seed=epoch * 10_000 + it))
             optimizer.zero_grad()
-            if sampler is not None:
-                loss = model.calc_sampled_negative_loss(bh, br, bp, batch, weights=weights, margin=a.margin,
-                                                        temperature=a.temperature)
-            elif a.objective == "self_adversarial":
-                loss = model.calc_self_adversarial_loss(*group_sampled_batch(bh, br, bp, bn, k), margin=a.margin,
-                                                        temperature=a.temperature)
-            elif a.objective == "kvs_all":
-                ent, rel = distinct_queries(bh[::k], br[::k])
-                loss = model.calc_kvs_all_loss(ent, rel, known, margin=a.margin, label_smoothing=a.label_smoothing)
-            elif a.objective == "relation":
-                loss = model.calc_relation_loss(bh[::k], br[::k], bp[::k], known=known)    # (known is None without --filtered)
-            elif a.filtered:
-                loss = model.calc_one_vs_all_loss(bh[::k], br[::k], bp[::k], known=known)
-            elif a.objective == "one_vs_all":
-                loss = model(bh[::k], br[::k], bp[::k], device=device, mode="one_vs_all")   # one triple per group
-            else:
-                loss = model(bh, br, bp, bn, device=device, mode="pre_training")
+            with product_route("ordered" if a.ordered_products else "engine"):     # read by the loss in its forward
+                if sampler is not None:
+                    loss = model.calc_sampled_negative_loss(bh, br, bp, batch, weights=weights, margin=a.margin,
+                                                            temperature=a.temperature)
+                elif a.objective == "self_adversarial":
+                    loss = model.calc_self_adversarial_loss(*group_sampled_batch(bh, br, bp, bn, k), margin=a.margin,
+                                                            temperature=a.temperature)
+                elif a.objective == "kvs_all":
+                    ent, rel = distinct_queries(bh[::k], br[::k])
+                    loss = model.calc_kvs_all_loss(ent, rel, known, margin=a.margin, label_smoothing=a.label_smoothing)
+                elif a.objective == "relation":
+                    loss = model.calc_relation_loss(bh[::k], br[::k], bp[::k], known=known)    # (known is None without --filtered)
+                elif a.filtered:
+                    loss = model.calc_one_vs_all_loss(bh[::k], br[::k], bp[::k], known=known)
+                elif a.objective == "one_vs_all":
+                    loss = model(bh[::k], br[::k], bp[::k], device=device, mode="one_vs_all")   # one triple per group
+                else:
+                    loss = model(bh, br, bp, bn, device=device, mode="pre_training")
             if np.isnan(loss.cpu().detach().numpy()):
                 sys.exit("ERROR (Pre-training): loss is nan")
             loss.backward()

@@ -26,6 +26,8 @@ from .self_adversarial import group_sampled_batch, sampled_sigmoid_loss, self_ad
 from .negatives import (NegativeBatch, NegativeSampler, RelationCardinalities, TripleEpoch, answer_counts,   # noqa: F401
                         relation_cardinalities, sampled_negative_loss, subsampling_weights)
 from .relation_loss import relation_loss, relation_softmax_loss   # noqa: F401  (the name relation_loss is the FUNCTION here)
+from .gemm_ordered import (current_route, gemm_ordered, gemm_ordered_splits, matmul_ordered,   # noqa: F401  (gemm_ordered: the
+                           product_route)                                                      # FUNCTION here, as above)
 
 __all__ = ["LiteralKG", "Aggregator", "Gate", "GateMul", "KGStructure", "KnownTriples", "RankResult", "evaluate_ranking",
            "TopKResult", "predict_topk", "FoldedMLPHead", "fold_mlp_head", "mlp_scores", "rank_pairs_mlp",
@@ -35,4 +37,5 @@ __all__ = ["LiteralKG", "Aggregator", "Gate", "GateMul", "KGStructure", "KnownTr
            "AnswerRanks", "rank_answers", "evaluate_retrieval", "one_vs_all_loss", "kvs_all_loss",
            "sigmoid_all_loss", "distinct_queries", "self_adversarial_loss", "sampled_sigmoid_loss", "group_sampled_batch",
            "NegativeSampler", "NegativeBatch", "TripleEpoch", "RelationCardinalities", "relation_cardinalities",
-           "answer_counts", "subsampling_weights", "sampled_negative_loss", "relation_loss", "relation_softmax_loss"]
+           "answer_counts", "subsampling_weights", "sampled_negative_loss", "relation_loss", "relation_softmax_loss",
+           "gemm_ordered", "gemm_ordered_splits", "matmul_ordered", "product_route", "current_route"]

@@ -158,11 +158,20 @@ RELATION_TRAIN_PROTOTYPES = {
     "lkg_relation_loss_fwd_f32": [i64, i32, i32, vp, i64, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, f32, vp, i64, vp, vp, vp],
     "lkg_relation_loss_bwd_f32": [i64, i32, i32, vp, i64, i64, vp, i64, vp, f32, vp, vp, i64, vp, i64, vp, i64, vp],
 }
+# the sixth table: include/literalkg_hip_gemm_ordered.h (the ordered split-K GEMM), mirrored the same way
+ORDERED_GEMM_PROTOTYPES = {
+    "lkg_gemm_ordered_splits": [i32, i32, i64, i64, i64],
+    "lkg_gemm_ordered_partition": [i64, i32, vp],
+    "lkg_gemm_ordered_workspace": [i64, i64, i64, i32],
+    "lkg_gemm_ordered_f32": [i32, i32, i64, i64, i64, i32, f32, vp, i64, vp, i64, f32, vp, i64, vp, vp, i64, vp],
+}
 _RESTYPE = {"lkg_last_error": C.c_char_p, "lkg_csr_build_device_workspace": C.c_int64,
             "lkg_gemm_tall_workspace": C.c_int64, "lkg_gemm_workspace": C.c_int64,
             "lkg_linear_act_layernorm_workspace": C.c_int64, "lkg_narrow_layer_bwd_workspace": C.c_int64,
             "lkg_csr_transpose_device_workspace": C.c_int64, "lkg_binary_curve_workspace": C.c_int64,
-            "lkg_threshold_fit_workspace": C.c_int64, "lkg_accept_order_workspace": C.c_int64}
+            "lkg_threshold_fit_workspace": C.c_int64, "lkg_accept_order_workspace": C.c_int64,
+            "lkg_gemm_ordered_splits": C.c_int32, "lkg_gemm_ordered_partition": C.c_int64,
+            "lkg_gemm_ordered_workspace": C.c_int64}
 
 
 class LkgError(RuntimeError):
@@ -185,7 +194,8 @@ def load():
             "literalkg_amd has no CPU fallback.")
     lib = C.CDLL(_LIB_PATH)
     for name, argtypes in list(PROTOTYPES.items()) + list(EXTRA_PROTOTYPES.items()) + list(TRAIN_PROTOTYPES.items()) + \
-            list(SAMPLE_PROTOTYPES.items()) + list(RELATION_TRAIN_PROTOTYPES.items()):
+            list(SAMPLE_PROTOTYPES.items()) + list(RELATION_TRAIN_PROTOTYPES.items()) + \
+            list(ORDERED_GEMM_PROTOTYPES.items()):
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
         fn.argtypes = argtypes
         fn.restype = _RESTYPE.get(name, C.c_int)

@@ -33,6 +33,7 @@ from . import _objectives as O
 from . import _queries as Q
 from . import ops
 from ._objectives import check_margin      # noqa: F401  (its home before _objectives.py)
+from .gemm_ordered import check_route, current_route, keyword_route
 
 MLP_MESSAGE = ("scoring='mlp' has no KvsAll loss: the pair head is trained by train_MLP on labelled pairs -- use 'transr', "
                "'transe' or 'dot'")
@@ -118,6 +119,7 @@ class _SigmoidAllLoss(Function):
         loss = sigmoid_all_forward(q_, p_, pn, bias_, positives, scale, eps, splits)
         ctx.save_for_backward(q_, p_, pn, bias_, yptr, ycol)
         ctx.meta = (scale, eps, chunk_bytes, bias.shape if bias is not None else None)
+        ctx.route = current_route()              # the backward follows the forward's choice wherever it is called
         return loss
 
     @staticmethod
@@ -143,7 +145,8 @@ class _SigmoidAllLoss(Function):
             N.call("lkg_sigmoid_all_finish_f32", b, (c1 - c0 + 255) // 256, N.ptr(tiles), N.ptr(part), ops._stream())
             rows.add_(part)
 
-        dq, dp = ops.all_entity_backward(q, p, pn, width, want_q, want_p, fill, add_row_sums if want_b else None)
+        dq, dp = ops.all_entity_backward(q, p, pn, width, want_q, want_p, fill, add_row_sums if want_b else None,
+                                         route=ctx.route)
         sb = scale if pn is not None else 0.5 * scale
         dbias = (rows / sb).float().reshape(bias_shape) if want_b else None
         return (dq, dp, dbias) + (None,) * 7
@@ -151,7 +154,7 @@ class _SigmoidAllLoss(Function):
 
 def sigmoid_all_loss(q: torch.Tensor, p: torch.Tensor, bias: Optional[torch.Tensor], positives=None, distance: bool = True,
                      scale: float = 1.0, label_smoothing: float = 0.0, splits: Optional[int] = None,
-                     chunk_bytes: int = ops.SOFTMAX_CHUNK_BYTES) -> torch.Tensor:
+                     chunk_bytes: int = ops.SOFTMAX_CHUNK_BYTES, products: str = "engine") -> torch.Tensor:
     """float32[B]: binary cross-entropy with logits of ALL N rows of p for query row q[i], summed over the candidates, the
     target 1 on the positions positives = (yptr int32[B + 1], ycol int32[M]) list for the row (sorted, unique; None: no
     positive anywhere) and 0 elsewhere, smoothed to (1 - label_smoothing) y + label_smoothing / N.  distance True: logits
@@ -159,12 +162,14 @@ def sigmoid_all_loss(q: torch.Tensor, p: torch.Tensor, bias: Optional[torch.Tens
     ||q_i - p_c||^2); False: z = scale q.p_c + bias_i.  bias float32[B] or None (0).  Differentiable in q, p and bias; the
     gradient of p is a dense N x k table.  splits: candidate splits of the forward pass (None: automatic) -- the last bits
     of the loss may depend on it, for a given value they do not change from run to run.  chunk_bytes bounds the backward's
-    B x Nc weights."""
-    scale, splits, chunk_bytes = ops.check_softmax_args(scale, splits, chunk_bytes)
-    eps = check_label_smoothing(label_smoothing)
-    ops._need_gpu(q, p, bias)
-    yptr, ycol = ops.list_pair("sigmoid_all_loss", "positives", positives, q.shape[0])
-    return _SigmoidAllLoss.apply(q, p, bias, yptr, ycol, bool(distance), scale, eps, splits, chunk_bytes)
+    B x Nc weights.  products "ordered": the backward's dQ product runs on gemm_ordered (gemm_ordered.keyword_route;
+    ops.all_entity_backward says what changes); the loss, dP and dbias keep their bits."""
+    with keyword_route(products):
+        scale, splits, chunk_bytes = ops.check_softmax_args(scale, splits, chunk_bytes)
+        eps = check_label_smoothing(label_smoothing)
+        ops._need_gpu(q, p, bias)
+        yptr, ycol = ops.list_pair("sigmoid_all_loss", "positives", positives, q.shape[0])
+        return _SigmoidAllLoss.apply(q, p, bias, yptr, ycol, bool(distance), scale, eps, splits, chunk_bytes)
 
 
 def distinct_queries(ent: torch.Tensor, r: torch.Tensor):
@@ -177,14 +182,17 @@ def distinct_queries(ent: torch.Tensor, r: torch.Tensor):
 
 def kvs_all_loss(model, ent: torch.Tensor, r: torch.Tensor, known, side: str = "tail", margin: float = 0.0,
                  scale: float = 1.0, label_smoothing: float = 0.0, reduction: str = "mean", scoring: Optional[str] = None,
-                 splits: Optional[int] = None, candidates: Optional[torch.Tensor] = None) -> torch.Tensor:
+                 splits: Optional[int] = None, candidates: Optional[torch.Tensor] = None,
+                 products: str = "engine") -> torch.Tensor:
     """The KvsAll loss of the queries (ent, r) under the model (see the module docstring): one row per GIVEN query
     (duplicates get equal values; distinct_queries gives the unique pairs of a batch), side 'tail' ((ent, r, ?), the
     positives known's tails) or 'head' ((?, r, ent), its heads), margin any finite number, scale > 0, label_smoothing in
     [0, 1), reduction 'mean' / 'sum' / 'none' over the rows (a row is the SUM over its candidates), scoring 'transr' /
     'transe' / 'dot' (default: model.scoring), splits as in one_vs_all_loss.  known: the KnownTriples the positives are
     read from.  candidates: the unique entity ids scored (n = their number; a positive that is not among them is simply
-    absent).  Differentiable in every parameter the table, the relation embeddings and (transr) gat_trans_M depend on."""
+    absent).  products as in sigmoid_all_loss.  Differentiable in every parameter the table, the relation embeddings and
+    (transr) gat_trans_M depend on."""
+    check_route(products)
     O.check_single_device(model, SHARDED_MESSAGE)
     side = Q.check_one_side(side, "a KvsAll row is one side's query")
     scoring = Q.resolve_scoring(model, scoring, MLP_MESSAGE)
@@ -217,6 +225,7 @@ def kvs_all_loss(model, ent: torch.Tensor, r: torch.Tensor, known, side: str = "
             bias = torch.full((ent.numel(),), scale * margin, dtype=torch.float32, device=ent.device)
         none = torch.full_like(ent, -1)                          # no truth to exempt: every known answer is listed
         positives = ops.softmax_excluded(known.for_side(side), ent, O.known_relations(scoring, r), none, p.shape[0], pos)
-        return sigmoid_all_loss(q, p, bias, positives, distance=distance, scale=scale, label_smoothing=eps, splits=splits)
+        return sigmoid_all_loss(q, p, bias, positives, distance=distance, scale=scale, label_smoothing=eps, splits=splits,
+                                products=products)
 
     return O.all_entity_loss(model, scoring, r, (ent,), cand, reduction, score_group)

@@ -562,28 +562,30 @@ class LiteralKG(nn.Module):
                                self.kg_l2loss_lambda, keep, sparse)
 
     def calc_one_vs_all_loss(self, h, r, t, side: str = "tail", scale: float = 1.0, reduction: str = "mean",
-                             scoring: Optional[str] = None, splits: Optional[int] = None, known=None, candidates=None):
+                             scoring: Optional[str] = None, splits: Optional[int] = None, known=None, candidates=None,
+                             products: str = "engine"):
         """1-vs-all training loss of the triples (h, r, t) (literalkg_amd/one_vs_all.py): cross-entropy of the true tail
         (side 'tail'), head ('head') or the mean of both ('both') against the softmax over EVERY entity under scoring
         'transr' / 'transe' / 'dot' (default: self.scoring).  Always on the full table of the step (prune_to_batch does
         not apply); no L2 term (weight decay is the optimizer's).  known (a KnownTriples): the other known answers of a
         query leave its softmax (the filtered loss); candidates (unique entity ids, one side only): the softmax runs over
-        those entities alone.  Also ``model(h, r, t, device=, mode='one_vs_all')``, the plain call."""
+        those entities alone.  products "ordered": the backward's long reduction runs on the ordered split-K GEMM
+        (literalkg_amd/gemm_ordered.py).  Also ``model(h, r, t, device=, mode='one_vs_all')``, the plain call."""
         from .one_vs_all import one_vs_all_loss
         return one_vs_all_loss(self, h, r, t, side=side, scale=scale, reduction=reduction, scoring=scoring, splits=splits,
-                               known=known, candidates=candidates)
+                               known=known, candidates=candidates, products=products)
 
     def calc_kvs_all_loss(self, ent, r, known, side: str = "tail", margin: float = 0.0, scale: float = 1.0,
                           label_smoothing: float = 0.0, reduction: str = "mean", scoring: Optional[str] = None,
-                          splits: Optional[int] = None, candidates=None):
+                          splits: Optional[int] = None, candidates=None, products: str = "engine"):
         """KvsAll training loss of the queries (ent, r) (literalkg_amd/kvs_all.py): one row per query scored against EVERY
         entity, binary cross-entropy with logits against the multi-hot vector of the query's answers in known (a
         KnownTriples), summed over the candidates; side 'tail' ((ent, r, ?)) or 'head' ((?, r, ent)), logits
         scale (margin - ||q - p||^2) ('dot': scale (margin + q.p)), optional label smoothing.  Always on the full table of
-        the step (prune_to_batch does not apply).  There is no mode= string for it."""
+        the step (prune_to_batch does not apply).  products as in calc_one_vs_all_loss.  There is no mode= string for it."""
         from .kvs_all import kvs_all_loss
         return kvs_all_loss(self, ent, r, known, side=side, margin=margin, scale=scale, label_smoothing=label_smoothing,
-                            reduction=reduction, scoring=scoring, splits=splits, candidates=candidates)
+                            reduction=reduction, scoring=scoring, splits=splits, candidates=candidates, products=products)
 
     def calc_self_adversarial_loss(self, h, r, t, neg, side: str = "tail", margin: float = 0.0, scale: float = 1.0,
                                    temperature: float = 1.0, reduction: str = "mean", scoring: Optional[str] = None):
@@ -607,15 +609,15 @@ class LiteralKG(nn.Module):
                                      temperature=temperature, reduction=reduction, scoring=scoring)
 
     def calc_relation_loss(self, h, r, t, known=None, scoring: Optional[str] = None, scale: float = 1.0,
-                           reduction: str = "mean", chunk_bytes: int = 256 << 20):
+                           reduction: str = "mean", chunk_bytes: int = 256 << 20, products: str = "engine"):
         """Relation-slot loss of the triples (h, r, t) (literalkg_amd/relation_loss.py): the cross-entropy of r against the
         softmax over every relation of (h, ?, t), logits -scale ||(T[h] - T[t]) W_j + e_j||^2 ('transe': no W_j), with
         ``known`` (a KnownTriples) the pair's other known relations left out -- the objective of
         evaluate_relation_prediction's filtered metric.  Reads two table rows per pair, so prune_to_batch applies; no L2
-        term.  There is no mode= string for it."""
+        term.  products as in calc_one_vs_all_loss.  There is no mode= string for it."""
         from .relation_loss import relation_loss
         return relation_loss(self, h, r, t, known=known, scoring=scoring, scale=scale, reduction=reduction,
-                             chunk_bytes=chunk_bytes)
+                             chunk_bytes=chunk_bytes, products=products)
 
     def _rows_only_projection_applies(self) -> bool:
         """A loss that reads a few rows of linear_gat's output and has to run the encoder anyway (a training step, or any call

@@ -38,6 +38,7 @@ from . import _objectives as O
 from . import _queries as Q
 from . import ops
 from ._objectives import REDUCTIONS, check_reduction      # noqa: F401  (their home before _objectives.py)
+from .gemm_ordered import check_route
 
 MLP_MESSAGE = ("scoring='mlp' has no 1-vs-all loss: the pair head is trained by train_MLP on labelled pairs -- use "
                "'transr', 'transe' or 'dot'")
@@ -45,14 +46,16 @@ MLP_MESSAGE = ("scoring='mlp' has no 1-vs-all loss: the pair head is trained by 
 
 def one_vs_all_loss(model, h: torch.Tensor, r: torch.Tensor, t: torch.Tensor, side: str = "tail", scale: float = 1.0,
                     reduction: str = "mean", scoring: Optional[str] = None, splits: Optional[int] = None,
-                    known=None, candidates: Optional[torch.Tensor] = None) -> torch.Tensor:
+                    known=None, candidates: Optional[torch.Tensor] = None, products: str = "engine") -> torch.Tensor:
     """The 1-vs-all loss of the triples (h, r, t) under the model (see the module docstring): side 'tail' / 'head' / 'both'
     (the mean of the two sides), scale > 0 a temperature on the logits, reduction 'mean' / 'sum' / 'none' (float32[B]),
     scoring 'transr' / 'transe' / 'dot' (default: model.scoring), splits the candidate splits of the forward kernel (None:
     automatic; the last bits of the loss may depend on it, for a given value they repeat from run to run).  known: a
     KnownTriples whose other answers of each query leave its softmax; candidates: the unique entity ids the softmax runs
-    over (one side only; every truth among them).  Differentiable in every parameter the table, the relation embeddings
-    and (transr) gat_trans_M depend on."""
+    over (one side only; every truth among them).  products as in ops.softmax_all_loss ("ordered": the backward's dQ
+    product on gemm_ordered).  Differentiable in every parameter the table, the relation embeddings and (transr)
+    gat_trans_M depend on."""
+    check_route(products)
     side = Q.check_side(side)
     scoring = Q.resolve_scoring(model, scoring, MLP_MESSAGE)
     reduction = check_reduction(reduction)
@@ -94,7 +97,7 @@ def one_vs_all_loss(model, h: torch.Tensor, r: torch.Tensor, t: torch.Tensor, si
                 exclude = ops.softmax_excluded(known.for_side(s_), ent, O.known_relations(scoring, r), truth, p.shape[0],
                                                pos)
             loss = ops.softmax_all_loss(q, p, truth, distance=scoring != "dot", scale=scale, splits=splits,
-                                        exclude=exclude)
+                                        exclude=exclude, products=products)
             total = loss if total is None else total + loss
         return total if side != "both" else 0.5 * total
 

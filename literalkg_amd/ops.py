@@ -3110,14 +3110,18 @@ def softmax_all_weights(q: torch.Tensor, p: torch.Tensor, pn: Optional[torch.Ten
 
 
 def all_entity_backward(q: torch.Tensor, p: torch.Tensor, pn: Optional[torch.Tensor], width: int, want_q: bool,
-                        want_p: bool, fill_v, after_v=None):
+                        want_p: bool, fill_v, after_v=None, route: str = "engine"):
     """(dq, dp) of a loss over ALL rows of p whose logits are those of softmax_all_forward (None for a gradient nobody
     wants, whose product is not launched): per chunk of ``width`` candidates fill_v(c0, c1, out) stores the weights
     V[:, c0:c1] = dL/dz (times scale beta) into ``out`` and returns it, after_v(c0, c1) (optional) does what else the loss
     needs of them, then dQ += 2 V P_chunk in slices of SOFTMAX_DQ_SLICE candidates and dP_chunk = 2 V^T Q -
     2 diag(colsum V) P_chunk (pn None, the dot product: 2 V^T Q) on ops.gemm.  Both products run with beta = 1 onto an
     initialised output: lkg_gemm_f32 splits a beta = 0 product with a long reduction over float atomics, whose sum changes
-    from run to run."""
+    from run to run.  route "ordered" (gemm_ordered.product_route): dQ of a chunk is ONE gemm_ordered product with
+    ceil(chunk / SOFTMAX_DQ_SLICE) splits instead of the slice loop -- no chain longer than a slice's, the partials added
+    in a fixed order; dP, a large output over a short reduction, stays on ops.gemm."""
+    from .gemm_ordered import accumulate_ordered, check_route
+    check_route(route)
     (b, k), n, dev = q.shape, p.shape[0], q.device
     if b == 0:
         return (torch.zeros((0, k), dtype=torch.float32, device=dev) if want_q else None,
@@ -3136,7 +3140,9 @@ def all_entity_backward(q: torch.Tensor, p: torch.Tensor, pn: Optional[torch.Ten
         if after_v is not None:
             after_v(c0, c1)
         pc = p[c0:c1]
-        if want_q:
+        if want_q and route == "ordered":
+            accumulate_ordered(v, pc, dq, SOFTMAX_DQ_SLICE, alpha=2.0)
+        elif want_q:
             for s0 in range(0, c1 - c0, SOFTMAX_DQ_SLICE):
                 s1 = min(c1 - c0, s0 + SOFTMAX_DQ_SLICE)
                 gemm(v[:, s0:s1], pc[s0:s1], alpha=2.0, beta=1.0, out=dq)
@@ -3164,6 +3170,8 @@ class _SoftmaxAllLoss(Function):
         exclude = (xptr, xcol) if xptr is not None else None
         lse, loss = softmax_all_forward(q_, p_, pn, truth, scale, splits, exclude)
         ctx.save_for_backward(q_, p_, pn, truth, lse, xptr, xcol)
+        from .gemm_ordered import current_route
+        ctx.route = current_route()              # the backward follows the forward's choice wherever it is called
         ctx.meta = (scale, chunk_bytes)
         return loss
 
@@ -3179,11 +3187,12 @@ class _SoftmaxAllLoss(Function):
             return softmax_all_weights(q, p, pn, truth, lse, g, scale, c0, c1, out=out, exclude=exclude)
 
         width = softmax_chunk_width(q.shape[0], p.shape[0], chunk_bytes)
-        return all_entity_backward(q, p, pn, width, want_q, want_p, fill) + (None,) * 7
+        return all_entity_backward(q, p, pn, width, want_q, want_p, fill, route=ctx.route) + (None,) * 7
 
 
 def softmax_all_loss(q: torch.Tensor, p: torch.Tensor, truth: torch.Tensor, distance: bool = True, scale: float = 1.0,
-                     splits: Optional[int] = None, chunk_bytes: int = SOFTMAX_CHUNK_BYTES, exclude=None) -> torch.Tensor:
+                     splits: Optional[int] = None, chunk_bytes: int = SOFTMAX_CHUNK_BYTES, exclude=None,
+                     products: str = "engine") -> torch.Tensor:
     """float32[B]: the cross-entropy of truth[i] against the softmax over ALL N rows of p for query row q[i] (1-vs-all).
     distance True: logits z = -scale ||q - p_c||^2 (||q||^2 cancels; ||p_c||^2 is computed here, so the gradient of p is
     complete); False: z = scale q.p_c.  Differentiable in q and p; the gradient of p is a dense N x k table (no RowSet
@@ -3191,8 +3200,12 @@ def softmax_all_loss(q: torch.Tensor, p: torch.Tensor, truth: torch.Tensor, dist
     loss may depend on it, for a given value they do not change from run to run.  chunk_bytes bounds the backward's B x Nc
     weights.  No L2 term: weight decay belongs to the optimizer (lkg_adam_step_f32).  exclude = (xptr, xcol) of
     softmax_excluded: row i's softmax runs over the candidates NOT in xcol[xptr[i] : xptr[i + 1]] (the filtered loss; the
-    truth must not be listed) and those rows of p get no gradient from row i.  None: the unfiltered launches, bit for bit."""
-    _need_gpu(q, p, truth)
-    scale, splits, chunk_bytes = check_softmax_args(scale, splits, chunk_bytes)
-    xptr, xcol = list_pair("softmax_all_loss", "exclude", exclude, truth.numel())
-    return _SoftmaxAllLoss.apply(q, p, truth, bool(distance), scale, splits, chunk_bytes, xptr, xcol)
+    truth must not be listed) and those rows of p get no gradient from row i.  None: the unfiltered launches, bit for bit.
+    products "ordered": the backward's dQ product runs on gemm_ordered (gemm_ordered.keyword_route: product_route entered
+    around the call; all_entity_backward says what changes).  The loss and dP keep their bits."""
+    from .gemm_ordered import keyword_route
+    with keyword_route(products):                # (a bad name: ValueError before any device work)
+        _need_gpu(q, p, truth)
+        scale, splits, chunk_bytes = check_softmax_args(scale, splits, chunk_bytes)
+        xptr, xcol = list_pair("softmax_all_loss", "exclude", exclude, truth.numel())
+        return _SoftmaxAllLoss.apply(q, p, truth, bool(distance), scale, splits, chunk_bytes, xptr, xcol)

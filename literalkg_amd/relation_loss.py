@@ -33,6 +33,7 @@ from . import _objectives as O
 from . import _queries as Q
 from . import ops, pruned
 from . import relations as R
+from .gemm_ordered import accumulate_ordered, check_route, current_route, gemm_ordered, keyword_route
 
 SHARDED_MESSAGE = ("the relation loss gathers its rows from a single-device table: the row-sharded model holds a block of it "
                    "per rank (train it on a single-device LiteralKG)")
@@ -131,6 +132,7 @@ class _RelationSoftmaxLoss(Function):
         (p, c), (n_rel, k), dev = d.shape, e.shape, d.device
         ctx.shapes = (d.shape, None if w is None else w.shape, e.shape)
         ctx.empty = p == 0
+        ctx.route = current_route()                      # the backward follows the forward's choice wherever it is called
         if ctx.empty:
             return torch.empty(0, dtype=torch.float32, device=dev)
         if w is None:
@@ -158,6 +160,7 @@ class _RelationSoftmaxLoss(Function):
         want_d, want_w, want_e = ctx.needs_input_grad[:3]
         nothing = (None,) * 6
         dev = g.device
+        ordered = ctx.route == "ordered"
         if ctx.empty or not (want_d or want_w or want_e):
             return tuple(torch.zeros(s, dtype=torch.float32, device=dev) if wnt and s is not None else None
                          for s, wnt in zip(ctx.shapes, (want_d, want_w, want_e))) + nothing
@@ -171,8 +174,12 @@ class _RelationSoftmaxLoss(Function):
             if want_e:
                 # de = c^T d + diag(colsum c) e; the column sums ride in the product as a column of ones next to d
                 # (lkg_colsum_f32 adds with float atomics)
-                t = torch.zeros((n_rel, k + 1), dtype=torch.float32, device=dev)
-                ops.gemm(cf, torch.cat((d, ones), dim=1), trans_a=True, beta=1.0, out=t)
+                d1 = torch.cat((d, ones), dim=1)
+                if ordered:                              # R x (k + 1) over P rows: split over the chip, added in order
+                    t = gemm_ordered(cf, d1, trans_a=True)
+                else:
+                    t = torch.zeros((n_rel, k + 1), dtype=torch.float32, device=dev)
+                    ops.gemm(cf, d1, trans_a=True, beta=1.0, out=t)
                 de = torch.addcmul(t[:, :k], t[:, k:], e)
             return (gd, None, de) + nothing
         wcat = _wcat(w)
@@ -188,7 +195,9 @@ class _RelationSoftmaxLoss(Function):
             hi = min(p, lo + rows)
             u = ops.gemm(d[lo:hi], wcat, out=ubuf[:hi - lo])
             gm = relation_softmax_backward(u, k, e, truth[lo:hi], scale, g[lo:hi], z[lo:hi])
-            if want_d:
+            if want_d and ordered:                       # one product per chunk, no split longer than a slice
+                accumulate_ordered(gm, wcat, dd[lo:hi], step, trans_b=True)
+            elif want_d:
                 for s0 in range(0, n_rel * k, step):
                     s1 = min(n_rel * k, s0 + step)
                     ops.gemm(gm[:, s0:s1], wcat[:, s0:s1], trans_b=True, beta=1.0, out=dd[lo:hi])
@@ -201,7 +210,8 @@ class _RelationSoftmaxLoss(Function):
 
 def relation_softmax_loss(d: torch.Tensor, w: Optional[torch.Tensor], e: torch.Tensor, truth: torch.Tensor,
                           scale: float = 1.0, filt=None, filter_row: Optional[torch.Tensor] = None,
-                          filter_col: Optional[torch.Tensor] = None, chunk_bytes: int = CHUNK_BYTES) -> torch.Tensor:
+                          filter_col: Optional[torch.Tensor] = None, chunk_bytes: int = CHUNK_BYTES,
+                          products: str = "engine") -> torch.Tensor:
     """float32[P]: loss_i = logsumexp_j z_ij - z_i,truth_i with z_ij = -scale ||d_i W_j + e_j||^2 (w None, shared mode:
     ||d_i + e_j||^2, d as wide as e) for d float32[P, C], w float32[R, C, D] or None, e float32[R, D], truth int64[P] in
     [0, R).  filt = (rowptr, col, eptr, rel) of ops.csr_build_device: row i's softmax leaves out every relation other than
@@ -210,21 +220,28 @@ def relation_softmax_loss(d: torch.Tensor, w: Optional[torch.Tensor], e: torch.T
     share ONE product, launched when either is needed), the others keep their bits.  Slab mode (w given) runs in chunks
     of pairs whose slab rows x R x D x 4 bytes fits chunk_bytes (ValueError when one pair's does not) and recomputes the
     slab in the backward pass; its bits may depend on chunk_bytes (the GEMM's engine may change with the row count), the
-    loss from a given slab does not.  Shared mode has no slab: chunk_bytes bounds nothing there and changes no bit."""
-    scale, _, chunk_bytes = ops.check_softmax_args(scale, None, chunk_bytes)
-    ops._need_gpu(d, w, e, truth, filter_row, filter_col)
-    return _RelationSoftmaxLoss.apply(d, w, e, truth, scale, filt, filter_row, filter_col, chunk_bytes)
+    loss from a given slab does not.  Shared mode has no slab: chunk_bytes bounds nothing there and changes no bit.
+    products "ordered" (gemm_ordered.keyword_route): slab mode's dd += G Wcat^T is one gemm_ordered product per chunk
+    (no split longer than a DD_SLICE slice), shared mode's c^T [d | 1] behind de runs on gemm_ordered; the loss and the
+    other gradients keep their bits."""
+    with keyword_route(products):                        # (a bad name: ValueError before any device work)
+        scale, _, chunk_bytes = ops.check_softmax_args(scale, None, chunk_bytes)
+        ops._need_gpu(d, w, e, truth, filter_row, filter_col)
+        return _RelationSoftmaxLoss.apply(d, w, e, truth, scale, filt, filter_row, filter_col, chunk_bytes)
 
 
 def relation_loss(model, h: torch.Tensor, r: torch.Tensor, t: torch.Tensor, known=None, scoring: Optional[str] = None,
-                  scale: float = 1.0, reduction: str = "mean", chunk_bytes: int = CHUNK_BYTES) -> torch.Tensor:
+                  scale: float = 1.0, reduction: str = "mean", chunk_bytes: int = CHUNK_BYTES,
+                  products: str = "engine") -> torch.Tensor:
     """The cross-entropy of the true relations r of the pairs (h, t) (int64[P] each) against the softmax over every
     relation under the model (see the module docstring): scoring 'transr' / 'transe' (default: model.scoring; 'dot' and
     'mlp' are refused as relation prediction refuses them), scale > 0, reduction 'mean' / 'sum' / 'none' over the pairs,
     known a KnownTriples (the other known relations of a pair leave its softmax; the truth never does).  The logits are
     summed directly and are not the bits of score_relations.  Differentiable in every parameter the table, the relation
     embeddings and (transr) gat_trans_M depend on; the table is taken as self_adversarial_loss takes it (training or grad
-    enabled: the graph-carrying table, prune_to_batch honoured; otherwise the kept one)."""
+    enabled: the graph-carrying table, prune_to_batch honoured; otherwise the kept one).  products as in
+    relation_softmax_loss."""
+    check_route(products)
     O.check_single_device(model, SHARDED_MESSAGE)
     scoring = R._check_scoring(model, scoring)
     reduction = O.check_reduction(reduction)
@@ -249,5 +266,5 @@ def relation_loss(model, h: torch.Tensor, r: torch.Tensor, t: torch.Tensor, know
     w = model.gat_trans_M if scoring == "transr" else None
     filt = known.by_head if known is not None else None              # (h, r', t): heads with their tails, raw entity ids
     loss = relation_softmax_loss(d, w, model.relation_embed.weight, r, scale, filt, h if filt is not None else None,
-                                 t if filt is not None else None, chunk_bytes)
+                                 t if filt is not None else None, chunk_bytes, products=products)
     return O.reduce(loss, reduction)
