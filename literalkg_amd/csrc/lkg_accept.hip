@@ -147,16 +147,12 @@ int launch_accept(const char *name, int64_t n_q, int64_t n_cand, int32_t k, cons
     LKG_REQUIRE(tiles_q * s_ < INT32_MAX, "%s: too many workgroups (split the queries)", name);
     const dim3 grid((unsigned)(tiles_q * s_)), block(TK_THREADS);
     const hipStream_t st = (hipStream_t)stream;
-    if (vec_ok(q, ldq, p, ldp))
-        hipLaunchKernelGGL((accept_kernel<true, EMIT>), grid, block, 0, st, (long)n_q, (long)n_cand, k, q, (long)ldq, p,
-                           (long)ldp, pn, qn, thr, (int)(higher != 0), (const long *)cand_ids, (const long *)filter_row,
-                           (const long *)filter_rel, rowptr, col, eptr, rel, s_, tiles_q, tiles_c, counts,
-                           (const long *)base, cursor, (long *)out_ids, out_s, out_v, flag);
-    else
-        hipLaunchKernelGGL((accept_kernel<false, EMIT>), grid, block, 0, st, (long)n_q, (long)n_cand, k, q, (long)ldq, p,
-                           (long)ldp, pn, qn, thr, (int)(higher != 0), (const long *)cand_ids, (const long *)filter_row,
-                           (const long *)filter_rel, rowptr, col, eptr, rel, s_, tiles_q, tiles_c, counts,
-                           (const long *)base, cursor, (long *)out_ids, out_s, out_v, flag);
+    vec_dispatch(vec_ok(q, ldq, p, ldp), [&](auto vec) {
+        hipLaunchKernelGGL((accept_kernel<decltype(vec)::value, EMIT>), grid, block, 0, st, (long)n_q, (long)n_cand, k, q,
+                           (long)ldq, p, (long)ldp, pn, qn, thr, (int)(higher != 0), (const long *)cand_ids,
+                           (const long *)filter_row, (const long *)filter_rel, rowptr, col, eptr, rel, s_, tiles_q, tiles_c,
+                           counts, (const long *)base, cursor, (long *)out_ids, out_s, out_v, flag);
+    });
     LKG_CHECK_LAUNCH(name);
     return LKG_OK;
 }

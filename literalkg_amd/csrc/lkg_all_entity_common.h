@@ -7,6 +7,11 @@
 
 #include <climits>
 
+// the tile of every kernel of the two files (and what lkg_softmax_all_splits, which both use, divides by)
+constexpr int AE_THREADS = 256;
+constexpr int AE_ROWS = 64;           // queries per workgroup
+constexpr int AE_COLS = 256;          // candidates per tile (64 per wave)
+
 // A row's walk through its list: entries [cur, end) of col are still ahead, next = col[cur] (INT_MAX when none is left:
 // positions are < n_c < INT32_MAX).  ptr is clamped into [0, m_total], so a bad list cannot be read past.
 struct ListCursor {

@@ -12,9 +12,9 @@
 // once).  With eps == 0 the product is not executed: the sum has the bits of the plain one.  Floating-point contraction is
 // off in this file: every rounding above is one the references restate.
 //
-// Forward: the tile, the split scheme and the workspace of softmax_partial_masked_kernel (lkg_softmax.hip): a 256-thread
-// workgroup owns 64 query rows and a contiguous range of 256-candidate tiles.  A lane keeps ONE running sum per row it
-// holds (16 of them, over its 4 columns of every tile) -- no maximum to carry, so nothing crosses lanes inside the loop.
+// Forward: the tile, the split scheme and the workspace of softmax_partial_kernel with MASKED (lkg_softmax.hip): a
+// 256-thread workgroup owns 64 query rows and a contiguous range of 256-candidate tiles.  A lane keeps ONE running sum per
+// row it holds (16 of them, over its 4 columns of every tile) -- no maximum to carry, so nothing crosses lanes inside the loop.
 // The 16 lanes of a row meet once and the 4 waves meet once in LDS, after the last tile; the workgroup's sum goes to
 // workspace [S][B], sigmoid_finish_kernel merges the S partials of a row in split order in float64.  No float atomics: for
 // a given S every bit is the same from run to run.
@@ -33,10 +33,6 @@
 
 namespace {
 
-constexpr int KV_THREADS = 256;
-constexpr int KV_ROWS = 64;           // queries per workgroup
-constexpr int KV_COLS = 256;          // candidates per tile (64 per wave)
-
 // softplus(x) without cancellation; NaN in, NaN out (fmaxf drops it, the logarithm keeps it)
 __device__ __forceinline__ float softplus_f(float x) { return fmaxf(x, 0.f) + log1pf(expf(-fabsf(x))); }
 
@@ -48,20 +44,20 @@ __device__ __forceinline__ float sigmoid_f(float x) {
 
 // (two workgroups per CU stated: without the hint the compiler took 260 registers, with it 225 and no spill)
 template <bool VEC>
-__global__ __launch_bounds__(KV_THREADS, 2) void sigmoid_partial_kernel(
+__global__ __launch_bounds__(AE_THREADS, 2) void sigmoid_partial_kernel(
     long n_q, long n_c, int k, const float *__restrict__ q, long ldq, const float *__restrict__ p, long ldp,
     const float *__restrict__ pn, const float *__restrict__ bias, float nsb, float ce1, float ce0, int smooth, int splits,
     long tiles_q, long tiles_c, float *__restrict__ ws, const int *__restrict__ yptr, const int *__restrict__ ycol,
     int m_total) {
-    __shared__ unsigned long long sm_y[4][KV_ROWS];
-    __shared__ float sm_b[KV_ROWS], sm_l[4][KV_ROWS];
+    __shared__ unsigned long long sm_y[4][AE_ROWS];
+    __shared__ float sm_b[AE_ROWS], sm_l[4][AE_ROWS];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r = lane & 15, s = lane >> 4;
     const long bid = blockIdx.x;
-    const long q0 = (bid % tiles_q) * KV_ROWS;
+    const long q0 = (bid % tiles_q) * AE_ROWS;
     const int split = (int)(bid / tiles_q);
     const long t_lo = split * tiles_c / splits, t_hi = (split + 1) * tiles_c / splits;
-    if (tid < KV_ROWS) sm_b[tid] = (bias && q0 + tid < n_q) ? bias[q0 + tid] : 0.f;
+    if (tid < AE_ROWS) sm_b[tid] = (bias && q0 + tid < n_q) ? bias[q0 + tid] : 0.f;
     __syncthreads();
     const float *qrow[4];
 #pragma unroll
@@ -71,10 +67,10 @@ __global__ __launch_bounds__(KV_THREADS, 2) void sigmoid_partial_kernel(
     for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int v = 0; v < 4; ++v) l[i][v] = 0.f;
-    ListCursor x = list_seek(yptr, ycol, m_total, q0 + lane, yptr ? n_q : 0, t_lo * KV_COLS);
+    ListCursor x = list_seek(yptr, ycol, m_total, q0 + lane, yptr ? n_q : 0, t_lo * AE_COLS);
 
     for (long t = t_lo; t < t_hi; ++t) {
-        const long c0 = t * KV_COLS + wave * 64;
+        const long c0 = t * AE_COLS + wave * 64;
         const float *prow[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) prow[i] = p + min(c0 + 16 * i + r, n_c - 1) * ldp;
@@ -118,7 +114,7 @@ __global__ __launch_bounds__(KV_THREADS, 2) void sigmoid_partial_kernel(
             if (r == 0) sm_l[wave][16 * i + 4 * s + v] = sum;
         }
     __syncthreads();
-    if (tid < KV_ROWS && q0 + tid < n_q) {
+    if (tid < AE_ROWS && q0 + tid < n_q) {
         float lw = sm_l[0][tid];
 #pragma unroll
         for (int w = 1; w < 4; ++w) lw += sm_l[w][tid];
@@ -128,9 +124,9 @@ __global__ __launch_bounds__(KV_THREADS, 2) void sigmoid_partial_kernel(
 
 // one thread per query: the S partials of a row (the forward's splits, or the tiles of the weights' row sums) in order in
 // float64, rounded once
-__global__ __launch_bounds__(KV_THREADS) void sigmoid_finish_kernel(long n_q, int splits, const float *__restrict__ ws,
+__global__ __launch_bounds__(AE_THREADS) void sigmoid_finish_kernel(long n_q, int splits, const float *__restrict__ ws,
                                                                     float *__restrict__ loss) {
-    const long i = (long)blockIdx.x * KV_THREADS + threadIdx.x;
+    const long i = (long)blockIdx.x * AE_THREADS + threadIdx.x;
     if (i >= n_q) return;
     double sum = 0.0;
     for (int j = 0; j < splits; ++j) sum += (double)ws[(long)j * n_q + i];
@@ -145,23 +141,20 @@ __global__ __launch_bounds__(KV_THREADS) void sigmoid_finish_kernel(long n_q, in
 // A row sum through the dQ product's f32 MFMA chain (a column of ones next to P) was measured first: its terms all have
 // one sign away from the positives, and the chain's error then grew with the length, not with its root.
 template <bool VEC>
-__global__ __launch_bounds__(KV_THREADS) void sigmoid_weights_kernel(
+__global__ __launch_bounds__(AE_THREADS) void sigmoid_weights_kernel(
     long n_q, long n_c, int k, const float *__restrict__ q, long ldq, const float *__restrict__ p, long ldp,
     const float *__restrict__ pn, const float *__restrict__ bias, long c_base, const float *__restrict__ g, float nsb,
     float sb, float ce1, float ce0, float *__restrict__ vout, long ldv, long tiles_q, const int *__restrict__ yptr,
     const int *__restrict__ ycol, int m_total, float *__restrict__ rowsum) {
-    __shared__ unsigned long long sm_y[4][KV_ROWS];
-    __shared__ float sm_r[4][KV_ROWS];
+    __shared__ unsigned long long sm_y[4][AE_ROWS];
+    __shared__ float sm_r[4][AE_ROWS];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r = lane & 15, s = lane >> 4;
     const long bid = blockIdx.x;
-    const long q0 = (bid % tiles_q) * KV_ROWS, c0 = (bid / tiles_q) * KV_COLS + wave * 64;
+    const long q0 = (bid % tiles_q) * AE_ROWS, c0 = (bid / tiles_q) * AE_COLS + wave * 64;
     const float *qrow[4], *prow[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        qrow[i] = q + min(q0 + 16 * i + r, n_q - 1) * ldq;        // rows and columns past the end are clamped, never stored
-        prow[i] = p + min(c0 + 16 * i + r, n_c - 1) * ldp;
-    }
+    tile_rows(qrow, q, ldq, q0, n_q, r);
+    tile_rows(prow, p, ldp, c0, n_c, r);
     f32x4 acc[4][4];
     rank_tile_dots<VEC>(acc, qrow, prow, k, s);
     ListCursor x = list_seek(yptr, ycol, m_total, q0 + lane, yptr ? n_q : 0, c_base + c0);
@@ -200,7 +193,7 @@ __global__ __launch_bounds__(KV_THREADS) void sigmoid_weights_kernel(
         }
     if (rowsum) {
         __syncthreads();
-        if (tid < KV_ROWS && q0 + tid < n_q)
+        if (tid < AE_ROWS && q0 + tid < n_q)
             rowsum[(bid / tiles_q) * n_q + q0 + tid] = ((sm_r[0][tid] + sm_r[1][tid]) + sm_r[2][tid]) + sm_r[3][tid];
     }
 }
@@ -226,19 +219,16 @@ extern "C" int lkg_sigmoid_all_partial_f32(int64_t n_q, int64_t n_cand, int32_t 
     LKG_REQUIRE(splits >= 1 && splits == lkg_softmax_all_splits(n_q, n_cand, splits),
                 "lkg_sigmoid_all_partial_f32: splits must come from lkg_softmax_all_splits");
     LKG_REQUIRE(q && p && ws && (!yptr || ycol || n_pos == 0), "lkg_sigmoid_all_partial_f32: null pointer");
-    const long tiles_q = (n_q + KV_ROWS - 1) / KV_ROWS, tiles_c = (n_cand + KV_COLS - 1) / KV_COLS;
+    const long tiles_q = (n_q + AE_ROWS - 1) / AE_ROWS, tiles_c = (n_cand + AE_COLS - 1) / AE_COLS;
     LKG_REQUIRE(tiles_q * splits < INT32_MAX, "lkg_sigmoid_all_partial_f32: too many workgroups (split the queries)");
-    const dim3 grid((unsigned)(tiles_q * splits)), block(KV_THREADS);
+    const dim3 grid((unsigned)(tiles_q * splits)), block(AE_THREADS);
     const float nsb = neg_scale_beta(scale, pn);
     const int m_total = yptr ? (int)n_pos : 0;
-    if (vec_ok(q, ldq, p, ldp))
-        hipLaunchKernelGGL(sigmoid_partial_kernel<true>, grid, block, 0, (hipStream_t)stream, (long)n_q, (long)n_cand, k,
-                           q, (long)ldq, p, (long)ldp, pn, bias, nsb, ce_pos(eps, n_cand), ce_neg(eps, n_cand),
-                           (int)(eps > 0.0), splits, tiles_q, tiles_c, ws, yptr, ycol, m_total);
-    else
-        hipLaunchKernelGGL(sigmoid_partial_kernel<false>, grid, block, 0, (hipStream_t)stream, (long)n_q, (long)n_cand, k,
-                           q, (long)ldq, p, (long)ldp, pn, bias, nsb, ce_pos(eps, n_cand), ce_neg(eps, n_cand),
-                           (int)(eps > 0.0), splits, tiles_q, tiles_c, ws, yptr, ycol, m_total);
+    vec_dispatch(vec_ok(q, ldq, p, ldp), [&](auto vec) {
+        hipLaunchKernelGGL(sigmoid_partial_kernel<decltype(vec)::value>, grid, block, 0, (hipStream_t)stream, (long)n_q,
+                           (long)n_cand, k, q, (long)ldq, p, (long)ldp, pn, bias, nsb, ce_pos(eps, n_cand),
+                           ce_neg(eps, n_cand), (int)(eps > 0.0), splits, tiles_q, tiles_c, ws, yptr, ycol, m_total);
+    });
     LKG_CHECK_LAUNCH("lkg_sigmoid_all_partial_f32");
     return LKG_OK;
 }
@@ -247,7 +237,7 @@ extern "C" int lkg_sigmoid_all_finish_f32(int64_t n_q, int32_t splits, const flo
     LKG_REQUIRE(n_q >= 0 && splits >= 1, "lkg_sigmoid_all_finish_f32: bad sizes");
     if (n_q == 0) return LKG_OK;
     LKG_REQUIRE(ws && loss, "lkg_sigmoid_all_finish_f32: null pointer");
-    const dim3 grid((unsigned)((n_q + KV_THREADS - 1) / KV_THREADS)), block(KV_THREADS);
+    const dim3 grid((unsigned)((n_q + AE_THREADS - 1) / AE_THREADS)), block(AE_THREADS);
     hipLaunchKernelGGL(sigmoid_finish_kernel, grid, block, 0, (hipStream_t)stream, (long)n_q, splits, ws, loss);
     LKG_CHECK_LAUNCH("lkg_sigmoid_all_finish_f32");
     return LKG_OK;
@@ -266,19 +256,16 @@ extern "C" int lkg_sigmoid_all_weights_f32(int64_t n_q, int64_t n_cand, int32_t 
     LKG_REQUIRE(eps_ok(eps), "lkg_sigmoid_all_weights_f32: eps must lie in [0, 1)");
     if (n_q == 0 || n_cand == 0) return LKG_OK;
     LKG_REQUIRE(q && p && g && v && (!yptr || ycol || n_pos == 0), "lkg_sigmoid_all_weights_f32: null pointer");
-    const long tiles_q = (n_q + KV_ROWS - 1) / KV_ROWS, tiles_c = (n_cand + KV_COLS - 1) / KV_COLS;
+    const long tiles_q = (n_q + AE_ROWS - 1) / AE_ROWS, tiles_c = (n_cand + AE_COLS - 1) / AE_COLS;
     LKG_REQUIRE(tiles_q * tiles_c < INT32_MAX, "lkg_sigmoid_all_weights_f32: too many tiles (use smaller chunks)");
-    const dim3 grid((unsigned)(tiles_q * tiles_c)), block(KV_THREADS);
+    const dim3 grid((unsigned)(tiles_q * tiles_c)), block(AE_THREADS);
     const float nsb = neg_scale_beta(scale, pn);
     const int m_total = yptr ? (int)n_pos : 0;
-    if (vec_ok(q, ldq, p, ldp))
-        hipLaunchKernelGGL(sigmoid_weights_kernel<true>, grid, block, 0, (hipStream_t)stream, (long)n_q, (long)n_cand, k,
-                           q, (long)ldq, p, (long)ldp, pn, bias, (long)c_base, g, nsb, -nsb, ce_pos(eps, n_total),
-                           ce_neg(eps, n_total), v, (long)ldv, tiles_q, yptr, ycol, m_total, rowsum);
-    else
-        hipLaunchKernelGGL(sigmoid_weights_kernel<false>, grid, block, 0, (hipStream_t)stream, (long)n_q, (long)n_cand, k,
-                           q, (long)ldq, p, (long)ldp, pn, bias, (long)c_base, g, nsb, -nsb, ce_pos(eps, n_total),
-                           ce_neg(eps, n_total), v, (long)ldv, tiles_q, yptr, ycol, m_total, rowsum);
+    vec_dispatch(vec_ok(q, ldq, p, ldp), [&](auto vec) {
+        hipLaunchKernelGGL(sigmoid_weights_kernel<decltype(vec)::value>, grid, block, 0, (hipStream_t)stream, (long)n_q,
+                           (long)n_cand, k, q, (long)ldq, p, (long)ldp, pn, bias, (long)c_base, g, nsb, -nsb,
+                           ce_pos(eps, n_total), ce_neg(eps, n_total), v, (long)ldv, tiles_q, yptr, ycol, m_total, rowsum);
+    });
     LKG_CHECK_LAUNCH("lkg_sigmoid_all_weights_f32");
     return LKG_OK;
 }

@@ -41,11 +41,8 @@ __global__ __launch_bounds__(RK_THREADS) void rank_count_kernel(long n_q, long n
         cnt[1][tid] = 0;
     }
     const float *qrow[4], *prow[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        qrow[i] = q + min(q0 + 16 * i + r, n_q - 1) * ldq;        // rows past the end are clamped (never counted)
-        prow[i] = p + min(c0 + 16 * i + r, n_c - 1) * ldp;
-    }
+    tile_rows(qrow, q, ldq, q0, n_q, r);
+    tile_rows(prow, p, ldp, c0, n_c, r);
     f32x4 acc[4][4];
 #pragma unroll
     for (int i = 0; i < 4; ++i)
@@ -221,14 +218,11 @@ extern "C" int lkg_rank_prepare_f32(int64_t n_q, int64_t n_cand, int32_t k, cons
     LKG_REQUIRE(q && p && truth && thr && better && equal, "lkg_rank_prepare_f32: null pointer");
     LKG_REQUIRE(known_filter_complete(rowptr, filter_row, filter_rel, col, eptr, rel), "lkg_rank_prepare_f32: incomplete filter");
     const dim3 grid((unsigned)((n_q + 3) / 4)), block(RK_THREADS);
-    if (vec_ok(q, ldq, p, ldp))
-        hipLaunchKernelGGL(rank_prepare_kernel<true>, grid, block, 0, (hipStream_t)stream, (long)n_q, (long)n_cand, k, q,
-                           (long)ldq, p, (long)ldp, pn, (const long *)truth, (const long *)filter_row,
+    vec_dispatch(vec_ok(q, ldq, p, ldp), [&](auto vec) {
+        hipLaunchKernelGGL(rank_prepare_kernel<decltype(vec)::value>, grid, block, 0, (hipStream_t)stream, (long)n_q,
+                           (long)n_cand, k, q, (long)ldq, p, (long)ldp, pn, (const long *)truth, (const long *)filter_row,
                            (const long *)filter_rel, rowptr, col, eptr, rel, thr, better, equal);
-    else
-        hipLaunchKernelGGL(rank_prepare_kernel<false>, grid, block, 0, (hipStream_t)stream, (long)n_q, (long)n_cand, k,
-                           q, (long)ldq, p, (long)ldp, pn, (const long *)truth, (const long *)filter_row,
-                           (const long *)filter_rel, rowptr, col, eptr, rel, thr, better, equal);
+    });
     LKG_CHECK_LAUNCH("lkg_rank_prepare_f32");
     return LKG_OK;
 }
@@ -243,12 +237,10 @@ extern "C" int lkg_rank_count_f32(int64_t n_q, int64_t n_cand, int32_t k, const 
     const long tiles_q = (n_q + RK_ROWS - 1) / RK_ROWS, tiles_c = (n_cand + RK_COLS - 1) / RK_COLS;
     LKG_REQUIRE(tiles_q * tiles_c < INT32_MAX, "lkg_rank_count_f32: too many tiles (split the queries)");
     const dim3 grid((unsigned)(tiles_q * tiles_c)), block(RK_THREADS);
-    if (vec_ok(q, ldq, p, ldp))
-        hipLaunchKernelGGL(rank_count_kernel<true>, grid, block, 0, (hipStream_t)stream, (long)n_q, (long)n_cand, k, q,
-                           (long)ldq, p, (long)ldp, pn, thr, (const long *)truth, better, equal, tiles_q);
-    else
-        hipLaunchKernelGGL(rank_count_kernel<false>, grid, block, 0, (hipStream_t)stream, (long)n_q, (long)n_cand, k, q,
-                           (long)ldq, p, (long)ldp, pn, thr, (const long *)truth, better, equal, tiles_q);
+    vec_dispatch(vec_ok(q, ldq, p, ldp), [&](auto vec) {
+        hipLaunchKernelGGL(rank_count_kernel<decltype(vec)::value>, grid, block, 0, (hipStream_t)stream, (long)n_q,
+                           (long)n_cand, k, q, (long)ldq, p, (long)ldp, pn, thr, (const long *)truth, better, equal, tiles_q);
+    });
     LKG_CHECK_LAUNCH("lkg_rank_count_f32");
     return LKG_OK;
 }

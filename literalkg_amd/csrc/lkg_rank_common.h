@@ -8,11 +8,21 @@
 #pragma once
 #include "lkg_common.h"
 
+#include <type_traits>
+
 using f32x4 = __attribute__((ext_vector_type(4))) float;
 
 // host side: may the kernels be launched with VEC (16-byte loads of both operands' rows)?
 static inline bool vec_ok(const void *a, long lda, const void *b, long ldb) {
     return lkg_aligned16(a) && lkg_aligned16(b) && lda % 4 == 0 && ldb % 4 == 0;
+}
+
+// host side: the one way to launch a VEC-templated kernel.  `launch` holds the launch statement, written once with
+// kernel<decltype(vec)::value, ...>; it is called with std::true_type (16-byte loads) or std::false_type.
+template <class Launch>
+static inline void vec_dispatch(bool vec, Launch &&launch) {
+    if (vec) launch(std::true_type{});
+    else launch(std::false_type{});
 }
 
 template <bool VEC>
@@ -53,6 +63,16 @@ __device__ __forceinline__ float rank_pair_scores(const float *__restrict__ qrow
         mfma_chunk(acc, a, b);
     }
     return rank_score(acc[0], pn, cand);     // C[4 s + 0][r]: the same value on every s
+}
+
+// The four operand rows lane r feeds to rank_tile_dots: rows first + 16 i + r of x, clamped to the last of the n rows (a
+// tile may hang over the end: what a clamped row produces is never stored or counted).  For the kernels of one tile per
+// workgroup; the kernels that walk a range of tiles keep the statement inline: through this helper their register
+// allocation, though not their arithmetic, would change (profiles/all_entity_tile_merge.txt).
+__device__ __forceinline__ void tile_rows(const float *(&row)[4], const float *__restrict__ x, long ldx, long first, long n,
+                                          int r) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) row[i] = x + min(first + 16 * i + r, n - 1) * ldx;
 }
 
 // One wave's 64 x 64 block of dot products: acc[i][j][v] = q_(16 i + 4 s + v) . p_(16 j + r) for lane (r, s) = (l & 15,

@@ -220,14 +220,11 @@ extern "C" int lkg_relation_scores_f32(int64_t n, int32_t k, int32_t n_rel, cons
     LKG_REQUIRE(p && pn && q_idx && c_idx && e && out, "lkg_relation_scores_f32: null pointer");
     const long blocks = (n + RS_PAIRS - 1) / RS_PAIRS;
     const dim3 grid((unsigned)(blocks < RS_GRID ? blocks : RS_GRID)), block(RS_THREADS);
-    if (vec_ok(p, ldp, e, lde) && rel_stride % 4 == 0)
-        hipLaunchKernelGGL(relation_scores_kernel<true>, grid, block, 0, (hipStream_t)stream, (long)n, k, (int)n_rel, p,
-                           (long)ldp, (long)rel_stride, pn, (long)pn_stride, (const long *)q_idx, (const long *)c_idx, e,
-                           (long)lde, alpha, out, (long)ldo);
-    else
-        hipLaunchKernelGGL(relation_scores_kernel<false>, grid, block, 0, (hipStream_t)stream, (long)n, k, (int)n_rel, p,
-                           (long)ldp, (long)rel_stride, pn, (long)pn_stride, (const long *)q_idx, (const long *)c_idx, e,
-                           (long)lde, alpha, out, (long)ldo);
+    vec_dispatch(vec_ok(p, ldp, e, lde) && rel_stride % 4 == 0, [&](auto vec) {
+        hipLaunchKernelGGL(relation_scores_kernel<decltype(vec)::value>, grid, block, 0, (hipStream_t)stream, (long)n, k,
+                           (int)n_rel, p, (long)ldp, (long)rel_stride, pn, (long)pn_stride, (const long *)q_idx,
+                           (const long *)c_idx, e, (long)lde, alpha, out, (long)ldo);
+    });
     LKG_CHECK_LAUNCH("lkg_relation_scores_f32");
     return LKG_OK;
 }

@@ -310,16 +310,13 @@ extern "C" int lkg_retrieval_prepare_f32(int64_t n_rows, int64_t n_cand, int32_t
     LKG_REQUIRE(known_filter_complete(rowptr, filter_row, filter_rel, col, eptr, rel), "lkg_retrieval_prepare_f32: incomplete filter");
     const dim3 grid((unsigned)((n_rows + 3) / 4)), block(TK_THREADS);
     const hipStream_t st = (hipStream_t)stream;
-    if (vec_ok(q, ldq, p, ldp))
-        hipLaunchKernelGGL(retrieval_prepare_kernel<true>, grid, block, 0, st, (long)n_rows, (long)n_cand, k, q, (long)ldq,
-                           (const long *)row_q, p, (long)ldp, pn, (long)n_ids, cand_slot, (const long *)key_off, key_n,
-                           (const long *)qkey_off, (const long *)qkey_n, key_s, (const long *)key_id,
-                           (const long *)filter_row, (const long *)filter_rel, rowptr, col, eptr, rel, buckets);
-    else
-        hipLaunchKernelGGL(retrieval_prepare_kernel<false>, grid, block, 0, st, (long)n_rows, (long)n_cand, k, q, (long)ldq,
-                           (const long *)row_q, p, (long)ldp, pn, (long)n_ids, cand_slot, (const long *)key_off, key_n,
-                           (const long *)qkey_off, (const long *)qkey_n, key_s, (const long *)key_id,
-                           (const long *)filter_row, (const long *)filter_rel, rowptr, col, eptr, rel, buckets);
+    vec_dispatch(vec_ok(q, ldq, p, ldp), [&](auto vec) {
+        hipLaunchKernelGGL(retrieval_prepare_kernel<decltype(vec)::value>, grid, block, 0, st, (long)n_rows, (long)n_cand,
+                           k, q, (long)ldq, (const long *)row_q, p, (long)ldp, pn, (long)n_ids, cand_slot,
+                           (const long *)key_off, key_n, (const long *)qkey_off, (const long *)qkey_n, key_s,
+                           (const long *)key_id, (const long *)filter_row, (const long *)filter_rel, rowptr, col, eptr, rel,
+                           buckets);
+    });
     LKG_CHECK_LAUNCH("lkg_retrieval_prepare_f32");
     return LKG_OK;
 }
@@ -338,14 +335,11 @@ extern "C" int lkg_retrieval_count_f32(int64_t n_rows, int64_t n_cand, int32_t k
     LKG_REQUIRE(tiles_q * s_ < INT32_MAX, "lkg_retrieval_count_f32: too many workgroups (split the rows)");
     const dim3 grid((unsigned)(tiles_q * s_)), block(TK_THREADS);
     const hipStream_t st = (hipStream_t)stream;
-    if (vec_ok(q, ldq, p, ldp))
-        hipLaunchKernelGGL(retrieval_count_kernel<true>, grid, block, 0, st, (long)n_rows, (long)n_cand, k, q, (long)ldq,
-                           (const long *)row_q, p, (long)ldp, pn, (const long *)cand_ids, (const long *)key_off, key_n,
-                           key_s, (const long *)key_id, s_, tiles_q, tiles_c, buckets);
-    else
-        hipLaunchKernelGGL(retrieval_count_kernel<false>, grid, block, 0, st, (long)n_rows, (long)n_cand, k, q, (long)ldq,
-                           (const long *)row_q, p, (long)ldp, pn, (const long *)cand_ids, (const long *)key_off, key_n,
-                           key_s, (const long *)key_id, s_, tiles_q, tiles_c, buckets);
+    vec_dispatch(vec_ok(q, ldq, p, ldp), [&](auto vec) {
+        hipLaunchKernelGGL(retrieval_count_kernel<decltype(vec)::value>, grid, block, 0, st, (long)n_rows, (long)n_cand, k,
+                           q, (long)ldq, (const long *)row_q, p, (long)ldp, pn, (const long *)cand_ids,
+                           (const long *)key_off, key_n, key_s, (const long *)key_id, s_, tiles_q, tiles_c, buckets);
+    });
     LKG_CHECK_LAUNCH("lkg_retrieval_count_f32");
     return LKG_OK;
 }

@@ -17,8 +17,11 @@
 // goes to workspace [S][B]; softmax_finish_kernel merges the S partials of a row in split order in float64.  No float
 // atomics: for a given S every bit is the same from run to run.
 //
-// Filtered variants (MASKED): query i drops the sorted candidate positions xcol[xptr[i] .. xptr[i + 1]) from
-// its softmax -- the other known answers of the query.  A dropped column gets z = -inf inside the tile, exactly as a column
+// MASKED (template parameter of the partial and the weights kernel) is the filtered loss: the kernel then
+// reads its last three arguments, the exclusion lists, which the unmasked launches pass as NULL, NULL, 0 and the unmasked
+// instantiations never touch (they compile to the instructions of a kernel without the parameter).  Query i drops the
+// sorted candidate positions xcol[xptr[i] .. xptr[i + 1]) from its softmax -- the other known answers of the query.  A
+// dropped column gets z = -inf inside the tile, exactly as a column
 // past n_c does, BEFORE the running (max, sum) sees it (subtracting the dropped mass afterwards is amplified by
 // 1 / (1 - dropped mass) without bound); the weights kernel stores exactly 0 there.  Lane = row of the wave's 64 walks its
 // row's list with a cursor, turns the entries inside the wave's 64 columns into a 64-bit mask and leaves it in LDS for the
@@ -30,112 +33,22 @@
 
 namespace {
 
-constexpr int SM_THREADS = 256;
-constexpr int SM_ROWS = 64;           // queries per workgroup
-constexpr int SM_COLS = 256;          // candidates per tile (64 per wave)
 constexpr int SM_MAX_SPLITS = LKG_SOFTMAX_MAX_SPLITS;
 
 // exp(z - m) must not see inf - inf: a pair that has met no candidate yet is (-inf, 0) and takes 0 as its reference
 __device__ __forceinline__ float safe_ref(float m) { return m == -__builtin_inff() ? 0.f : m; }
 
-template <bool VEC>
-__global__ __launch_bounds__(SM_THREADS) void softmax_partial_kernel(long n_q, long n_c, int k, const float *__restrict__ q,
-                                                                     long ldq, const float *__restrict__ p, long ldp,
-                                                                     const float *__restrict__ pn, float nsb, int splits,
-                                                                     long tiles_q, long tiles_c, float *__restrict__ ws_m,
-                                                                     float *__restrict__ ws_l) {
-    __shared__ float sm_m[4][SM_ROWS], sm_l[4][SM_ROWS];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int r = lane & 15, s = lane >> 4;
-    const long bid = blockIdx.x;
-    const long q0 = (bid % tiles_q) * SM_ROWS;
-    const int split = (int)(bid / tiles_q);
-    const long t_lo = split * tiles_c / splits, t_hi = (split + 1) * tiles_c / splits;
-    const float *qrow[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) qrow[i] = q + min(q0 + 16 * i + r, n_q - 1) * ldq;    // rows past the end: never written
-    float m[4][4], l[4][4];           // [i][v]: query row 16 i + 4 s + v, the same on the 16 lanes of the row
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int v = 0; v < 4; ++v) {
-            m[i][v] = -__builtin_inff();
-            l[i][v] = 0.f;
-        }
-
-    for (long t = t_lo; t < t_hi; ++t) {
-        const long c0 = t * SM_COLS + wave * 64;
-        const float *prow[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) prow[i] = p + min(c0 + 16 * i + r, n_c - 1) * ldp;
-        f32x4 acc[4][4];
-        rank_tile_dots<VEC>(acc, qrow, prow, k, s);
-        // acc[i][j][v]: query row 16 i + 4 s + v, candidate c0 + 16 j + r
-        float pnv[4];
-        bool ok[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const long c = c0 + 16 * j + r;
-            ok[j] = c < n_c;
-            pnv[j] = (pn && ok[j]) ? pn[c] : 0.f;
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int v = 0; v < 4; ++v) {
-                float z[4], mt = -__builtin_inff();
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {       // a column past the end is -inf: no maximum, exp = 0
-                    z[j] = ok[j] ? nsb * __builtin_fmaf(-2.f, acc[i][j][v], pnv[j]) : -__builtin_inff();
-                    mt = fmaxf(mt, z[j]);           // (a NaN logit is skipped here and poisons l below)
-                }
-                mt = group_max<16>(mt);
-                const float mn = fmaxf(m[i][v], mt), ref = safe_ref(mn);
-                float sum = 0.f;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) sum += expf(z[j] - ref);
-                sum = group_sum<16>(sum);
-                l[i][v] = l[i][v] * expf(m[i][v] - ref) + sum;
-                m[i][v] = mn;
-            }
-    }
-    if (r == 0) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int v = 0; v < 4; ++v) {
-                sm_m[wave][16 * i + 4 * s + v] = m[i][v];
-                sm_l[wave][16 * i + 4 * s + v] = l[i][v];
-            }
-    }
-    __syncthreads();
-    if (tid < SM_ROWS && q0 + tid < n_q) {
-        float mw = sm_m[0][tid];
-#pragma unroll
-        for (int w = 1; w < 4; ++w) mw = fmaxf(mw, sm_m[w][tid]);
-        const float ref = safe_ref(mw);
-        float lw = 0.f;
-#pragma unroll
-        for (int w = 0; w < 4; ++w) lw += sm_l[w][tid] * expf(sm_m[w][tid] - ref);
-        const long o = (long)split * n_q + q0 + tid;
-        ws_m[o] = mw;
-        ws_l[o] = lw;
-    }
-}
-
-// The filtered forward pass: softmax_partial_kernel with the exclusion lists (see the head of this file); everything
-// else -- the tile, nsb * s, the (m, l) recurrence, the meeting in LDS -- is the same text.
-template <bool VEC>
-__global__ __launch_bounds__(SM_THREADS) void softmax_partial_masked_kernel(
+template <bool VEC, bool MASKED>
+__global__ __launch_bounds__(AE_THREADS) void softmax_partial_kernel(
     long n_q, long n_c, int k, const float *__restrict__ q, long ldq, const float *__restrict__ p, long ldp,
     const float *__restrict__ pn, float nsb, int splits, long tiles_q, long tiles_c, float *__restrict__ ws_m,
     float *__restrict__ ws_l, const int *__restrict__ xptr, const int *__restrict__ xcol, int m_total) {
-    __shared__ unsigned long long sm_x[4][SM_ROWS];
-    __shared__ float sm_m[4][SM_ROWS], sm_l[4][SM_ROWS];
+    __shared__ unsigned long long sm_x[4][AE_ROWS];        // MASKED only (unused, it takes no LDS)
+    __shared__ float sm_m[4][AE_ROWS], sm_l[4][AE_ROWS];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r = lane & 15, s = lane >> 4;
     const long bid = blockIdx.x;
-    const long q0 = (bid % tiles_q) * SM_ROWS;
+    const long q0 = (bid % tiles_q) * AE_ROWS;
     const int split = (int)(bid / tiles_q);
     const long t_lo = split * tiles_c / splits, t_hi = (split + 1) * tiles_c / splits;
     const float *qrow[4];
@@ -149,17 +62,19 @@ __global__ __launch_bounds__(SM_THREADS) void softmax_partial_masked_kernel(
             m[i][v] = -__builtin_inff();
             l[i][v] = 0.f;
         }
-    ListCursor x = list_seek(xptr, xcol, m_total, q0 + lane, n_q, t_lo * SM_COLS);
+    ListCursor x{0, 0, INT_MAX};
+    if constexpr (MASKED) x = list_seek(xptr, xcol, m_total, q0 + lane, n_q, t_lo * AE_COLS);
 
     for (long t = t_lo; t < t_hi; ++t) {
-        const long c0 = t * SM_COLS + wave * 64;
+        const long c0 = t * AE_COLS + wave * 64;
         const float *prow[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) prow[i] = p + min(c0 + 16 * i + r, n_c - 1) * ldp;
         f32x4 acc[4][4];
         rank_tile_dots<VEC>(acc, qrow, prow, k, s);
         // acc[i][j][v]: query row 16 i + 4 s + v, candidate c0 + 16 j + r
-        const bool any = list_publish(x, xcol, c0, sm_x[wave], lane);      // wave-uniform: some row drops a column here
+        bool any = false;                                   // wave-uniform: some row drops a column here
+        if constexpr (MASKED) any = list_publish(x, xcol, c0, sm_x[wave], lane);
         float pnv[4];
         bool ok[4];
 #pragma unroll
@@ -174,7 +89,9 @@ __global__ __launch_bounds__(SM_THREADS) void softmax_partial_masked_kernel(
             for (int v = 0; v < 4; ++v) {
                 float z[4], mt = -__builtin_inff();
                 unsigned long long mrow = 0ull;     // the row's dropped columns of the wave's 64
-                if (any) mrow = sm_x[wave][16 * i + 4 * s + v];
+                if constexpr (MASKED) {
+                    if (any) mrow = sm_x[wave][16 * i + 4 * s + v];
+                }
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {       // a column past the end, or a dropped one, is -inf: no maximum, exp = 0
                     const bool keep = ok[j] && !((mrow >> (16 * j + r)) & 1ull);
@@ -201,7 +118,7 @@ __global__ __launch_bounds__(SM_THREADS) void softmax_partial_masked_kernel(
             }
     }
     __syncthreads();
-    if (tid < SM_ROWS && q0 + tid < n_q) {
+    if (tid < AE_ROWS && q0 + tid < n_q) {
         float mw = sm_m[0][tid];
 #pragma unroll
         for (int w = 1; w < 4; ++w) mw = fmaxf(mw, sm_m[w][tid]);
@@ -215,19 +132,18 @@ __global__ __launch_bounds__(SM_THREADS) void softmax_partial_masked_kernel(
     }
 }
 
-
 // One wave per query: the truth's logit with the pair routine of the ranking kernels, the S partials merged in split
 // order in float64, lse and loss rounded once each; lse_lo (nullable) is the remainder of lse's rounding, with which the
 // backward's exp(z - lse) does not carry |lse| u / 2 into every weight of the row.
 template <bool VEC>
-__global__ __launch_bounds__(SM_THREADS) void softmax_finish_kernel(long n_q, long n_c, int k, const float *__restrict__ q,
+__global__ __launch_bounds__(AE_THREADS) void softmax_finish_kernel(long n_q, long n_c, int k, const float *__restrict__ q,
                                                                     long ldq, const float *__restrict__ p, long ldp,
                                                                     const float *__restrict__ pn,
                                                                     const long *__restrict__ truth, float nsb, int splits,
                                                                     const float *__restrict__ ws_m,
                                                                     const float *__restrict__ ws_l, float *__restrict__ lse,
                                                                     float *__restrict__ lse_lo, float *__restrict__ loss) {
-    const long i = (long)blockIdx.x * (SM_THREADS / 64) + (threadIdx.x >> 6);
+    const long i = (long)blockIdx.x * (AE_THREADS / 64) + (threadIdx.x >> 6);
     if (i >= n_q) return;                           // (a whole wave leaves)
     const int lane = threadIdx.x & 63;
     const long tr = min(max(truth[i], 0L), n_c - 1);
@@ -250,78 +166,28 @@ __global__ __launch_bounds__(SM_THREADS) void softmax_finish_kernel(long n_q, lo
 // The backward's recompute: V[i, c] = sb g_i (exp((z_ic - lse_i) - lse_lo_i) - [c_base + c == t_i]) for the n_c candidates
 // of a chunk that starts at candidate c_base of the table (p, pn point at the chunk).  One 64 x 256 tile per workgroup, stored
 // straight from the accumulator layout: the 16 lanes of a row write 64 consecutive bytes.
-template <bool VEC>
-__global__ __launch_bounds__(SM_THREADS) void softmax_weights_kernel(long n_q, long n_c, int k, const float *__restrict__ q,
-                                                                     long ldq, const float *__restrict__ p, long ldp,
-                                                                     const float *__restrict__ pn, long c_base,
-                                                                     const long *__restrict__ truth,
-                                                                     const float *__restrict__ lse,
-                                                                     const float *__restrict__ lse_lo,
-                                                                     const float *__restrict__ g, float nsb, float sb,
-                                                                     float *__restrict__ vout, long ldv, long tiles_q) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int r = lane & 15, s = lane >> 4;
-    const long bid = blockIdx.x;
-    const long q0 = (bid % tiles_q) * SM_ROWS, c0 = (bid / tiles_q) * SM_COLS + wave * 64;
-    const float *qrow[4], *prow[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        qrow[i] = q + min(q0 + 16 * i + r, n_q - 1) * ldq;        // rows and columns past the end are clamped, never stored
-        prow[i] = p + min(c0 + 16 * i + r, n_c - 1) * ldp;
-    }
-    f32x4 acc[4][4];
-    rank_tile_dots<VEC>(acc, qrow, prow, k, s);
-    float pnv[4];
-    long cid[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        cid[j] = c0 + 16 * j + r;
-        pnv[j] = (pn && cid[j] < n_c) ? pn[cid[j]] : 0.f;
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int v = 0; v < 4; ++v) {
-            const long row = q0 + 16 * i + 4 * s + v;
-            const long rr = min(row, n_q - 1);
-            const float ls = lse[rr], lo = lse_lo ? lse_lo[rr] : 0.f, coef = sb * g[rr];
-            const long tl = truth[rr] - c_base;
-            float *out = vout + rr * ldv;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const float z = nsb * __builtin_fmaf(-2.f, acc[i][j][v], pnv[j]);
-                // exp(z - lse) with lse = ls + lo: d = fl(z - ls), its rounding error recovered exactly (TwoSum) and, with
-                // lo, applied to first order -- neither subtraction's rounding (up to |z - lse| u each) reaches the weight
-                const float d = z - ls, zp = d + ls, e = (z - zp) + (-ls - (d - zp));
-                const float w = expf(d) * (1.f + (e - lo)) - (cid[j] == tl ? 1.f : 0.f);
-                if (row < n_q && cid[j] < n_c) out[cid[j]] = coef * w;
-            }
-        }
-}
-
-// The filtered backward's recompute: softmax_weights_kernel, a dropped column stored as exactly 0.
-template <bool VEC>
-__global__ __launch_bounds__(SM_THREADS) void softmax_weights_masked_kernel(
+// MASKED: a dropped column is stored as exactly 0; the lists hold table positions, c_base + the chunk's column.
+template <bool VEC, bool MASKED>
+__global__ __launch_bounds__(AE_THREADS) void softmax_weights_kernel(
     long n_q, long n_c, int k, const float *__restrict__ q, long ldq, const float *__restrict__ p, long ldp,
     const float *__restrict__ pn, long c_base, const long *__restrict__ truth, const float *__restrict__ lse,
     const float *__restrict__ lse_lo, const float *__restrict__ g, float nsb, float sb, float *__restrict__ vout, long ldv,
     long tiles_q, const int *__restrict__ xptr, const int *__restrict__ xcol, int m_total) {
-    __shared__ unsigned long long sm_x[4][SM_ROWS];
+    __shared__ unsigned long long sm_x[4][AE_ROWS];        // MASKED only (unused, it takes no LDS)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r = lane & 15, s = lane >> 4;
     const long bid = blockIdx.x;
-    const long q0 = (bid % tiles_q) * SM_ROWS, c0 = (bid / tiles_q) * SM_COLS + wave * 64;
+    const long q0 = (bid % tiles_q) * AE_ROWS, c0 = (bid / tiles_q) * AE_COLS + wave * 64;
     const float *qrow[4], *prow[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        qrow[i] = q + min(q0 + 16 * i + r, n_q - 1) * ldq;        // rows and columns past the end are clamped, never stored
-        prow[i] = p + min(c0 + 16 * i + r, n_c - 1) * ldp;
-    }
+    tile_rows(qrow, q, ldq, q0, n_q, r);
+    tile_rows(prow, p, ldp, c0, n_c, r);
     f32x4 acc[4][4];
     rank_tile_dots<VEC>(acc, qrow, prow, k, s);
-    // as in the forward pass; the lists hold table positions: c_base + the chunk's column
-    ListCursor x = list_seek(xptr, xcol, m_total, q0 + lane, n_q, c_base + c0);
-    const bool any = list_publish(x, xcol, c_base + c0, sm_x[wave], lane);
+    bool any = false;
+    if constexpr (MASKED) {
+        ListCursor x = list_seek(xptr, xcol, m_total, q0 + lane, n_q, c_base + c0);
+        any = list_publish(x, xcol, c_base + c0, sm_x[wave], lane);
+    }
     float pnv[4];
     long cid[4];
 #pragma unroll
@@ -339,7 +205,9 @@ __global__ __launch_bounds__(SM_THREADS) void softmax_weights_masked_kernel(
             const long tl = truth[rr] - c_base;
             float *out = vout + rr * ldv;
             unsigned long long mrow = 0ull;
-            if (any) mrow = sm_x[wave][16 * i + 4 * s + v];
+            if constexpr (MASKED) {
+                if (any) mrow = sm_x[wave][16 * i + 4 * s + v];
+            }
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const bool dropped = (mrow >> (16 * j + r)) & 1ull;
@@ -353,18 +221,17 @@ __global__ __launch_bounds__(SM_THREADS) void softmax_weights_masked_kernel(
         }
 }
 
-
 // The exclusion lists of the filtered loss, one wave per query and two passes (FILL false: cnt[i] = the length of query
 // i's list; a cumulative sum on the host side makes xptr; FILL true: the entries).  Query i walks the known row frow[i]
 // (lkg_known.h) 64 entries at a time and keeps an entry iff it is known under relation frel[i], maps to a candidate through
 // pos and is not the row's truth.  pos is monotone where it is not -1, so the kept positions come out ascending.
 template <bool FILL>
-__global__ __launch_bounds__(SM_THREADS) void softmax_excluded_kernel(
+__global__ __launch_bounds__(AE_THREADS) void softmax_excluded_kernel(
     long n_q, long n_rows, long n_c, const long *__restrict__ frow, const long *__restrict__ frel,
     const long *__restrict__ truth, const int *__restrict__ rowptr, const int *__restrict__ col,
     const int *__restrict__ eptr, const int *__restrict__ rel, const int *__restrict__ pos, int *__restrict__ cnt,
     const int *__restrict__ xptr, int *__restrict__ xcol) {
-    const long i = (long)blockIdx.x * (SM_THREADS / 64) + (threadIdx.x >> 6);
+    const long i = (long)blockIdx.x * (AE_THREADS / 64) + (threadIdx.x >> 6);
     if (i >= n_q) return;                           // (a whole wave leaves)
     const int lane = threadIdx.x & 63;
     const long f = min(max(frow[i], 0L), n_rows - 1), tr = truth[i];
@@ -394,35 +261,81 @@ __global__ __launch_bounds__(SM_THREADS) void softmax_excluded_kernel(
 
 extern "C" int32_t lkg_softmax_all_splits(int64_t n_q, int64_t n_cand, int32_t requested) {
     if (n_q <= 0 || n_cand <= 0 || requested < 0 || requested > SM_MAX_SPLITS) return 0;
-    const long tiles_q = (n_q + SM_ROWS - 1) / SM_ROWS, tiles_c = (n_cand + SM_COLS - 1) / SM_COLS;
+    const long tiles_q = (n_q + AE_ROWS - 1) / AE_ROWS, tiles_c = (n_cand + AE_COLS - 1) / AE_COLS;
     long s_ = requested > 0 ? requested : (2 * 256 + tiles_q - 1) / tiles_q;   // auto: >= 2 workgroups per CU
     s_ = s_ < SM_MAX_SPLITS ? s_ : SM_MAX_SPLITS;
     s_ = s_ < tiles_c ? s_ : tiles_c;
     return (int32_t)(s_ > 1 ? s_ : 1);
 }
 
+namespace {
+
+// lkg_softmax_all_partial_f32 (MASKED false: no lists) and lkg_softmax_all_partial_masked_f32: the checks and the launch
+template <bool MASKED>
+int softmax_partial(const char *name, int64_t n_q, int64_t n_cand, int32_t k, const float *q, int64_t ldq, const float *p,
+                    int64_t ldp, const float *pn, float scale, int32_t splits, const int32_t *xptr, const int32_t *xcol,
+                    int64_t n_excl, float *ws_m, float *ws_l, void *stream) {
+    LKG_REQUIRE(n_q >= 0 && n_cand > 0 && n_cand < INT32_MAX && k > 0 && ldq >= k && ldp >= k &&
+                    (!MASKED || (n_excl >= 0 && n_excl < INT32_MAX)),
+                "%s: bad sizes", name);
+    LKG_REQUIRE(scale_ok(scale), "%s: scale must be positive and finite", name);
+    if (n_q == 0) return LKG_OK;
+    LKG_REQUIRE(splits >= 1 && splits == lkg_softmax_all_splits(n_q, n_cand, splits),
+                "%s: splits must come from lkg_softmax_all_splits", name);
+    LKG_REQUIRE(q && p && ws_m && ws_l && (!MASKED || (xptr && (xcol || n_excl == 0))), "%s: null pointer", name);
+    const long tiles_q = (n_q + AE_ROWS - 1) / AE_ROWS, tiles_c = (n_cand + AE_COLS - 1) / AE_COLS;
+    LKG_REQUIRE(tiles_q * splits < INT32_MAX, "%s: too many workgroups (split the queries)", name);
+    const dim3 grid((unsigned)(tiles_q * splits)), block(AE_THREADS);
+    const float nsb = neg_scale_beta(scale, pn);
+    vec_dispatch(vec_ok(q, ldq, p, ldp), [&](auto vec) {
+        hipLaunchKernelGGL((softmax_partial_kernel<decltype(vec)::value, MASKED>), grid, block, 0, (hipStream_t)stream,
+                           (long)n_q, (long)n_cand, k, q, (long)ldq, p, (long)ldp, pn, nsb, splits, tiles_q, tiles_c, ws_m,
+                           ws_l, xptr, xcol, (int)n_excl);
+    });
+    LKG_CHECK_LAUNCH(name);
+    return LKG_OK;
+}
+
+// lkg_softmax_all_weights_f32 and lkg_softmax_all_weights_masked_f32, in the same way
+template <bool MASKED>
+int softmax_weights(const char *name, int64_t n_q, int64_t n_cand, int32_t k, const float *q, int64_t ldq, const float *p,
+                    int64_t ldp, const float *pn, int64_t c_base, const int64_t *truth, const float *lse,
+                    const float *lse_lo, const float *g, float scale, const int32_t *xptr, const int32_t *xcol,
+                    int64_t n_excl, float *v, int64_t ldv, void *stream) {
+    LKG_REQUIRE(n_q >= 0 && n_cand >= 0 && n_cand < INT32_MAX && k > 0 && ldq >= k && ldp >= k && ldv >= n_cand &&
+                    c_base >= 0 && (!MASKED || (c_base < INT32_MAX && n_excl >= 0 && n_excl < INT32_MAX)),
+                "%s: bad sizes", name);
+    LKG_REQUIRE(scale_ok(scale), "%s: scale must be positive and finite", name);
+    if (n_q == 0 || n_cand == 0) return LKG_OK;
+    LKG_REQUIRE(q && p && truth && lse && g && v && (!MASKED || (xptr && (xcol || n_excl == 0))), "%s: null pointer", name);
+    const long tiles_q = (n_q + AE_ROWS - 1) / AE_ROWS, tiles_c = (n_cand + AE_COLS - 1) / AE_COLS;
+    LKG_REQUIRE(tiles_q * tiles_c < INT32_MAX, "%s: too many tiles (use smaller chunks)", name);
+    const dim3 grid((unsigned)(tiles_q * tiles_c)), block(AE_THREADS);
+    const float nsb = neg_scale_beta(scale, pn);
+    vec_dispatch(vec_ok(q, ldq, p, ldp), [&](auto vec) {
+        hipLaunchKernelGGL((softmax_weights_kernel<decltype(vec)::value, MASKED>), grid, block, 0, (hipStream_t)stream,
+                           (long)n_q, (long)n_cand, k, q, (long)ldq, p, (long)ldp, pn, (long)c_base, (const long *)truth,
+                           lse, lse_lo, g, nsb, -nsb, v, (long)ldv, tiles_q, xptr, xcol, (int)n_excl);
+    });
+    LKG_CHECK_LAUNCH(name);
+    return LKG_OK;
+}
+
+}  // namespace
+
 extern "C" int lkg_softmax_all_partial_f32(int64_t n_q, int64_t n_cand, int32_t k, const float *q, int64_t ldq,
                                            const float *p, int64_t ldp, const float *pn, float scale, int32_t splits,
                                            float *ws_m, float *ws_l, void *stream) {
-    LKG_REQUIRE(n_q >= 0 && n_cand > 0 && n_cand < INT32_MAX && k > 0 && ldq >= k && ldp >= k,
-                "lkg_softmax_all_partial_f32: bad sizes");
-    LKG_REQUIRE(scale_ok(scale), "lkg_softmax_all_partial_f32: scale must be positive and finite");
-    if (n_q == 0) return LKG_OK;
-    LKG_REQUIRE(splits >= 1 && splits == lkg_softmax_all_splits(n_q, n_cand, splits),
-                "lkg_softmax_all_partial_f32: splits must come from lkg_softmax_all_splits");
-    LKG_REQUIRE(q && p && ws_m && ws_l, "lkg_softmax_all_partial_f32: null pointer");
-    const long tiles_q = (n_q + SM_ROWS - 1) / SM_ROWS, tiles_c = (n_cand + SM_COLS - 1) / SM_COLS;
-    LKG_REQUIRE(tiles_q * splits < INT32_MAX, "lkg_softmax_all_partial_f32: too many workgroups (split the queries)");
-    const dim3 grid((unsigned)(tiles_q * splits)), block(SM_THREADS);
-    const float nsb = neg_scale_beta(scale, pn);
-    if (vec_ok(q, ldq, p, ldp))
-        hipLaunchKernelGGL(softmax_partial_kernel<true>, grid, block, 0, (hipStream_t)stream, (long)n_q, (long)n_cand, k,
-                           q, (long)ldq, p, (long)ldp, pn, nsb, splits, tiles_q, tiles_c, ws_m, ws_l);
-    else
-        hipLaunchKernelGGL(softmax_partial_kernel<false>, grid, block, 0, (hipStream_t)stream, (long)n_q, (long)n_cand, k,
-                           q, (long)ldq, p, (long)ldp, pn, nsb, splits, tiles_q, tiles_c, ws_m, ws_l);
-    LKG_CHECK_LAUNCH("lkg_softmax_all_partial_f32");
-    return LKG_OK;
+    return softmax_partial<false>("lkg_softmax_all_partial_f32", n_q, n_cand, k, q, ldq, p, ldp, pn, scale, splits,
+                                  nullptr, nullptr, 0, ws_m, ws_l, stream);
+}
+
+extern "C" int lkg_softmax_all_partial_masked_f32(int64_t n_q, int64_t n_cand, int32_t k, const float *q, int64_t ldq,
+                                                  const float *p, int64_t ldp, const float *pn, float scale,
+                                                  int32_t splits, const int32_t *xptr, const int32_t *xcol, int64_t n_excl,
+                                                  float *ws_m, float *ws_l, void *stream) {
+    return softmax_partial<true>("lkg_softmax_all_partial_masked_f32", n_q, n_cand, k, q, ldq, p, ldp, pn, scale, splits,
+                                 xptr, xcol, n_excl, ws_m, ws_l, stream);
 }
 
 extern "C" int lkg_softmax_all_finish_f32(int64_t n_q, int64_t n_cand, int32_t k, const float *q, int64_t ldq,
@@ -436,14 +349,13 @@ extern "C" int lkg_softmax_all_finish_f32(int64_t n_q, int64_t n_cand, int32_t k
                 SM_MAX_SPLITS);
     if (n_q == 0) return LKG_OK;
     LKG_REQUIRE(q && p && truth && ws_m && ws_l && lse && loss, "lkg_softmax_all_finish_f32: null pointer");
-    const dim3 grid((unsigned)((n_q + 3) / 4)), block(SM_THREADS);
+    const dim3 grid((unsigned)((n_q + 3) / 4)), block(AE_THREADS);
     const float nsb = neg_scale_beta(scale, pn);
-    if (vec_ok(q, ldq, p, ldp))
-        hipLaunchKernelGGL(softmax_finish_kernel<true>, grid, block, 0, (hipStream_t)stream, (long)n_q, (long)n_cand, k, q,
-                           (long)ldq, p, (long)ldp, pn, (const long *)truth, nsb, splits, ws_m, ws_l, lse, lse_lo, loss);
-    else
-        hipLaunchKernelGGL(softmax_finish_kernel<false>, grid, block, 0, (hipStream_t)stream, (long)n_q, (long)n_cand, k,
-                           q, (long)ldq, p, (long)ldp, pn, (const long *)truth, nsb, splits, ws_m, ws_l, lse, lse_lo, loss);
+    vec_dispatch(vec_ok(q, ldq, p, ldp), [&](auto vec) {
+        hipLaunchKernelGGL(softmax_finish_kernel<decltype(vec)::value>, grid, block, 0, (hipStream_t)stream, (long)n_q,
+                           (long)n_cand, k, q, (long)ldq, p, (long)ldp, pn, (const long *)truth, nsb, splits, ws_m, ws_l,
+                           lse, lse_lo, loss);
+    });
     LKG_CHECK_LAUNCH("lkg_softmax_all_finish_f32");
     return LKG_OK;
 }
@@ -452,26 +364,17 @@ extern "C" int lkg_softmax_all_weights_f32(int64_t n_q, int64_t n_cand, int32_t 
                                            const float *p, int64_t ldp, const float *pn, int64_t c_base,
                                            const int64_t *truth, const float *lse, const float *lse_lo, const float *g,
                                            float scale, float *v, int64_t ldv, void *stream) {
-    LKG_REQUIRE(n_q >= 0 && n_cand >= 0 && n_cand < INT32_MAX && k > 0 && ldq >= k && ldp >= k && ldv >= n_cand &&
-                    c_base >= 0,
-                "lkg_softmax_all_weights_f32: bad sizes");
-    LKG_REQUIRE(scale_ok(scale), "lkg_softmax_all_weights_f32: scale must be positive and finite");
-    if (n_q == 0 || n_cand == 0) return LKG_OK;
-    LKG_REQUIRE(q && p && truth && lse && g && v, "lkg_softmax_all_weights_f32: null pointer");
-    const long tiles_q = (n_q + SM_ROWS - 1) / SM_ROWS, tiles_c = (n_cand + SM_COLS - 1) / SM_COLS;
-    LKG_REQUIRE(tiles_q * tiles_c < INT32_MAX, "lkg_softmax_all_weights_f32: too many tiles (use smaller chunks)");
-    const dim3 grid((unsigned)(tiles_q * tiles_c)), block(SM_THREADS);
-    const float nsb = neg_scale_beta(scale, pn);
-    if (vec_ok(q, ldq, p, ldp))
-        hipLaunchKernelGGL(softmax_weights_kernel<true>, grid, block, 0, (hipStream_t)stream, (long)n_q, (long)n_cand, k,
-                           q, (long)ldq, p, (long)ldp, pn, (long)c_base, (const long *)truth, lse, lse_lo, g, nsb, -nsb, v,
-                           (long)ldv, tiles_q);
-    else
-        hipLaunchKernelGGL(softmax_weights_kernel<false>, grid, block, 0, (hipStream_t)stream, (long)n_q, (long)n_cand, k,
-                           q, (long)ldq, p, (long)ldp, pn, (long)c_base, (const long *)truth, lse, lse_lo, g, nsb, -nsb, v,
-                           (long)ldv, tiles_q);
-    LKG_CHECK_LAUNCH("lkg_softmax_all_weights_f32");
-    return LKG_OK;
+    return softmax_weights<false>("lkg_softmax_all_weights_f32", n_q, n_cand, k, q, ldq, p, ldp, pn, c_base, truth, lse,
+                                  lse_lo, g, scale, nullptr, nullptr, 0, v, ldv, stream);
+}
+
+extern "C" int lkg_softmax_all_weights_masked_f32(int64_t n_q, int64_t n_cand, int32_t k, const float *q, int64_t ldq,
+                                                  const float *p, int64_t ldp, const float *pn, int64_t c_base,
+                                                  const int64_t *truth, const float *lse, const float *lse_lo,
+                                                  const float *g, float scale, const int32_t *xptr, const int32_t *xcol,
+                                                  int64_t n_excl, float *v, int64_t ldv, void *stream) {
+    return softmax_weights<true>("lkg_softmax_all_weights_masked_f32", n_q, n_cand, k, q, ldq, p, ldp, pn, c_base, truth,
+                                 lse, lse_lo, g, scale, xptr, xcol, n_excl, v, ldv, stream);
 }
 
 extern "C" int lkg_softmax_excluded(int64_t n_q, int64_t n_rows, int64_t n_cand, const int64_t *filter_row,
@@ -484,7 +387,7 @@ extern "C" int lkg_softmax_excluded(int64_t n_q, int64_t n_rows, int64_t n_cand,
                 "lkg_softmax_excluded: either count (first pass) or xptr and xcol (second pass)");
     if (n_q == 0) return LKG_OK;
     LKG_REQUIRE(filter_row && filter_rel && truth && rowptr && col && eptr && rel, "lkg_softmax_excluded: null pointer");
-    const dim3 grid((unsigned)((n_q + 3) / 4)), block(SM_THREADS);
+    const dim3 grid((unsigned)((n_q + 3) / 4)), block(AE_THREADS);
     if (count)
         hipLaunchKernelGGL(softmax_excluded_kernel<false>, grid, block, 0, (hipStream_t)stream, (long)n_q, (long)n_rows,
                            (long)n_cand, (const long *)filter_row, (const long *)filter_rel, (const long *)truth, rowptr,
@@ -494,64 +397,6 @@ extern "C" int lkg_softmax_excluded(int64_t n_q, int64_t n_rows, int64_t n_cand,
                            (long)n_cand, (const long *)filter_row, (const long *)filter_rel, (const long *)truth, rowptr,
                            col, eptr, rel, pos, count, xptr, xcol);
     LKG_CHECK_LAUNCH("lkg_softmax_excluded");
-    return LKG_OK;
-}
-
-extern "C" int lkg_softmax_all_partial_masked_f32(int64_t n_q, int64_t n_cand, int32_t k, const float *q, int64_t ldq,
-                                                  const float *p, int64_t ldp, const float *pn, float scale,
-                                                  int32_t splits, const int32_t *xptr, const int32_t *xcol, int64_t n_excl,
-                                                  float *ws_m, float *ws_l, void *stream) {
-    LKG_REQUIRE(n_q >= 0 && n_cand > 0 && n_cand < INT32_MAX && k > 0 && ldq >= k && ldp >= k && n_excl >= 0 &&
-                    n_excl < INT32_MAX,
-                "lkg_softmax_all_partial_masked_f32: bad sizes");
-    LKG_REQUIRE(scale_ok(scale), "lkg_softmax_all_partial_masked_f32: scale must be positive and finite");
-    if (n_q == 0) return LKG_OK;
-    LKG_REQUIRE(splits >= 1 && splits == lkg_softmax_all_splits(n_q, n_cand, splits),
-                "lkg_softmax_all_partial_masked_f32: splits must come from lkg_softmax_all_splits");
-    LKG_REQUIRE(q && p && ws_m && ws_l && xptr && (xcol || n_excl == 0),
-                "lkg_softmax_all_partial_masked_f32: null pointer");
-    const long tiles_q = (n_q + SM_ROWS - 1) / SM_ROWS, tiles_c = (n_cand + SM_COLS - 1) / SM_COLS;
-    LKG_REQUIRE(tiles_q * splits < INT32_MAX,
-                "lkg_softmax_all_partial_masked_f32: too many workgroups (split the queries)");
-    const dim3 grid((unsigned)(tiles_q * splits)), block(SM_THREADS);
-    const float nsb = neg_scale_beta(scale, pn);
-    if (vec_ok(q, ldq, p, ldp))
-        hipLaunchKernelGGL(softmax_partial_masked_kernel<true>, grid, block, 0, (hipStream_t)stream, (long)n_q,
-                           (long)n_cand, k, q, (long)ldq, p, (long)ldp, pn, nsb, splits, tiles_q, tiles_c, ws_m, ws_l, xptr,
-                           xcol, (int)n_excl);
-    else
-        hipLaunchKernelGGL(softmax_partial_masked_kernel<false>, grid, block, 0, (hipStream_t)stream, (long)n_q,
-                           (long)n_cand, k, q, (long)ldq, p, (long)ldp, pn, nsb, splits, tiles_q, tiles_c, ws_m, ws_l, xptr,
-                           xcol, (int)n_excl);
-    LKG_CHECK_LAUNCH("lkg_softmax_all_partial_masked_f32");
-    return LKG_OK;
-}
-
-extern "C" int lkg_softmax_all_weights_masked_f32(int64_t n_q, int64_t n_cand, int32_t k, const float *q, int64_t ldq,
-                                                  const float *p, int64_t ldp, const float *pn, int64_t c_base,
-                                                  const int64_t *truth, const float *lse, const float *lse_lo,
-                                                  const float *g, float scale, const int32_t *xptr, const int32_t *xcol,
-                                                  int64_t n_excl, float *v, int64_t ldv, void *stream) {
-    LKG_REQUIRE(n_q >= 0 && n_cand >= 0 && n_cand < INT32_MAX && k > 0 && ldq >= k && ldp >= k && ldv >= n_cand &&
-                    c_base >= 0 && c_base < INT32_MAX && n_excl >= 0 && n_excl < INT32_MAX,
-                "lkg_softmax_all_weights_masked_f32: bad sizes");
-    LKG_REQUIRE(scale_ok(scale), "lkg_softmax_all_weights_masked_f32: scale must be positive and finite");
-    if (n_q == 0 || n_cand == 0) return LKG_OK;
-    LKG_REQUIRE(q && p && truth && lse && g && v && xptr && (xcol || n_excl == 0),
-                "lkg_softmax_all_weights_masked_f32: null pointer");
-    const long tiles_q = (n_q + SM_ROWS - 1) / SM_ROWS, tiles_c = (n_cand + SM_COLS - 1) / SM_COLS;
-    LKG_REQUIRE(tiles_q * tiles_c < INT32_MAX, "lkg_softmax_all_weights_masked_f32: too many tiles (use smaller chunks)");
-    const dim3 grid((unsigned)(tiles_q * tiles_c)), block(SM_THREADS);
-    const float nsb = neg_scale_beta(scale, pn);
-    if (vec_ok(q, ldq, p, ldp))
-        hipLaunchKernelGGL(softmax_weights_masked_kernel<true>, grid, block, 0, (hipStream_t)stream, (long)n_q,
-                           (long)n_cand, k, q, (long)ldq, p, (long)ldp, pn, (long)c_base, (const long *)truth, lse, lse_lo, g,
-                           nsb, -nsb, v, (long)ldv, tiles_q, xptr, xcol, (int)n_excl);
-    else
-        hipLaunchKernelGGL(softmax_weights_masked_kernel<false>, grid, block, 0, (hipStream_t)stream, (long)n_q,
-                           (long)n_cand, k, q, (long)ldq, p, (long)ldp, pn, (long)c_base, (const long *)truth, lse, lse_lo, g,
-                           nsb, -nsb, v, (long)ldv, tiles_q, xptr, xcol, (int)n_excl);
-    LKG_CHECK_LAUNCH("lkg_softmax_all_weights_masked_f32");
     return LKG_OK;
 }
 

@@ -247,14 +247,11 @@ extern "C" int lkg_topk_select_f32(int64_t n_q, int64_t n_cand, int32_t k, const
     LKG_REQUIRE(tiles_q * splits < INT32_MAX, "lkg_topk_select_f32: too many workgroups (split the queries)");
     const dim3 grid((unsigned)(tiles_q * splits));
     const hipStream_t st = (hipStream_t)stream;
-    if (vec_ok(q, ldq, p, ldp))
-        launch_select_kc<true>(grid, st, n_q, n_cand, k, q, ldq, p, ldp, pn, (const long *)cand_ids,
-                               (const long *)filter_row, (const long *)filter_rel, rowptr, col, eptr, rel, top_k,
-                               splits, tiles_q, tiles_c, ws_s, ws_i);
-    else
-        launch_select_kc<false>(grid, st, n_q, n_cand, k, q, ldq, p, ldp, pn, (const long *)cand_ids,
-                                (const long *)filter_row, (const long *)filter_rel, rowptr, col, eptr, rel, top_k,
-                                splits, tiles_q, tiles_c, ws_s, ws_i);
+    vec_dispatch(vec_ok(q, ldq, p, ldp), [&](auto vec) {
+        launch_select_kc<decltype(vec)::value>(grid, st, n_q, n_cand, k, q, ldq, p, ldp, pn, (const long *)cand_ids,
+                                               (const long *)filter_row, (const long *)filter_rel, rowptr, col, eptr, rel,
+                                               top_k, splits, tiles_q, tiles_c, ws_s, ws_i);
+    });
     LKG_CHECK_LAUNCH("lkg_topk_select_f32");
     return LKG_OK;
 }

@@ -136,14 +136,11 @@ extern "C" int lkg_triple_scores_f32(int64_t n, int32_t k, const float *p, int64
     LKG_REQUIRE(p && q_idx && c_idx, "lkg_triple_scores_f32: null pointer");
     const long blocks = (n + TS_TRIPLES - 1) / TS_TRIPLES;
     const dim3 grid((unsigned)(blocks < TS_GRID ? blocks : TS_GRID)), block(TS_THREADS);
-    if (vec_ok(p, ldp, e, e ? lde : 0))
-        hipLaunchKernelGGL(triple_scores_kernel<true>, grid, block, 0, (hipStream_t)stream, (long)n, k, p, (long)ldp,
-                           (const long *)q_idx, (const long *)c_idx, pn, e, (long)lde, (const long *)rel, alpha,
+    vec_dispatch(vec_ok(p, ldp, e, e ? lde : 0), [&](auto vec) {
+        hipLaunchKernelGGL(triple_scores_kernel<decltype(vec)::value>, grid, block, 0, (hipStream_t)stream, (long)n, k, p,
+                           (long)ldp, (const long *)q_idx, (const long *)c_idx, pn, e, (long)lde, (const long *)rel, alpha,
                            (int)flags, labels, thr, out, (unsigned long long *)counts);
-    else
-        hipLaunchKernelGGL(triple_scores_kernel<false>, grid, block, 0, (hipStream_t)stream, (long)n, k, p, (long)ldp,
-                           (const long *)q_idx, (const long *)c_idx, pn, e, (long)lde, (const long *)rel, alpha,
-                           (int)flags, labels, thr, out, (unsigned long long *)counts);
+    });
     LKG_CHECK_LAUNCH("lkg_triple_scores_f32");
     return LKG_OK;
 }
