@@ -521,13 +521,13 @@ def check_attention(lines, what, g, ent, rel, val, logits, vec, row_lo=0, row_hi
 
 
 # =============================================================================================== (g) scores and losses
-def draw_triples(device, form, dim, b, group=1, offset=False, seed=0):
+def draw_triples(device, form, dim, b, group=1, offset=False, seed=0, n_rel=3):
     """Trained-like tables: a small pool of heads (ids repeated hundreds of times at b = 1025); for every (h, r) a tail whose
     row is h + r + 1e-3 noise; far rows at a distance^2 of 50 .. 250, so that neg - pos reaches +-90.  A third of the triples
     has the near tail as t+ (neg - pos >> 0), a third as t- (<< 0), the rest two far rows.  form: transe | dot | transr
     (rows are then the PROJECTED rows' stand-ins: the caller projects with identity-like matrices)"""
     gen = gen_for(device, 8000 + seed + dim + 3 * b + group + int(offset))
-    n_heads, n_rel, n_far = 4, 3, 40
+    n_heads, n_far = 4, 40
     n_ent = n_heads + n_heads * n_rel + n_far
     emb = table_view(gen, device, n_ent, dim, offset)
     rel = table_view(gen, device, n_rel, dim, offset, 0.5)
