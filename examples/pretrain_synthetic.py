@@ -83,7 +83,16 @@ def main():
     ap.add_argument("--ordered-products", action="store_true",
                     help="with --objective one_vs_all, kvs_all or relation: the backward's long reductions run on the ordered "
                          "split-K GEMM (literalkg_amd.product_route('ordered')); the other objectives have none")
+    ap.add_argument("--prune-to-batch", action="store_true",
+                    help="evaluate every layer on the batch's frontier only (model.prune_to_batch; the objectives that read a "
+                         "few thousand rows: sampled, self_adversarial, relation)")
+    ap.add_argument("--fanout", type=int, default=None,
+                    help="with --prune-to-batch: a row aggregates at most this many of its stored neighbours per training "
+                         "step, drawn anew every step (model.neighbor_fanout)")
+    ap.add_argument("--neighbor-seed", type=int, default=0, help="with --fanout: the seed of the neighbour draws")
     a = ap.parse_args()
+    if a.fanout is not None and not a.prune_to_batch:
+        ap.error("--fanout goes with --prune-to-batch")
     if a.filtered and a.objective not in ("one_vs_all", "relation"):
         ap.error("--filtered goes with --objective one_vs_all or relation")
     if a.sampler == "triples" and a.objective != "self_adversarial":
@@ -101,6 +110,8 @@ def main():
     h, t, r = make_kg(a.entities, a.edges)
     num = torch.rand(a.entities, 2)
     model = LiteralKG(args, a.entities, 16, initial_a_in(a.entities, h, t, r), num, None)
+    model.prune_to_batch = a.prune_to_batch
+    model.neighbor_fanout, model.neighbor_seed = a.fanout, a.neighbor_seed
     optimizer = torch.optim.Adam(model.parameters(), lr=a.lr)
     model.to(device)
     h_list, t_list, r_list = (torch.from_numpy(x).to(device) for x in (h, t, r))

@@ -28,6 +28,7 @@ from .negatives import (NegativeBatch, NegativeSampler, RelationCardinalities, T
 from .relation_loss import relation_loss, relation_softmax_loss   # noqa: F401  (the name relation_loss is the FUNCTION here)
 from .gemm_ordered import (current_route, gemm_ordered, gemm_ordered_splits, matmul_ordered,   # noqa: F401  (gemm_ordered: the
                            product_route)                                                      # FUNCTION here, as above)
+from .pruned import sample_neighbors   # noqa: F401
 
 __all__ = ["LiteralKG", "Aggregator", "Gate", "GateMul", "KGStructure", "KnownTriples", "RankResult", "evaluate_ranking",
            "TopKResult", "predict_topk", "FoldedMLPHead", "fold_mlp_head", "mlp_scores", "rank_pairs_mlp",
@@ -38,4 +39,5 @@ __all__ = ["LiteralKG", "Aggregator", "Gate", "GateMul", "KGStructure", "KnownTr
            "sigmoid_all_loss", "distinct_queries", "self_adversarial_loss", "sampled_sigmoid_loss", "group_sampled_batch",
            "NegativeSampler", "NegativeBatch", "TripleEpoch", "RelationCardinalities", "relation_cardinalities",
            "answer_counts", "subsampling_weights", "sampled_negative_loss", "relation_loss", "relation_softmax_loss",
-           "gemm_ordered", "gemm_ordered_splits", "matmul_ordered", "product_route", "current_route"]
+           "gemm_ordered", "gemm_ordered_splits", "matmul_ordered", "product_route", "current_route",
+           "sample_neighbors"]

@@ -165,6 +165,10 @@ ORDERED_GEMM_PROTOTYPES = {
     "lkg_gemm_ordered_workspace": [i64, i64, i64, i32],
     "lkg_gemm_ordered_f32": [i32, i32, i64, i64, i64, i32, f32, vp, i64, vp, i64, f32, vp, i64, vp, vp, i64, vp],
 }
+# the seventh table: include/literalkg_hip_neighbors.h (neighbour sampling for the batch-pruned step), mirrored the same way
+NEIGHBOR_PROTOTYPES = {
+    "lkg_csr_sample_rows": [i64, vp, vp, vp, vp, i32, u64, u64, i32, vp, vp, vp, vp],
+}
 _RESTYPE = {"lkg_last_error": C.c_char_p, "lkg_csr_build_device_workspace": C.c_int64,
             "lkg_gemm_tall_workspace": C.c_int64, "lkg_gemm_workspace": C.c_int64,
             "lkg_linear_act_layernorm_workspace": C.c_int64, "lkg_narrow_layer_bwd_workspace": C.c_int64,
@@ -195,7 +199,7 @@ def load():
     lib = C.CDLL(_LIB_PATH)
     for name, argtypes in list(PROTOTYPES.items()) + list(EXTRA_PROTOTYPES.items()) + list(TRAIN_PROTOTYPES.items()) + \
             list(SAMPLE_PROTOTYPES.items()) + list(RELATION_TRAIN_PROTOTYPES.items()) + \
-            list(ORDERED_GEMM_PROTOTYPES.items()):
+            list(ORDERED_GEMM_PROTOTYPES.items()) + list(NEIGHBOR_PROTOTYPES.items()):
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
         fn.argtypes = argtypes
         fn.restype = _RESTYPE.get(name, C.c_int)

@@ -461,7 +461,10 @@ class ShardedLiteralKG(nn.Module):
         model(h, pos_t, neg_t, device=dev, mode="fine_tuning");  model(heads, tails, device=dev, mode="predict" | "mlp")
 
     ``model.parameters()`` = this rank's rows of ``entity_embed`` + the replicated weights, so any optimizer keeps the
-    entity table's state sharded (no optimizer traffic).  ``full_state_dict()`` gathers a reference-shaped checkpoint."""
+    entity table's state sharded (no optimizer traffic).  ``full_state_dict()`` gathers a reference-shaped checkpoint.
+
+    The sharded step replaces the batch-pruned path of the local module with its own row exchange and does NOT sample
+    neighbours: ``neighbor_fanout`` of the local module is cleared, every row aggregates all of its stored entries."""
 
     def __init__(self, local, part: RowPartition, scheme: str, kernels, group=None, sparse_backward: str = "auto",
                  pipelined: bool = True):
@@ -474,6 +477,7 @@ class ShardedLiteralKG(nn.Module):
         self._att: Optional[DistributedAttention] = None
         local._attention = self._attention   # the layers aggregate through the distributed exchange
         local.prune_to_batch = False
+        local.neighbor_fanout = None         # (no neighbour sampling here: it lives in the pruned path this module replaces)
         local.id_space = part.n              # callers hand in GLOBAL entity ids
         # the heads read rows of the concatenated table by id: they get the gathered rows and positions into them --
         # the contract of the batch-pruned path (model.LiteralKG._embeddings_and_ids), so the module's own head code runs

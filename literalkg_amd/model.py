@@ -321,6 +321,14 @@ class LiteralKG(nn.Module):
         # self.gat_embed holds the rows self.gat_rows instead of all N
         self.prune_to_batch = bool(getattr(args, "prune_to_batch", False))
         self.prune_max_fraction = 0.5     # frontier larger than this share of the entities: the dense path is cheaper
+        # opt-in, inside the pruned path and in training mode only: a row aggregates at most neighbor_fanout of its stored
+        # neighbours per step (pruned.sample_rows: the draw is a function of (neighbor_seed, neighbor_draw, row id)); every
+        # sampled subgraph build uses neighbor_draw and then increments it -- set it back to repeat a step
+        self.neighbor_fanout = getattr(args, "neighbor_fanout", None)
+        self.neighbor_seed = 0
+        self.neighbor_draw = 0
+        self.neighbor_rescale = True      # kept values times d / fanout: the sampled neighbour sum estimates the full one
+        self.last_step_sampled = False    # did the last subgraph build sample (False: exact, or the dense fall-back)
         self.gat_rows = None
         self.group_reuse = True           # TransR: project (h, t+) once per group of pre_training_neg_rate rows
         # linear_gat on the rows the loss reads instead of all N (calc_triplet_loss); LKG_ROWS_ONLY_PROJECTION=0: as the reference
@@ -439,13 +447,34 @@ class LiteralKG(nn.Module):
 
     PRUNE_RETRY_EVERY = 64
 
+    def _neighbor_sampling(self) -> Optional[int]:
+        """The fanout the next subgraph build samples with, or None: sampling is active in training mode with
+        ``neighbor_fanout`` set (eval mode runs the exact path, as dropout is off there).  A fanout that is no int >= 1, or set
+        where the pruned path does not run (``prune_to_batch`` off, 'gin'), is a ValueError -- raised here, ahead of any
+        device work of the call."""
+        if self.neighbor_fanout is None or not self.training:
+            return None
+        fanout = pruned.checked_fanout(self.neighbor_fanout)
+        if not self.prune_to_batch:
+            raise ValueError("neighbor_fanout needs prune_to_batch = True: neighbours are sampled inside the batch-pruned step")
+        if self.aggregation_type == "gin":
+            raise ValueError("neighbor_fanout does not apply to aggregation_type 'gin': the batch-pruned step does not support it")
+        return fanout
+
     def gat_embeddings_for(self, ids: torch.Tensor):
         """Rows `unique(ids)` of gat_embeddings(), computed on the batch's L-hop frontier only (pruned.py).
         Returns (compact table, BatchSubgraph), or (None, None) when the frontier covers more than
-        ``prune_max_fraction`` of the entities (large batches x many layers: the dense path is cheaper then)."""
+        ``prune_max_fraction`` of the entities (large batches x many layers: the dense path is cheaper then).
+        With neighbour sampling active the frontier is that of the sampled matrix (draw ``neighbor_draw``, which is then
+        incremented) and ``last_step_sampled`` says whether the returned subgraph is a sampled one."""
+        fanout = self._neighbor_sampling()
         att = self._attention()
         sub = pruned.build_batch_subgraph(att.graph, att.val, ids, self.n_layers,
-                                          max_rows=int(self.prune_max_fraction * self.n_entities))
+                                          max_rows=int(self.prune_max_fraction * self.n_entities), fanout=fanout,
+                                          seed=self.neighbor_seed, draw=self.neighbor_draw, rescale=self.neighbor_rescale)
+        if fanout is not None:
+            self.neighbor_draw += 1
+        self.last_step_sampled = fanout is not None and sub is not None
         if sub is None:
             return None, None
         top = self.n_layers
@@ -504,8 +533,10 @@ class LiteralKG(nn.Module):
 
     def _embeddings_and_ids(self, *id_lists):
         """(table, relabelled ids): the full table with the ids as given, or the pruned table with positions."""
+        self._neighbor_sampling()                 # (a fanout that cannot apply raises before anything is launched)
         if not self._can_prune():
             self.gat_rows = None
+            self.last_step_sampled = False
             return self._table_for_inference(), id_lists
         table, sub = self.gat_embeddings_for(torch.cat([i.reshape(-1) for i in id_lists]))
         if table is None:
@@ -519,6 +550,7 @@ class LiteralKG(nn.Module):
     def calc_triplet_loss(self, h, r, pos_t, neg_t):
         # generate_kg_batch repeats every sampled (h, r, t+) pre_training_neg_rate times (dataloader.py:318-330): such
         # a batch projects h and t+ once per group.  Checked on the ids (any other batch takes the general path).
+        self._neighbor_sampling()
         h, pos_t, neg_t = ops.checked_ids(self.id_space, h, pos_t, neg_t)     # (out-of-range ids never reach a kernel)
         (r,) = ops.checked_ids(self.n_relations, r, what="relation")
         check, k = None, int(self.pre_training_neg_rate)
@@ -545,6 +577,7 @@ class LiteralKG(nn.Module):
             # the loss reads <= 3B rows: the N-row copy of the raw entity table into slot 0 of the concatenated table is
             # deferred (made only if somebody asks for self.gat_embed), its columns are read from the raw table
             self.gat_rows = None
+            self.last_step_sampled = False
             table, raw = self.gat_embeddings(defer_slot0=True)
             self._gat_state = (table, raw)        # (a tuple: nn.Module would register a bare Parameter attribute)
             group = k if (check is not None and check.result()) else 1
@@ -595,6 +628,7 @@ class LiteralKG(nn.Module):
         side 'tail' (the negatives replace the tail) or 'head'.  Reads only the (2 + K) G rows it scores, so
         prune_to_batch applies; no L2 term.  There is no mode= string for it."""
         from .self_adversarial import self_adversarial_loss
+        self._neighbor_sampling()
         return self_adversarial_loss(self, h, r, t, neg, side=side, margin=margin, scale=scale, temperature=temperature,
                                      reduction=reduction, scoring=scoring)
 
@@ -605,6 +639,7 @@ class LiteralKG(nn.Module):
         calc_self_adversarial_loss scores them alone (one table for both), the per-group losses back in group order,
         weighted by ``weights`` (e.g. subsampling_weights): 'mean' is sum(w L) / sum(w)."""
         from .negatives import sampled_negative_loss
+        self._neighbor_sampling()
         return sampled_negative_loss(self, h, r, t, batch, weights=weights, margin=margin, scale=scale,
                                      temperature=temperature, reduction=reduction, scoring=scoring)
 
@@ -616,6 +651,7 @@ class LiteralKG(nn.Module):
         evaluate_relation_prediction's filtered metric.  Reads two table rows per pair, so prune_to_batch applies; no L2
         term.  products as in calc_one_vs_all_loss.  There is no mode= string for it."""
         from .relation_loss import relation_loss
+        self._neighbor_sampling()
         return relation_loss(self, h, r, t, known=known, scoring=scoring, scale=scale, reduction=reduction,
                              chunk_bytes=chunk_bytes, products=products)
 
@@ -628,6 +664,7 @@ class LiteralKG(nn.Module):
     def _unprojected_table(self):
         """The concatenated table without linear_gat; it stays behind self.gat_embed, projected on first access."""
         self.gat_rows = None
+        self.last_step_sampled = False
         cat = self.gat_embeddings(project=False)
         self._gat_state = (cat, None, True)
         self._raise_bad_ids()
@@ -734,6 +771,7 @@ class LiteralKG(nn.Module):
 
     # ------------------------------------------------------------------ f1 heads
     def calc_score(self, head_ids, tail_ids):
+        self._neighbor_sampling()
         head_ids, tail_ids = ops.checked_ids(self.id_space, head_ids, tail_ids)
         emb, (head_ids, tail_ids) = self._embeddings_and_ids(head_ids, tail_ids)
         self._raise_bad_ids()
@@ -887,6 +925,7 @@ class LiteralKG(nn.Module):
         """mode='mlp' (model.py:506-519): sigmoid(fc3(bn2(relu(fc2(bn1(relu(fc1([e_h | e_t])))))))) ."""
         if not hasattr(self, "fc1"):
             raise AttributeError("call initialize_MLP() first (model.py:499)")
+        self._neighbor_sampling()
         head_ids, tail_ids = ops.checked_ids(self.id_space, head_ids, tail_ids)
         self.gat_embed, (head_ids, tail_ids) = self._embeddings_and_ids(head_ids, tail_ids)
         self._raise_bad_ids()
@@ -923,6 +962,7 @@ class LiteralKG(nn.Module):
 
     def calculate_prediction_loss(self, head_ids, tail_pos_ids, tail_neg_ids):
         """f1: dot-product BPR fine-tuning loss (model.py:316-348)."""
+        self._neighbor_sampling()
         head_ids, tail_pos_ids, tail_neg_ids = ops.checked_ids(self.id_space, head_ids, tail_pos_ids, tail_neg_ids)
         if self._rows_only_projection_applies() and (self.training or torch.is_grad_enabled()):
             rows, (head_ids, tail_pos_ids, tail_neg_ids) = self._projected_rows(self._unprojected_table(), head_ids, tail_pos_ids,

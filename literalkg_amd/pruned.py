@@ -13,6 +13,12 @@ so no transpose is built per step.  Loss, scores and every parameter gradient eq
 fp32 summation order (tests/test_gpu_parity.py::test_pruned_*); only the dropout mask indexes compact rows.
 
 Index bookkeeping (unique / searchsorted / cumsum over a few thousand ids) uses torch device ops.
+
+Neighbour sampling (opt-in on top: ``model.neighbor_fanout = f``, training mode only).  Where the frontier explodes -- a hub
+row pulls its whole neighbourhood in at every level -- a row may aggregate at most f of its stored entries per step:
+``lkg_csr_sample_rows`` stands in for ``lkg_csr_extract_rows`` at every level.  The draw is counter-based and stated exactly
+(include/literalkg_hip_neighbors.h): a row's sample depends on (seed, draw, row id, the row's entries) alone, the same at
+every level, so a sampled step is the EXACT step of the matrix ``sample_neighbors(graph, val, f, seed, draw)``.
 """
 from __future__ import annotations
 
@@ -49,11 +55,63 @@ class BatchSubgraph:
         return torch.searchsorted(self.rows[base], self.rows[k])
 
 
+def checked_fanout(fanout) -> int:
+    """A fanout is an int >= 1 (bool and float are refused: True and 4.0 are somebody's mistake, not a count)."""
+    if isinstance(fanout, bool) or not isinstance(fanout, int) or fanout < 1:
+        raise ValueError(f"neighbour fanout must be an int >= 1, got {fanout!r}")
+    if fanout > 2 ** 31 - 1:
+        raise ValueError(f"neighbour fanout {fanout} does not fit int32 (a row holds fewer than 2^31 entries: use None)")
+    return fanout
+
+
+_U64 = (1 << 64) - 1
+
+
+@torch.no_grad()
+def sample_rows(graph: KGStructure, val: torch.Tensor, rows: torch.Tensor, fanout: int, seed: int = 0, draw: int = 0,
+                rescale: bool = True):
+    """At most ``fanout`` stored entries of every row of ``rows`` (sorted int64 ids) as a compact CSR
+    (out_rowptr, out_col, out_val), out_col holding the original ids: lkg_csr_sample_rows, whose header
+    (include/literalkg_hip_neighbors.h) states the draw.  A row's sample depends on (seed, draw, its id, its entries) alone.
+    One host read: the number of kept entries, as the exact extraction does."""
+    fanout = checked_fanout(fanout)
+    ops._need_gpu(rows, val)
+    rp = graph.rowptr
+    deg = (rp[rows + 1] - rp[rows]).clamp(max=fanout)
+    out_rowptr = torch.zeros(rows.numel() + 1, dtype=torch.int32, device=rows.device)
+    out_rowptr[1:] = torch.cumsum(deg, 0)
+    m = int(out_rowptr[-1])                                       # the one host sync per level
+    out_col = torch.empty(max(m, 1), dtype=torch.int32, device=rows.device)
+    out_val = torch.empty(max(m, 1), dtype=torch.float32, device=rows.device)
+    if m:
+        N.call("lkg_csr_sample_rows", rows.numel(), N.ptr(rows), N.ptr(rp), N.ptr(graph.col), N.ptr(val), fanout,
+               int(seed) & _U64, int(draw) & _U64, int(bool(rescale)), N.ptr(out_rowptr), N.ptr(out_col), N.ptr(out_val),
+               ops._stream())
+    return out_rowptr, out_col[:m], out_val[:m]
+
+
+@torch.no_grad()
+def sample_neighbors(graph: KGStructure, val: torch.Tensor, fanout: int, seed: int = 0, draw: int = 0, rescale: bool = True,
+                     rows: Optional[torch.Tensor] = None):
+    """The sampled matrix A' = sample(A, seed, draw) as (rowptr, col, val) over ``rows`` (sorted unique ids; None: all
+    graph.n rows): what a sampled training step of that seed and draw aggregates over, at every level -- a sampled step is
+    the exact step of A'.  col keeps the original ids."""
+    if rows is None:
+        rows = torch.arange(graph.n, dtype=torch.int64, device=val.device)
+    return sample_rows(graph, val, ops._i64(rows), fanout, seed, draw, rescale)
+
+
 @torch.no_grad()
 def build_batch_subgraph(graph: KGStructure, val: torch.Tensor, ids: torch.Tensor, n_layers: int,
-                         max_rows: Optional[int] = None) -> Optional[BatchSubgraph]:
+                         max_rows: Optional[int] = None, fanout: Optional[int] = None, seed: int = 0, draw: int = 0,
+                         rescale: bool = True) -> Optional[BatchSubgraph]:
     """max_rows: give up (None) as soon as a level's row set outgrows it -- the caller takes the dense path, and a deep model
-    does not pay for eight levels of bookkeeping to find that out (the reference's default architecture: two levels instead)."""
+    does not pay for eight levels of bookkeeping to find that out (the reference's default architecture: two levels instead).
+    fanout (None: every stored entry, the exact step): each level keeps at most that many entries of a row (sample_rows) --
+    the same sample of a row at every level, so the result is the exact subgraph of sample_neighbors(graph, val, fanout,
+    seed, draw, rescale); max_rows then bounds the sampled frontier."""
+    if fanout is not None:
+        fanout = checked_fanout(fanout)
     ops._need_gpu(ids, val)
     rows = [None] * (n_layers + 1)
     layers: List[Optional[SubLayer]] = [None] * (n_layers + 1)
@@ -61,15 +119,19 @@ def build_batch_subgraph(graph: KGStructure, val: torch.Tensor, ids: torch.Tenso
     rp = graph.rowptr
     for k in range(n_layers, 0, -1):
         rk = rows[k]
-        deg = rp[rk + 1] - rp[rk]
-        out_rowptr = torch.zeros(rk.numel() + 1, dtype=torch.int32, device=rk.device)
-        out_rowptr[1:] = torch.cumsum(deg, 0)
-        m = int(out_rowptr[-1])                                   # the one host sync per layer
-        out_col = torch.empty(max(m, 1), dtype=torch.int32, device=rk.device)
-        out_val = torch.empty(max(m, 1), dtype=torch.float32, device=rk.device)
-        if m:                                    # (no entry to extract: an empty matrix, or rows that are nobody's head)
-            N.call("lkg_csr_extract_rows", rk.numel(), N.ptr(rk), N.ptr(rp), N.ptr(graph.col), N.ptr(val),
-                   N.ptr(out_rowptr), N.ptr(out_col), N.ptr(out_val), ops._stream())
+        if fanout is not None:
+            out_rowptr, out_col, out_val = sample_rows(graph, val, rk, fanout, seed, draw, rescale)
+            m = out_col.numel()
+        else:
+            deg = rp[rk + 1] - rp[rk]
+            out_rowptr = torch.zeros(rk.numel() + 1, dtype=torch.int32, device=rk.device)
+            out_rowptr[1:] = torch.cumsum(deg, 0)
+            m = int(out_rowptr[-1])                                   # the one host sync per layer
+            out_col = torch.empty(max(m, 1), dtype=torch.int32, device=rk.device)
+            out_val = torch.empty(max(m, 1), dtype=torch.float32, device=rk.device)
+            if m:                                    # (no entry to extract: an empty matrix, or rows that are nobody's head)
+                N.call("lkg_csr_extract_rows", rk.numel(), N.ptr(rk), N.ptr(rp), N.ptr(graph.col), N.ptr(val),
+                       N.ptr(out_rowptr), N.ptr(out_col), N.ptr(out_val), ops._stream())
         col_ids = out_col[:m].long()
         prev = torch.unique(torch.cat([rk, col_ids]))
         if max_rows is not None and prev.numel() > max_rows:
