@@ -14,8 +14,8 @@ from .ranking import KnownTriples, RankResult, evaluate_ranking   # noqa: F401
 from .topk import TopKResult, predict_topk   # noqa: F401
 from .accepted import AcceptedResult, count_accepted, predict_accepted   # noqa: F401
 from .retrieval import AnswerRanks, evaluate_retrieval, rank_answers   # noqa: F401
-from .pairmlp import (FoldedMLPHead, evaluate_mlp_classification, evaluate_mlp_ranking,   # noqa: F401
-                      fold_mlp_head, mlp_scores, rank_pairs_mlp, score_pairs_mlp)
+from .pairmlp import (FoldedMLPHead, count_accepted_mlp, evaluate_mlp_classification, evaluate_mlp_ranking,   # noqa: F401
+                      fold_mlp_head, mlp_scores, predict_accepted_mlp, rank_pairs_mlp, score_pairs_mlp)
 from .triples import (TripleThresholds, evaluate_triple_classification, fit_triple_thresholds,   # noqa: F401
                       score_triples)
 from .relations import (RelationTopK, evaluate_relation_prediction, predict_relations, rank_relations,   # noqa: F401
@@ -40,4 +40,4 @@ __all__ = ["LiteralKG", "Aggregator", "Gate", "GateMul", "KGStructure", "KnownTr
            "NegativeSampler", "NegativeBatch", "TripleEpoch", "RelationCardinalities", "relation_cardinalities",
            "answer_counts", "subsampling_weights", "sampled_negative_loss", "relation_loss", "relation_softmax_loss",
            "gemm_ordered", "gemm_ordered_splits", "matmul_ordered", "product_route", "current_route",
-           "sample_neighbors"]
+           "sample_neighbors", "predict_accepted_mlp", "count_accepted_mlp"]

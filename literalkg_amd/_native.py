@@ -169,6 +169,13 @@ ORDERED_GEMM_PROTOTYPES = {
 NEIGHBOR_PROTOTYPES = {
     "lkg_csr_sample_rows": [i64, vp, vp, vp, vp, i32, u64, u64, i32, vp, vp, vp, vp],
 }
+# the eighth table: include/literalkg_hip_pair_accept.h (threshold retrieval under the MLP pair head), mirrored the same way
+_PAIR_ACCEPT_HEAD = [i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp]   # .. splits, counts
+PAIR_ACCEPT_PROTOTYPES = {
+    "lkg_pair_mlp_accept_count_f32": _PAIR_ACCEPT_HEAD + [vp],
+    "lkg_pair_mlp_accept_append_f32": _PAIR_ACCEPT_HEAD + [i64, vp, vp, vp, vp, vp],
+    "lkg_pair_mlp_accept_emit_f32": _PAIR_ACCEPT_HEAD + [vp, vp, vp, vp, vp, vp, vp],
+}
 _RESTYPE = {"lkg_last_error": C.c_char_p, "lkg_csr_build_device_workspace": C.c_int64,
             "lkg_gemm_tall_workspace": C.c_int64, "lkg_gemm_workspace": C.c_int64,
             "lkg_linear_act_layernorm_workspace": C.c_int64, "lkg_narrow_layer_bwd_workspace": C.c_int64,
@@ -199,7 +206,8 @@ def load():
     lib = C.CDLL(_LIB_PATH)
     for name, argtypes in list(PROTOTYPES.items()) + list(EXTRA_PROTOTYPES.items()) + list(TRAIN_PROTOTYPES.items()) + \
             list(SAMPLE_PROTOTYPES.items()) + list(RELATION_TRAIN_PROTOTYPES.items()) + \
-            list(ORDERED_GEMM_PROTOTYPES.items()) + list(NEIGHBOR_PROTOTYPES.items()):
+            list(ORDERED_GEMM_PROTOTYPES.items()) + list(NEIGHBOR_PROTOTYPES.items()) + \
+            list(PAIR_ACCEPT_PROTOTYPES.items()):
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
         fn.argtypes = argtypes
         fn.restype = _RESTYPE.get(name, C.c_int)

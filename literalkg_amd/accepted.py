@@ -34,7 +34,9 @@ class AcceptedResult:
     """The accepted candidates of B queries in CSR form, on the model's device: query i owns [rowptr[i], rowptr[i + 1]) of
     ``ids`` (int64 entity ids, best first), ``scores`` (float32 reported scores, the bits of score_triples) and
     ``kernel_scores`` (float32 s, the ordering key, the bits of TopKResult.kernel_scores); ``counts`` = the lengths.
-    ``query_ids`` / ``r`` are the queries as given (on the device), which triples() pairs the lists with."""
+    ``query_ids`` / ``r`` are the queries as given (on the device), which triples() and pairs() pair the lists with.
+    From predict_accepted_mlp (pairmlp.py) ``scores`` are probabilities and ``kernel_scores`` logits, as in a TopKResult
+    under scoring='mlp'."""
     rowptr: torch.Tensor
     ids: torch.Tensor
     scores: torch.Tensor
@@ -48,9 +50,18 @@ class AcceptedResult:
         """(h, r, t), int64[M] each: the proposed triples in list order."""
         if self.r is None:
             raise ValueError("the queries carry no relation (r=None): there are pairs here, not triples")
-        rows = torch.repeat_interleave(torch.arange(self.counts.numel(), device=self.counts.device), self.counts)
+        rows = self._rows()
         q, r = self.query_ids[rows], self.r[rows]
         return (q, r, self.ids) if self.side == "tail" else (self.ids, r, q)
+
+    def pairs(self):
+        """(h, t), int64[M] each: the listed pairs in list order, whichever side was asked; works with r=None (the lists
+        of predict_accepted_mlp, pairmlp.py, whose scores are probabilities and kernel_scores logits)."""
+        q = self.query_ids[self._rows()]
+        return (q, self.ids) if self.side == "tail" else (self.ids, q)
+
+    def _rows(self):
+        return torch.repeat_interleave(torch.arange(self.counts.numel(), device=self.counts.device), self.counts)
 
 
 def _check_max_total(max_total) -> int:

@@ -26,6 +26,7 @@
 // every tile, so a push always lands.
 #include "lkg_rank_common.h"
 #include "lkg_topk_common.h"
+#include "../../include/literalkg_hip_pair_accept.h"
 
 namespace {
 
@@ -449,6 +450,98 @@ __global__ __launch_bounds__(PM_THREADS) void pair_mlp_pairs_kernel(
     if (tid < 5 && cnt[tid]) atomicAdd(counts + tid, (unsigned long long)cnt[tid]);
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Threshold retrieval under the head (predict_accepted_mlp, count_accepted_mlp; include/literalkg_hip_pair_accept.h):
+// the count kernel's loop with ONE compare per logit, z > thr[row], and the filter lookup only on a pass.  Three modes
+// share every instruction up to the decision:
+//   PM_ACC_COUNT   the pass is added to the row's LDS counter; one integer global add per row and workgroup.
+//   PM_ACC_APPEND  count, and the entry takes a slot from ONE global cursor: (row, id, z) is written when the slot lies
+//                  below `capacity`, nothing otherwise -- the counts stay exact either way, and the host sees an
+//                  overflow as sum(counts) > capacity.
+//   PM_ACC_EMIT    the entry takes a slot from its row's cursor and is written at base[row] + slot when the slot lies
+//                  inside the row's counted length; otherwise nothing is written and the flag is raised.
+// Entries land in an arbitrary order, which lkg_accept_order fixes: (s = -2 z, id) is unique within a row.
+enum { PM_ACC_COUNT = 0, PM_ACC_APPEND = 1, PM_ACC_EMIT = 2 };
+
+template <int MODE>
+__global__ __launch_bounds__(PM_THREADS) void pair_mlp_accept_kernel(
+    long n_q, long n_c, const float *__restrict__ uq, long ldu, const float *__restrict__ vt, long ldv,
+    const float *__restrict__ w2, const float *__restrict__ b2, const float *__restrict__ w3,
+    const float *__restrict__ b3, const float *__restrict__ thr, const long *__restrict__ cand,
+    const long *__restrict__ frow, const long *__restrict__ frel, const int *__restrict__ rowptr,
+    const int *__restrict__ col, const int *__restrict__ eptr, const int *__restrict__ rel, int splits, int qr,
+    long tiles_q, long tiles_c, int *__restrict__ counts, long capacity, unsigned long long *__restrict__ gcursor,
+    int *__restrict__ out_row, int *__restrict__ out_id32, const long *__restrict__ base, int *__restrict__ cursor,
+    long *__restrict__ out_id, float *__restrict__ out_s, float *__restrict__ out_z, int *__restrict__ flag) {
+    __shared__ __attribute__((aligned(16))) float su[PM_ROWS * PM_H1];
+    __shared__ float sthr[PM_ROWS];
+    __shared__ int cnt[PM_ROWS];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int r = lane & 15, s = lane >> 4;
+    const long bid = blockIdx.x;
+    const long q0 = (bid % tiles_q) * qr;
+    const long split = bid / tiles_q;
+    const long t_lo = split * tiles_c / splits, t_hi = (split + 1) * tiles_c / splits;
+    const int nq = (int)(n_q - q0 < qr ? n_q - q0 : qr);
+    if (tid < PM_ROWS) {
+        sthr[tid] = tid < nq ? thr[q0 + tid] : __builtin_nanf("");
+        cnt[tid] = 0;
+    }
+    pm_stage_u(su, uq, ldu, q0, nq);
+    PairWeights w;
+    pm_load_weights(w, w2, b2, w3, b3, r, s);
+    __syncthreads();
+    // as in pair_mlp_count_kernel: lane qi holds query qi's threshold (read with v_readlane, qi being uniform) and lane
+    // (r < 4, s) takes its candidate's logit through bit masks; a lane that speaks for no candidate takes a NaN, which
+    // never passes
+    const int my_thr = __float_as_int(sthr[lane]);
+    int pick[4];
+#pragma unroll
+    for (int x = 0; x < 4; ++x) pick[x] = r == x ? -1 : 0;
+    for (long t = t_lo; t < t_hi; ++t) {
+        float4 vf[PM_H1 / 16];
+        long cw;
+        const bool mine = pm_open_tile(vf, cw, t, wave, r, s, vt, ldv, n_c);
+        const int none = mine ? 0 : 0x7fc00000;
+        const int cid = mine ? (int)(cand ? cand[cw] : cw) : TK_NONE;
+        for (int qi = 0; qi < nq; ++qi) {
+            float z[4];
+            pm_pair_logits(z, su + qi * PM_H1, vf, w, s);
+            const float tq = __int_as_float(__builtin_amdgcn_readlane(my_thr, qi));
+            const float zc = __int_as_float((__float_as_int(z[0]) & pick[0]) | (__float_as_int(z[1]) & pick[1]) |
+                                            (__float_as_int(z[2]) & pick[2]) | (__float_as_int(z[3]) & pick[3]) | none);
+            if (zc > tq) {                                           // rare at the selectivities this is built for
+                const long grow = q0 + qi;
+                if (rowptr && known_lookup(rowptr, col, eptr, rel, frow[grow], (int)frel[grow], cid)) continue;
+                if (MODE != PM_ACC_EMIT) atomicAdd(&cnt[qi], 1);
+                if (MODE == PM_ACC_APPEND) {
+                    const unsigned long long slot = atomicAdd(gcursor, 1ull);
+                    if (slot < (unsigned long long)capacity) {
+                        out_row[slot] = (int)grow;
+                        out_id32[slot] = cid;
+                        out_z[slot] = zc;
+                    }
+                }
+                if (MODE == PM_ACC_EMIT) {
+                    const int slot = atomicAdd(cursor + grow, 1);
+                    if (slot >= 0 && slot < counts[grow]) {
+                        const long o = base[grow] + slot;
+                        out_id[o] = cid;
+                        out_s[o] = -2.f * zc;
+                        out_z[o] = zc;
+                    } else {
+                        atomicOr(flag, 1);
+                    }
+                }
+            }
+        }
+    }
+    if (MODE != PM_ACC_EMIT) {
+        __syncthreads();
+        if (tid < nq && cnt[tid]) atomicAdd(counts + q0 + tid, cnt[tid]);
+    }
+}
+
 // candidate splits of the count kernel: enough workgroups for a smooth tail, each with a long run of tiles, and never
 // fewer than two workgroups per CU while there are tiles to hand out
 long pm_count_splits(long tiles_q, long tiles_c) {
@@ -587,6 +680,81 @@ extern "C" int lkg_pair_mlp_pairs_f32(int64_t n_pairs, const float *u, int64_t l
                        (unsigned long long *)counts);
     LKG_CHECK_LAUNCH("lkg_pair_mlp_pairs_f32");
     return LKG_OK;
+}
+
+namespace {
+
+template <int MODE>
+int pm_launch_accept(const char *name, int64_t n_q, int64_t n_cand, const float *uq, const float *v,
+                     const float *w2, const float *b2, const float *w3, const float *b3, const float *thr,
+                     const int64_t *cand_ids, const int64_t *filter_row, const int64_t *filter_rel, const int32_t *rowptr,
+                     const int32_t *col, const int32_t *eptr, const int32_t *rel, int32_t splits, int32_t *counts,
+                     int64_t capacity, int64_t *gcursor, int32_t *out_rows, int32_t *out_ids32, const int64_t *base,
+                     int32_t *cursor, int64_t *out_ids, float *out_s, float *out_z, int32_t *flag, void *stream) {
+    LKG_REQUIRE(n_q >= 0 && n_q < INT32_MAX && n_cand >= 0 && n_cand < INT32_MAX, "%s: bad sizes", name);
+    LKG_REQUIRE(splits >= 0 && splits <= LKG_TOPK_MAX_SPLITS, "%s: splits must lie in [0, %d]", name, LKG_TOPK_MAX_SPLITS);
+    LKG_REQUIRE(MODE != PM_ACC_APPEND || (capacity >= 0 && capacity < INT32_MAX), "%s: capacity must lie in [0, 2^31 - 1)",
+                name);
+    if (n_q == 0 || n_cand == 0) return LKG_OK;
+    LKG_REQUIRE(uq && v && w2 && b2 && w3 && b3 && thr && counts, "%s: null pointer", name);
+    LKG_REQUIRE(pm_operands_ok(uq, PM_H1, v, PM_H1, w2),
+                "%s: uq, v and w2 must be 16-byte aligned", name);
+    LKG_REQUIRE(MODE != PM_ACC_APPEND || (gcursor && (capacity == 0 || (out_rows && out_ids32 && out_z))),
+                "%s: null pointer", name);
+    LKG_REQUIRE(MODE != PM_ACC_EMIT || (base && cursor && out_ids && out_s && out_z && flag), "%s: null pointer", name);
+    LKG_REQUIRE(known_filter_complete(rowptr, filter_row, filter_rel, col, eptr, rel), "%s: incomplete filter", name);
+    const int s_ = lkg_pair_mlp_splits(n_q, n_cand, splits);      // the split policy of the select launch
+    LKG_REQUIRE(s_ >= 1, "%s: no split count for these sizes", name);
+    const long qr = pm_select_rows(n_q);
+    const long tiles_q = (n_q + qr - 1) / qr, tiles_c = (n_cand + PM_COLS - 1) / PM_COLS;
+    LKG_REQUIRE(tiles_q * s_ < INT32_MAX, "%s: too many workgroups (split the queries)", name);
+    hipLaunchKernelGGL((pair_mlp_accept_kernel<MODE>), dim3((unsigned)(tiles_q * s_)), dim3(PM_THREADS), 0,
+                       (hipStream_t)stream, (long)n_q, (long)n_cand, uq, (long)PM_H1, v, (long)PM_H1, w2, b2, w3, b3, thr,
+                       (const long *)cand_ids, (const long *)filter_row, (const long *)filter_rel, rowptr, col, eptr, rel,
+                       s_, (int)qr, tiles_q, tiles_c, counts, (long)capacity, (unsigned long long *)gcursor, out_rows,
+                       out_ids32, (const long *)base, cursor, (long *)out_ids, out_s, out_z, flag);
+    LKG_CHECK_LAUNCH(name);
+    return LKG_OK;
+}
+
+}  // namespace
+
+extern "C" int lkg_pair_mlp_accept_count_f32(int64_t n_q, int64_t n_cand, const float *uq, const float *v,
+                                             const float *w2, const float *b2, const float *w3,
+                                             const float *b3, const float *thr, const int64_t *cand_ids,
+                                             const int64_t *filter_row, const int64_t *filter_rel, const int32_t *rowptr,
+                                             const int32_t *col, const int32_t *eptr, const int32_t *rel, int32_t splits,
+                                             int32_t *counts, void *stream) {
+    return pm_launch_accept<PM_ACC_COUNT>("lkg_pair_mlp_accept_count_f32", n_q, n_cand, uq, v, w2, b2, w3, b3, thr,
+                                          cand_ids, filter_row, filter_rel, rowptr, col, eptr, rel, splits, counts, 0,
+                                          nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                          stream);
+}
+
+extern "C" int lkg_pair_mlp_accept_append_f32(int64_t n_q, int64_t n_cand, const float *uq, const float *v,
+                                              const float *w2, const float *b2, const float *w3,
+                                              const float *b3, const float *thr, const int64_t *cand_ids,
+                                              const int64_t *filter_row, const int64_t *filter_rel, const int32_t *rowptr,
+                                              const int32_t *col, const int32_t *eptr, const int32_t *rel, int32_t splits,
+                                              int32_t *counts, int64_t capacity, int64_t *cursor, int32_t *out_rows,
+                                              int32_t *out_ids, float *out_logits, void *stream) {
+    return pm_launch_accept<PM_ACC_APPEND>("lkg_pair_mlp_accept_append_f32", n_q, n_cand, uq, v, w2, b2, w3, b3,
+                                           thr, cand_ids, filter_row, filter_rel, rowptr, col, eptr, rel, splits, counts,
+                                           capacity, cursor, out_rows, out_ids, nullptr, nullptr, nullptr, nullptr,
+                                           out_logits, nullptr, stream);
+}
+
+extern "C" int lkg_pair_mlp_accept_emit_f32(int64_t n_q, int64_t n_cand, const float *uq, const float *v,
+                                            const float *w2, const float *b2, const float *w3,
+                                            const float *b3, const float *thr, const int64_t *cand_ids,
+                                            const int64_t *filter_row, const int64_t *filter_rel, const int32_t *rowptr,
+                                            const int32_t *col, const int32_t *eptr, const int32_t *rel, int32_t splits,
+                                            const int32_t *counts, const int64_t *base, int32_t *cursor, int64_t *out_ids,
+                                            float *out_scores, float *out_logits, int32_t *flag, void *stream) {
+    return pm_launch_accept<PM_ACC_EMIT>("lkg_pair_mlp_accept_emit_f32", n_q, n_cand, uq, v, w2, b2, w3, b3, thr,
+                                         cand_ids, filter_row, filter_rel, rowptr, col, eptr, rel, splits,
+                                         const_cast<int32_t *>(counts), 0, nullptr, nullptr, nullptr, base, cursor, out_ids,
+                                         out_scores, out_logits, flag, stream);
 }
 
 int lkg_internal_preload_pairmlp() {

@@ -886,6 +886,25 @@ class LiteralKG(nn.Module):
         return count_accepted(self, ids, r, thresholds, side=side, known=known, scoring=scoring, candidates=candidates,
                               batch_size=batch_size, splits=splits)
 
+    def predict_accepted_pairs(self, ids, r=None, threshold: float = 0.5, logit_threshold=None, side: str = "tail",
+                               known=None, candidates=None, batch_size: Optional[int] = None, splits: int = 0,
+                               max_total: int = 1 << 26, buffer: int = 1 << 22):
+        """Every pair (ids, ?) (side 'tail') or (?, ids) (side 'head') that the MLP pair head accepts -- logit > threshold
+        -- and that is not already known, best first (literalkg_amd/pairmlp.py, predict_accepted_mlp).  Returns an
+        accepted.AcceptedResult whose scores are probabilities and whose kernel_scores are logits."""
+        from .pairmlp import predict_accepted_mlp
+        return predict_accepted_mlp(self, ids, r=r, threshold=threshold, logit_threshold=logit_threshold, side=side,
+                                    known=known, candidates=candidates, batch_size=batch_size, splits=splits,
+                                    max_total=max_total, buffer=buffer)
+
+    def count_accepted_pairs(self, ids, r=None, threshold: float = 0.5, logit_threshold=None, side: str = "tail",
+                             known=None, candidates=None, batch_size: Optional[int] = None, splits: int = 0):
+        """int64[B]: how many pairs predict_accepted_pairs would list for every query (literalkg_amd/pairmlp.py,
+        count_accepted_mlp); nothing of the size of the lists is allocated."""
+        from .pairmlp import count_accepted_mlp
+        return count_accepted_mlp(self, ids, r=r, threshold=threshold, logit_threshold=logit_threshold, side=side,
+                                  known=known, candidates=candidates, batch_size=batch_size, splits=splits)
+
     def rank_answers(self, h, r, t, side: str = "tail", known=None, scoring: Optional[str] = None, candidates=None,
                      batch_size: Optional[int] = None, ks=None):
         """The place of every answer of every distinct query (h, r, ?) -- or (?, r, t) -- in the query's ranked list, each

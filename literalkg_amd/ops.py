@@ -2451,6 +2451,101 @@ def pair_mlp_rank_count(uq: torch.Tensor, v: torch.Tensor, w2: torch.Tensor, b2:
     return better, equal, thr
 
 
+def _pair_mlp_accept_operands(what, uq, v, w2, b2, w3, b3, thr, filt, filter_row, filter_rel, cand_ids, splits):
+    """The checked operands of a pair-head accept launch: (head arguments of the entry points, n_q, n_c, device, keep) --
+    keep holds the tensors whose pointers the arguments carry."""
+    _, splits = _check_k_splits(what, 1, splits)
+    _need_gpu(thr, cand_ids, filter_row, filter_rel)
+    uq, v, w2, b2, w3, b3 = _pair_mlp_operands(what, uq, v, w2, b2, w3, b3)
+    n_q, n_c = uq.shape[0], v.shape[0]
+    if cand_ids is not None and cand_ids.numel() != n_c:
+        raise ValueError(f"{what}: {cand_ids.numel()} candidate ids for {n_c} candidate rows")
+    if not isinstance(thr, torch.Tensor) or thr.dtype != torch.float32 or thr.dim() != 1 or thr.numel() != n_q:
+        raise ValueError(f"{what}: thr must be a float32 tensor of {n_q} elements (one logit threshold per query)")
+    if max(n_q, n_c) > 2 ** 31 - 2:
+        raise ValueError(f"{what}: {n_q} queries, {n_c} candidates (at most 2^31 - 2 each)")
+    thr = thr.contiguous()
+    uq, v = (t if _ld(t) == PAIR_MLP_H1 else t.contiguous() for t in (uq, v))     # dense rows: the entry points take no stride
+    cand_ids = _i64(cand_ids.reshape(-1)) if cand_ids is not None else None
+    fargs = _filter_args(what, filt, filter_row, filter_rel, n_q)
+    head = [n_q, n_c, N.ptr(uq), N.ptr(v), N.ptr(w2), N.ptr(b2), N.ptr(w3), N.ptr(b3), N.ptr(thr),
+            N.ptr(cand_ids), *fargs(), splits]
+    return head, n_q, n_c, uq.device, (uq, v, w2, b2, w3, b3, thr, cand_ids, fargs)
+
+
+def pair_mlp_accept_count(uq: torch.Tensor, v: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor, w3: torch.Tensor,
+                          b3: torch.Tensor, thr: torch.Tensor, filt=None, filter_row: Optional[torch.Tensor] = None,
+                          filter_rel: Optional[torch.Tensor] = None, cand_ids: Optional[torch.Tensor] = None,
+                          splits: int = 0) -> torch.Tensor:
+    """int32[n_q]: per query row of uq the number of candidate rows of v whose logit -- the bits of pair_mlp_scores --
+    passes ``z > thr[i]`` in one float32 compare (a NaN never passes) and that the filter does not drop (filt, filter_row,
+    filter_rel, cand_ids, splits as for pair_mlp_topk).  lkg_pair_mlp_accept_count_f32: nothing of the size of the result
+    is written."""
+    head, n_q, n_c, dev, keep = _pair_mlp_accept_operands("pair_mlp_accept_count", uq, v, w2, b2, w3, b3, thr, filt,
+                                                          filter_row, filter_rel, cand_ids, splits)
+    counts = torch.zeros(n_q, dtype=torch.int32, device=dev)
+    if n_q and n_c:
+        N.call("lkg_pair_mlp_accept_count_f32", *head, N.ptr(counts), _stream())
+    return counts
+
+
+def pair_mlp_accept_append(uq: torch.Tensor, v: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor, w3: torch.Tensor,
+                           b3: torch.Tensor, thr: torch.Tensor, filt=None, filter_row: Optional[torch.Tensor] = None,
+                           filter_rel: Optional[torch.Tensor] = None, cand_ids: Optional[torch.Tensor] = None,
+                           splits: int = 0, capacity: int = 0):
+    """(counts int32[n_q], rows int32[capacity], ids int32[capacity], z f32[capacity], n_written): pair_mlp_accept_count's
+    counts and, from the same pass, the accepted entries (query row, id, logit) in NO particular order, as far as they fit
+    ``capacity`` (lkg_pair_mlp_accept_append_f32: one global cursor; an entry past the capacity is counted, not written).
+    n_written = min(sum(counts), capacity) entries of the three buffers are valid; the buffer overflowed iff
+    sum(counts) > capacity, and the counts are exact either way."""
+    if isinstance(capacity, bool) or not isinstance(capacity, int) or not 0 <= capacity <= 2 ** 31 - 2:
+        raise ValueError(f"pair_mlp_accept_append: capacity must be an integer in [0, 2^31 - 2], got {capacity!r}")
+    head, n_q, n_c, dev, keep = _pair_mlp_accept_operands("pair_mlp_accept_append", uq, v, w2, b2, w3, b3, thr, filt,
+                                                          filter_row, filter_rel, cand_ids, splits)
+    counts = torch.zeros(n_q, dtype=torch.int32, device=dev)
+    rows = torch.empty(capacity, dtype=torch.int32, device=dev)
+    ids = torch.empty(capacity, dtype=torch.int32, device=dev)
+    z = torch.empty(capacity, dtype=torch.float32, device=dev)
+    if n_q == 0 or n_c == 0:
+        return counts, rows, ids, z, 0
+    cursor = torch.zeros(1, dtype=torch.int64, device=dev)
+    N.call("lkg_pair_mlp_accept_append_f32", *head, N.ptr(counts), capacity, N.ptr(cursor), N.ptr(rows), N.ptr(ids),
+           N.ptr(z), _stream())
+    return counts, rows, ids, z, min(int(counts.sum(dtype=torch.int64)), capacity)
+
+
+def pair_mlp_accept_emit(uq: torch.Tensor, v: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor, w3: torch.Tensor,
+                         b3: torch.Tensor, thr: torch.Tensor, filt=None, filter_row: Optional[torch.Tensor] = None,
+                         filter_rel: Optional[torch.Tensor] = None, cand_ids: Optional[torch.Tensor] = None,
+                         splits: int = 0, counts: Optional[torch.Tensor] = None, total: Optional[int] = None):
+    """(rowptr int64[n_q + 1], ids int64[M], s f32[M], z f32[M]): the accepted candidates of pair_mlp_accept_count's
+    arguments, row i in [rowptr[i], rowptr[i + 1]) in NO particular order (accept_order sorts) -- s = -2 z (exact), the
+    ascending key of the order, z the logit.  counts: pair_mlp_accept_count's result for the same arguments; total: its
+    sum if the caller has it.  lkg_pair_mlp_accept_emit_f32 refuses any store outside a row's counted range and raises a
+    flag, which surfaces here as a RuntimeError (accept_check_flag)."""
+    head, n_q, n_c, dev, keep = _pair_mlp_accept_operands("pair_mlp_accept_emit", uq, v, w2, b2, w3, b3, thr, filt,
+                                                          filter_row, filter_rel, cand_ids, splits)
+    if not isinstance(counts, torch.Tensor) or counts.dtype != torch.int32 or counts.dim() != 1 or \
+            counts.numel() != n_q or counts.device != dev:
+        raise ValueError(f"pair_mlp_accept_emit: counts must be an int32 tensor of {n_q} elements on {dev} "
+                         "(pair_mlp_accept_count's result)")
+    counts = counts.contiguous()
+    rowptr = torch.zeros(n_q + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(counts, 0, out=rowptr[1:])
+    m = int(rowptr[-1]) if total is None else int(total)
+    ids = torch.empty(m, dtype=torch.int64, device=dev)
+    s = torch.empty(m, dtype=torch.float32, device=dev)
+    z = torch.empty(m, dtype=torch.float32, device=dev)
+    if m == 0 or n_q == 0 or n_c == 0:
+        return rowptr, ids, s, z
+    cursor = torch.zeros(n_q, dtype=torch.int32, device=dev)
+    flag = torch.zeros(1, dtype=torch.int32, device=dev)
+    N.call("lkg_pair_mlp_accept_emit_f32", *head, N.ptr(counts), N.ptr(rowptr), N.ptr(cursor), N.ptr(ids), N.ptr(s),
+           N.ptr(z), N.ptr(flag), _stream())
+    accept_check_flag(flag)
+    return rowptr, ids, s, z
+
+
 def _u8_labels(what: str, labels: torch.Tensor, n: int) -> torch.Tensor:
     """uint8 / bool labels, one per score, as the contiguous uint8 the kernels read."""
     if labels.dtype == torch.bool:

@@ -1,7 +1,9 @@
 """The MLP pair head at inference: all-pairs logits (``mlp_scores``, the MLP counterpart of ``calc_score``), the backend
 of ``predict_topk(scoring="mlp")``, filtered ranking of held-out pairs under the head (``rank_pairs_mlp``,
 ``evaluate_mlp_ranking``), and the head's downstream task itself: scores of an explicit list of pairs
-(``score_pairs_mlp``) and their binary-classification metrics against labels (``evaluate_mlp_classification``).
+(``score_pairs_mlp``) and their binary-classification metrics against labels (``evaluate_mlp_classification``), and the
+retrieval side of that decision: every pair the head accepts, per query (``predict_accepted_mlp``,
+``count_accepted_mlp``).
 
 The head of mode='mlp' is sigmoid(fc3(bn2(relu(fc2(bn1(relu(fc1([e_h | e_t])))))))).  At inference BatchNorm is affine per
 feature, bn(x) = a x + c with a = gamma / sqrt(running_var + eps), c = beta - running_mean a, and since ReLU comes
@@ -372,3 +374,164 @@ def evaluate_mlp_classification(model, h: torch.Tensor, t: torch.Tensor, labels:
         tp, fp, tn, fn, nan = (int(x) for x in counts.tolist())
         n_pos = int(lab.sum())
     return classification_metrics(tp, fp, tn, fn, nan, n_pos, h.numel() - n_pos, curve)
+
+
+# ----------------------------------------------------------------------------- threshold retrieval under the head
+_ACCEPT_BUFFER = 1 << 22      # entries of the one-pass buffer (12 bytes each): a memory choice, not a measured optimum
+
+
+def _check_cap(name: str, x) -> int:
+    if isinstance(x, bool) or not isinstance(x, int) or x < 0:
+        raise ValueError(f"{name} must be a non-negative integer, got {x!r}")
+    return x
+
+
+def _logit_thresholds(threshold, logit_threshold, b: int):
+    """The per-query logit thresholds as given: a Python float, or the caller's float32[B] tensor."""
+    if logit_threshold is None:
+        return logit_of_probability(threshold)
+    if isinstance(logit_threshold, torch.Tensor):
+        if logit_threshold.dtype != torch.float32 or logit_threshold.dim() != 1 or logit_threshold.numel() != b:
+            raise ValueError(f"a tensor logit_threshold must be a float32 tensor of {b} elements (one per query), got "
+                             f"{logit_threshold.dtype} {tuple(logit_threshold.shape)}")
+        return logit_threshold
+    thr = float(logit_threshold)
+    if thr != thr:
+        raise ValueError("logit_threshold is NaN")
+    return thr
+
+
+def _accept_front(model, ids, r, threshold, logit_threshold, side, known, candidates, batch_size, splits):
+    """The argument checks predict_topk(scoring='mlp') makes, through the same functions in the same order, then the
+    thresholds; everything before any device work.  (side, folded head, thresholds, device)."""
+    side = Q.check_one_side(side, "top-k ranks one side at a time")
+    Q.check_query_lists(ids, r, "mlp")
+    if candidates is not None:
+        Q.check_ids("candidates", candidates)
+    Q.check_batch_size(batch_size)
+    Q.check_splits(splits)
+    Q.check_known_entities(known, model)
+    Q.check_unique(candidates)
+    head = fold_mlp_head(model)                          # (AttributeError without initialize_MLP)
+    dev = model.entity_embed.weight.device
+    Q.check_known_device(known, dev)
+    return side, head, _logit_thresholds(threshold, logit_threshold, ids.numel()), dev
+
+
+def _accept_run(model, head: FoldedMLPHead, ids, r, thr, side, known, cand, batch_size, splits, max_total, buffer):
+    """(counts int64[B], chunks, total) of the checked queries (ids on the device).  With max_total None only the count
+    kernel runs.  Otherwise chunks holds per query batch (ids, logits), every row in order and the rows in query order:
+    from the one-pass buffer where the batch's entries fit it, else from the emit pass into counted segments."""
+    dev, b = ids.device, ids.numel()
+    filt = known.for_side(side) if known is not None else None
+    if isinstance(thr, torch.Tensor):
+        thr_q = thr.to(dev).contiguous()
+    else:
+        thr_q = torch.full((b,), thr, dtype=torch.float32, device=dev)
+    counts = torch.zeros(b, dtype=torch.int64, device=dev)
+    chunks, total = [], 0
+    with torch.no_grad():
+        table = model._table_for_inference().detach()
+        _table_width_ok(head, table)
+        qrows = ops.gather_rows(table, ids)
+        crows = table if cand is None else ops.gather_rows(table, cand)
+        uq, v = _project_sides(head, side, qrows, crows)
+        del qrows, crows
+        frel = Q.filter_relations(r, b, dev)
+        n_c = v.shape[0]
+        for lo, hi in Q.batches(b, batch_size):
+            args = (uq[lo:hi], v, head.w2, head.b2, head.w3, head.b3, thr_q[lo:hi])
+            kw = dict(filt=filt, filter_row=ids[lo:hi], filter_rel=frel[lo:hi], cand_ids=cand, splits=splits)
+            if max_total is None:
+                counts[lo:hi] = ops.pair_mlp_accept_count(*args, **kw)
+                continue
+            cap = min(buffer, (hi - lo) * n_c)           # (no batch has more entries than pairs)
+            if cap > 0:
+                cnt, rows, ii, zz, n_w = ops.pair_mlp_accept_append(*args, **kw, capacity=cap)
+                m = n_w if n_w < cap else int(cnt.sum(dtype=torch.int64))
+            else:
+                cnt = ops.pair_mlp_accept_count(*args, **kw)
+                m = int(cnt.sum(dtype=torch.int64))
+            total += m
+            counts[lo:hi] = cnt
+            if total > max_total:
+                raise ValueError(f"more than max_total={max_total} accepted pairs: {total} so far (raise max_total, "
+                                 "tighten the threshold, or ask count_accepted_mlp for the sizes)")
+            if cap > 0 and m <= cap:                     # one pass: the buffer holds every entry; group them by row
+                order = torch.argsort(rows[:m], stable=True)
+                ii, zz = ii[:m][order].long(), zz[:m][order]
+                rowptr = torch.zeros(hi - lo + 1, dtype=torch.int64, device=dev)
+                torch.cumsum(cnt, 0, out=rowptr[1:])
+                ss = -2.0 * zz                           # (exact) the ascending key, as the select kernel feeds the merge
+            else:                                        # overflow, or no buffer: the second pass into counted segments
+                rowptr, ii, ss, zz = ops.pair_mlp_accept_emit(*args, **kw, counts=cnt, total=m)
+            ii, ss, zz = ops.accept_order(rowptr, ii, ss, zz, model.n_entities)
+            chunks.append((ii, zz))
+    return counts, chunks, total
+
+
+def predict_accepted_mlp(model, ids: torch.Tensor, r: Optional[torch.Tensor] = None, threshold: float = 0.5,
+                         logit_threshold=None, side: str = "tail", known: Optional[KnownTriples] = None,
+                         candidates: Optional[torch.Tensor] = None, batch_size: Optional[int] = None, splits: int = 0,
+                         max_total: int = 1 << 26, buffer: int = _ACCEPT_BUFFER):
+    """Every pair the MLP pair head accepts, per query, in CSR form (accepted.AcceptedResult): the sparse form of the
+    reference's mode='predict' under the head.
+
+    Queries, sides, r, known and candidates are exactly those of predict_topk(scoring='mlp'): side 'tail' scores the
+    pairs (query, c), side 'head' the pairs (c, query); r=None drops a candidate known with the query under ANY relation,
+    r given only one known under that relation; nothing is exempt; candidates are unique entity ids and any order of them
+    gives the same result.
+
+    Candidate c of query i is accepted iff its logit z(i, c) -- the bits mlp_scores(..., logits=True) gives that pair --
+    passes ONE float32 compare, z > thr_i, strictly (the decision of evaluate_mlp_classification), it is not dropped by
+    ``known``, and it is among ``candidates`` when those are given.  A NaN logit is never accepted.  threshold is a
+    probability strictly inside (0, 1), turned into a logit by logit_of_probability (0.5 is the logit 0.0 exactly);
+    logit_threshold overrides it: a Python float, or a float32 tensor of B per-query logit thresholds.  +inf accepts
+    nothing; -inf accepts every candidate whose logit is neither NaN nor -inf.
+
+    Every list is ordered as predict_topk(scoring='mlp') orders: descending logit by float comparison (-0.0 == +0.0),
+    then ascending entity id -- so a query's list is a prefix of its unbounded top-k list.  ``ids`` int64, ``scores``
+    float32 probabilities (the float64 sigmoid of the logit rounded once, the bits of TopKResult.scores),
+    ``kernel_scores`` float32 logits (the bits of TopKResult.kernel_scores); rowptr, counts, side, query_ids, r as in
+    predict_accepted; pairs() gives the (h, t) lists.  The result is a unique object: it does not depend on batch_size,
+    splits, buffer, the order of queries or candidates, the stream or the contents of any scratch; duplicate queries get
+    equal lists.
+
+    max_total caps the number of entries M as in predict_accepted: ValueError once the running total of the counts
+    exceeds it, and the full-size outputs are allocated only after the counts are known.  buffer: the entries of the
+    one-pass buffer (12 bytes each).  A query batch whose accepted entries fit it is scored ONCE (count and append in one
+    kernel, lkg_pair_mlp_accept_append_f32); one that overflows it is scored a second time into counted segments
+    (lkg_pair_mlp_accept_emit_f32); buffer=0 always takes the two passes.  BatchNorm enters in inference form whatever
+    model.training says; the model's mode, parameters, buffers and caches are left as they are."""
+    from .accepted import AcceptedResult, _empty
+    side, head, thr, dev = _accept_front(model, ids, r, threshold, logit_threshold, side, known, candidates, batch_size,
+                                         splits)
+    buffer = min(_check_cap("buffer", buffer), 2 ** 31 - 2)
+    max_total = _check_cap("max_total", max_total)
+    b = ids.numel()
+    if b == 0:
+        return _empty(side, dev, ids, r)
+    (ids,), r, cand = Q.ids_to_device(model, dev, (ids,), r, candidates, unique=True)
+    counts, chunks, total = _accept_run(model, head, ids, r, thr, side, known, cand, batch_size, splits, max_total, buffer)
+    rowptr = torch.zeros(b + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(counts, 0, out=rowptr[1:])
+    if chunks:
+        out_ids, out_z = torch.cat([c[0] for c in chunks]), torch.cat([c[1] for c in chunks])
+    else:
+        out_ids = torch.empty(0, dtype=torch.int64, device=dev)
+        out_z = torch.empty(0, dtype=torch.float32, device=dev)
+    return AcceptedResult(rowptr, out_ids, _sigmoid_(out_z.clone()), out_z, counts, side, ids, r)
+
+
+def count_accepted_mlp(model, ids: torch.Tensor, r: Optional[torch.Tensor] = None, threshold: float = 0.5,
+                       logit_threshold=None, side: str = "tail", known: Optional[KnownTriples] = None,
+                       candidates: Optional[torch.Tensor] = None, batch_size: Optional[int] = None,
+                       splits: int = 0) -> torch.Tensor:
+    """int64[B]: the length of every list predict_accepted_mlp would return, from the count kernel alone
+    (lkg_pair_mlp_accept_count_f32) -- there is no cap and nothing of the size of the lists is allocated."""
+    side, head, thr, dev = _accept_front(model, ids, r, threshold, logit_threshold, side, known, candidates, batch_size,
+                                         splits)
+    if ids.numel() == 0:
+        return torch.zeros(0, dtype=torch.int64, device=dev)
+    (ids,), r, cand = Q.ids_to_device(model, dev, (ids,), r, candidates, unique=True)
+    return _accept_run(model, head, ids, r, thr, side, known, cand, batch_size, splits, None, 0)[0]
