@@ -595,12 +595,12 @@ int lkg_gemm_f32(int32_t trans_a, int32_t trans_b, int64_t m, int64_t n, int64_t
  *                      its values are kept on chip while they pass through the staging registers) with tanh(g) / sigmoid(z)
  *                      optionally kept in gate_g / gate_z for lkg_gate_blend_bwd_f32(activated = 1);
  *   epilogue 0         C = alpha * product + beta * C + bias[n];
- *   epilogue bits 8-15 the tiling, chosen per call: 0 = the library's default, else 1 + {0 "256x2", 1 "128x1", 2 "256x1",
- *                      3 "256x1w", 4 "ws"} (tests and tools run them side by side; nothing in the environment selects code).
- *                      "ws" is the wave-specialised form: one 8-wave workgroup per CU, four loader waves keep the raw A windows
- *                      of up to six k steps in flight through an LDS ring (across tile boundaries) and split them into fp16
- *                      planes, four compute waves of 64 x 128 stream B's planes, run the MFMAs and the epilogue;
- *   workspace          >= lkg_gemm_tall_workspace(n, n_panels, ka, epilogue) bytes (B's fp16 planes: no allocation here). */
+ *   epilogue bits 8-15 the tiling, chosen per call: 0 = the library's default ("256x1"), else 1 + {0 "256x2" (two
+ *                      accumulators, 128 x 256 tiles), 1 "128x1" (one accumulator, 128 x 128 tiles), 2 "256x1" (one
+ *                      accumulator, 128 x 256 tiles)}: tests and tools run them side by side; nothing in the environment
+ *                      or the build selects code.  Any other value (4..6 named tilings that were removed) is an error;
+ *   workspace          >= lkg_gemm_tall_workspace(n, n_panels, ka, epilogue) bytes (B's fp16 planes: no allocation here;
+ *                      -1 for bad sizes or an unknown tiling). */
 int lkg_row_absmax_f32(int64_t n, int32_t d, const float *x, int64_t ldx, float *out, int32_t accumulate,
                        void *stream);
 int64_t lkg_gemm_tall_workspace(int32_t n, int32_t n_panels, const int32_t *ka, int32_t epilogue);

@@ -604,7 +604,7 @@ def tall_ok(m: int, n: int, ks: Sequence[int], single_panel_too: bool = False) -
     return n * sum(ks) <= (1 << 22)
 
 
-TALL_VARIANTS = {"256x2": 0, "128x1": 1, "256x1": 2, "256x1w": 3, "ws": 4, "256r": 5}      # lkg_gemm_tall_f32: bits 8-15 of `epilogue` = id + 1
+TALL_VARIANTS = {"256x2": 0, "128x1": 1, "256x1": 2}      # lkg_gemm_tall_f32: bits 8-15 of `epilogue` = id + 1
 DEFAULT_TALL_VARIANT: Optional[str] = None      # None = the library's default; tests / tools set a key to steer whole modules
 
 
@@ -658,7 +658,9 @@ def gemm_tall(a_panels: Sequence[torch.Tensor], b_blocks: Sequence[Sequence[torc
     b_ptr = (_C.c_void_p * len(flat))(*[b.data_ptr() for b in flat])
     b_ld = (_C.c_int64 * len(flat))(*[_ld(b) for b in flat])
     variant = variant if variant is not None else DEFAULT_TALL_VARIANT
-    epi = (1 if gate else 0) | (0 if variant is None else (TALL_VARIANTS[variant] + 1) << 8)
+    if variant is not None and variant not in TALL_VARIANTS:
+        raise ValueError(f"gemm_tall: unknown tiling {variant!r} (one of {sorted(TALL_VARIANTS)}, or None for the default)")
+    epi =(1 if gate else 0) | (0 if variant is None else (TALL_VARIANTS[variant] + 1) << 8)
     need = N.load().lkg_gemm_tall_workspace(n, np_, a_k, epi)
     ws = _workspace(int(need), out.device)
     gx = _f32_rows(gate_x) if gate else None

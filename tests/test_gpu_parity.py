@@ -329,13 +329,13 @@ def test_gemm_tall_f16x2_engine_is_f32_accurate(ops, gpu_device, ks, n, tb):
     assert err4 <= max(10.0 * f32, 5e-6), (err4, f32)
 
 
-@pytest.mark.parametrize("variant", ["256x2", "256x1", "256x1w", "128x1", "ws", "256r"])
+@pytest.mark.parametrize("variant", ["256x2", "256x1", "128x1"])
 @pytest.mark.parametrize("ks,n,tb", [((256,), 256, True), ((256, 2, 300), 256, True), ((512,), 300, True), ((30, 7), 50, False),
                                      ((40,), 200, True), ((16,), 600, True), ((3, 5, 2), 130, False)])
 def test_gemm_tall_every_tiling_variant_is_f32_accurate(ops, gpu_device, variant, ks, n, tb):
     """Every tiling of lkg_gemm_tall_f32 (bits 8-15 of its `epilogue` argument) against float64 on the same operands: the
-    two-accumulator form, the 8-wave and the 4-wave (64 x 128 wave tiles, prescaled mids) one-accumulator forms and the
-    128-column form -- plain product, alpha / beta / bias into a strided output, rows of very different magnitude."""
+    two-accumulator form, the one-accumulator form and the 128-column form -- plain product, alpha / beta / bias into a
+    strided output, rows of very different magnitude."""
     gen = torch.Generator().manual_seed(sum(ks) * 1000 + n + 7)
     m = 16384 + 131
     panels = [torch.randn(m, k + 1, generator=gen)[:, 1:].to(gpu_device) if i % 2 else torch.randn(m, k, generator=gen).to(gpu_device)
@@ -363,7 +363,7 @@ def test_gemm_tall_every_tiling_variant_is_f32_accurate(ops, gpu_device, variant
     assert float(got3[9].abs().max()) == 0.0
 
 
-@pytest.mark.parametrize("variant", ["256x2", "256x1", "256x1w", "ws", "256r"])
+@pytest.mark.parametrize("variant", ["256x2", "256x1"])
 def test_fused_gate_every_tiling_variant(L, ops, O, gpu_device, variant):
     """The gate's one-launch stacked product (blend epilogue) on every 256-column tiling against the oracle's gate."""
     torch.manual_seed(4)
@@ -382,12 +382,33 @@ def test_fused_gate_every_tiling_variant(L, ops, O, gpu_device, variant):
     torch.testing.assert_close(got.cpu(), want.float(), rtol=1e-4, atol=2e-5)
 
 
+def test_gemm_tall_default_dispatch(ops, gpu_device):
+    """What `variant=None` launches: "256x1" above 128 plain output columns, "128x1" up to 128, "256x1" under the gate
+    epilogue -- the same bits as the tiling named outright, and finite."""
+    gen = torch.Generator().manual_seed(11)
+    m, k = 129, 17
+    a = torch.randn(m, k, generator=gen).to(gpu_device)
+
+    def same(named, **kw):
+        got, want = ops.gemm_tall(variant=None, **kw), ops.gemm_tall(variant=named, **kw)
+        assert bool(torch.isfinite(got).all()) and bool(torch.isfinite(want).all()), named
+        assert torch.equal(got, want), named
+    for n, named in ((130, "256x1"), (128, "128x1")):
+        w = torch.randn(n, k, generator=gen).to(gpu_device)
+        same(named, a_panels=(a,), b_blocks=((w,),), trans_b=True, bias=torch.randn(n, generator=gen).to(gpu_device))
+    d, lits = 32, (2, 5)
+    panels = [torch.randn(m, w_, generator=gen).to(gpu_device) for w_ in (d,) + lits]
+    groups = [[(torch.randn(d, w_, generator=gen) * 0.3).to(gpu_device) for w_ in (d,) + lits] for _ in range(2)]
+    same("256x1", a_panels=panels, b_blocks=groups, trans_b=True, bias=torch.randn(2 * d, generator=gen).to(gpu_device),
+         gate_x=panels[0])
+
+
 @pytest.mark.parametrize("m", [16384 + 5, 40_000])
 @pytest.mark.parametrize("ks,n", [((256,), 256), ((64, 64), 128), ((300,), 32), ((256, 300), 200), ((40,), 7), ((128,), 256), ((32,), 32)])
 @pytest.mark.parametrize("drop_p", [0.0, 0.25])
 def test_fused_layer_epilogue_matches_the_unfused_pair(ops, gpu_device, m, ks, n, drop_p):
     """K5 in one launch (lkg_linear_act_layernorm_fwd_f32: Linear + LeakyReLU + LayerNorm + dropout + normalised copy in the
-    wave-specialised tall GEMM's epilogue) against the unfused pair lkg_gemm_tall_f32 + lkg_act_layernorm_fwd_f32 on the
+    tall GEMM's epilogue) against the unfused pair lkg_gemm_tall_f32 + lkg_act_layernorm_fwd_f32 on the
     same operands and the same dropout seed: y, yn, mean, rstd -- and against float64 LayerNorm of the float64 product."""
     gen = torch.Generator().manual_seed(m + n + sum(ks))
     panels = [torch.randn(m, k, generator=gen).to(gpu_device) * (0.5 + i) for i, k in enumerate(ks)]

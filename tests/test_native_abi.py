@@ -46,6 +46,25 @@ def test_error_convention(native):
         native.call("lkg_spmm_csr_f32", 4, 0, None, None, None, None, 0, None, 0, None, 0, None, 0, 0, None)
 
 
+def test_tall_gemm_refuses_unknown_tilings(native):
+    """Bits 8-15 of lkg_gemm_tall_f32's `epilogue`: 0 (default) and 1..3 name a tiling, anything else is an error that
+    names the value (4..6 were tilings once: retired, not renumbered).  m = 0: no HIP call is made."""
+    import ctypes
+    lib = native.load()
+    ka = (ctypes.c_int32 * 1)(16)
+
+    def call(bits):
+        return native.call("lkg_gemm_tall_f32", 0, 8, 1, None, None, ka, None, 1, None, None, 1, 1.0, 0.0, None, 8, None,
+                           bits << 8, None, 0, None, 0, None, 0, None, 0, None)
+    for bits in (0, 1, 2, 3):
+        call(bits)                                          # LKG_OK (native.call raises on anything else)
+        assert lib.lkg_gemm_tall_workspace(200, 1, ka, bits << 8) > 0
+    for bits in (4, 5, 6, 7):
+        with pytest.raises(native.LkgError, match=rf"unknown variant {bits}\b"):
+            call(bits)
+        assert lib.lkg_gemm_tall_workspace(200, 1, ka, bits << 8) == -1
+
+
 def numpy_csr(n, h, t, r):
     """Restatement of coalesce()'s index work (model.py:468-470): sort by (h,t), merge equal pairs."""
     order = np.lexsort((np.arange(len(h)), t, h))

@@ -378,7 +378,7 @@ def bodies(L, gpu_device):
         "wgrad f16x2": scaled(TC.test_wgrad_f16x2_scale_sweep, 16 * 2500),
         "wgrad f16x2 k + 5": scaled(TC.test_wgrad_f16x2_scale_sweep, 16 * 2500 + 5),
         **{f"ordered {i}": ordered(lay) for i, lay in zip(TGO.LAYOUT_IDS, TGO.LAYOUTS)},
-        **{f"tall {v}": scaled(TC.test_tall_scale_sweep, v) for v in (None, "256x2", "128x1", "256x1", "256x1w")},
+        **{f"tall {v}": scaled(TC.test_tall_scale_sweep, v) for v in (None, "256x2", "128x1", "256x1")},
         "tall gate epilogue": scaled(TC.test_tall_gate_epilogue_scale_sweep, None),
         "fused linear layernorm edges": lambda: TC.test_fused_linear_act_layernorm_at_the_range_edges(ops, g),
         "fused layer epilogue": lambda: TG.test_fused_layer_epilogue_matches_the_unfused_pair(ops, g, 16384 + 5, (32,), 32, 0.0),
@@ -418,7 +418,7 @@ BODIES = (
     ["grouped rows", "grouped rows trans_b", "grouped k", "gemm layouts k 33", "gemm layouts k 8003"] +
     [f"engine {c}" for c in ("bf16x3_rows", "bf16x3_kmajor", "longk", "f32_mfma", "skinny", "smallm")] +
     ["gemm f64acc", "wgrad f16x2", "wgrad f16x2 k + 5"] + [f"ordered {i}" for i in ("NN", "NT", "TN", "TT")] +
-    [f"tall {v}" for v in (None, "256x2", "128x1", "256x1", "256x1w")] +
+    [f"tall {v}" for v in (None, "256x2", "128x1", "256x1")] +
     ["tall gate epilogue", "fused linear layernorm edges", "fused layer epilogue", "fused layer two panels",
      "narrow layer backward"] +
     [f"kvs_all {b} x {n} x {k}" for b, n, k in ((65, 257, 17), (130, 255, 32))] +

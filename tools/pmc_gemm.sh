@@ -1,5 +1,5 @@
 #!/bin/bash
-# PMC attribution of one kernel (default: the tall GEMM through tools/gemm_tall_debug.py): several small counter groups,
+# PMC attribution of one kernel (e.g. the tall GEMM through tools/gemm_tall_micro.py): several small counter groups,
 # one rocprofv3 pass each, summarised per kernel name.  usage: tools/pmc_gemm.sh <outdir> <kernel substring> <python script>
 out=$1; kern=$2; script=$3
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"

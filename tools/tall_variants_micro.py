@@ -24,7 +24,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--rounds", type=int, default=7)
 ap.add_argument("--reps", type=int, default=6)
 ap.add_argument("--n", type=int, default=1_000_000)
-ap.add_argument("--variants", default="256x1,256x1w,ws")
+ap.add_argument("--variants", default="256x1,256x2,128x1")
 ap.add_argument("--json", default=None)
 args = ap.parse_args()
 dev = torch.device("cuda:0")
