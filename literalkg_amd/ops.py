@@ -376,8 +376,21 @@ import ctypes as _C
 import os as _os
 
 TALL_MIN_ROWS = 16384          # below this a product is bound by its launch overhead: the f32-MFMA engine serves it
-_ENGINE = _os.environ.get("LKG_GEMM_ENGINE", "f16x2")      # f16x2 | bf16x3 (round-1 split engines) | f32 via lkg_gemm_f32
-_WGRAD_ENGINE = _os.environ.get("LKG_WGRAD_ENGINE", "longk")  # longk (lkg_gemm_longk_f32) | bf16x3 (lkg_gemm_f32's long-k engine)
+GEMM_ENGINES = ("f16x2", "f16x2-all", "bf16x3", "f32")
+WGRAD_ENGINES = ("longk", "bf16x3")
+
+
+def _engine_from_env(var: str, default: str, accepted: Sequence[str]) -> str:
+    """The engine named by ``var`` (surrounding whitespace stripped).  A name that is none of ``accepted`` is refused here,
+    at import: every dispatch below compares against the names it knows, so a typo would silently select other arithmetic."""
+    v = _os.environ.get(var, default).strip()
+    if v not in accepted:
+        raise ValueError(f"{var}={v!r}: unknown engine (one of {', '.join(accepted)})")
+    return v
+
+
+_ENGINE = _engine_from_env("LKG_GEMM_ENGINE", "f16x2", GEMM_ENGINES)    # f16x2 | f16x2-all | bf16x3 (round-1 split engines) | f32 via lkg_gemm_f32
+_WGRAD_ENGINE = _engine_from_env("LKG_WGRAD_ENGINE", "longk", WGRAD_ENGINES)  # longk (lkg_gemm_longk_f32) | bf16x3 (lkg_gemm_f32's long-k engine)
 _workspaces = {}
 
 

@@ -300,11 +300,16 @@ def same_bits_fault(a, b, what):
     return None
 
 
-def run_matrix(entry, ops, inp, measures=None):
+def run_matrix(entry, ops, inp, measures=None, expect=None):
     """Every input subset x output subset of one Function variant, judged by structure, launch record, bits and float64
     (module docstring of test_autograd_surface_gpu.py).  Returns the list of faults, each named by its subsets.
-    measures: {entry name: [all-trainable, worst partial, torch float32]} is updated with the largest figures seen."""
+    measures: {entry name: [all-trainable, worst partial, torch float32]} is updated with the largest figures seen.
+    expect: (inp, subset, outs) -> launch expectations that REPLACE the entry's own -- those of another setting of the engine
+    switches (test_engine_switches_gpu.py); the bit comparison against the all-trainable run, which rests on the default
+    launches (same_launches), is then left out.  None: the entry's own, and every judge."""
     faults = []
+    default_launches = expect is None
+    expect = entry.expect if expect is None else expect
     allset = frozenset(inp.slots)
     dropout = inp.cfg.get("drop_p", 0.0) > 0
     det = entry.deterministic(inp)
@@ -325,7 +330,7 @@ def run_matrix(entry, ops, inp, measures=None):
         for k in also:              # by design no gradient, even when it requires one
             if base.leaves.t[k].requires_grad and base.leaves.t[k].grad is not None:
                 faults.append(f"{tag}: {k} never gets a gradient ({entry.by_design_none[k]}), yet it has one")
-        first = compare(inp, allset, base.grads, want64, entry.bound, judge) + check_expect(entry.expect(inp, allset, outs), base)
+        first = compare(inp, allset, base.grads, want64, entry.bound, judge) + check_expect(expect(inp, allset, outs), base)
         if first:                   # the all-trainable run first: a partial-gradient failure is then not one of the measure
             faults += [f"{tag}, all trainable: {f}" for f in first]
             continue
@@ -335,14 +340,14 @@ def run_matrix(entry, ops, inp, measures=None):
             if subset == allset:
                 continue
             run = applied(entry, ops, inp, subset, outs)
-            here = compare(inp, subset, run.grads, want64, entry.bound, judge) + check_expect(entry.expect(inp, subset, outs), run)
+            here = compare(inp, subset, run.grads, want64, entry.bound, judge) + check_expect(expect(inp, subset, outs), run)
             for s in sorted(subset):
                 g, b = run.grads[s], base.grads[s]
                 if g is None or b is None:
                     continue
                 if want64 is not None and want64[s] is not None:
                     m[1] = max(m[1], norm_measure(g, want64[s]))
-                if s in det and entry.same_launches(inp, subset):
+                if default_launches and s in det and entry.same_launches(inp, subset):
                     bad = same_bits_fault(g, b, f"{s} against the all-trainable run")
                     if bad:
                         here.append(bad)
@@ -748,11 +753,18 @@ Entry("_GateBlend", {"x": "diff", "gpre": "diff", "zpre": "diff", "out": "none"}
       deterministic=lambda inp: set(inp.slots), expect=lambda inp, subset, outs: {("bwd", "lkg_gate_blend_bwd_f32"): 1})
 
 FG = {"16387xd32 lits (2,12)": (2, 12), "16387xd32 lit (5)": (5,), "16387xd32 lits (2,12) tagged": (2, 12),
-      "16387xd32 lit (5) tagged": (5,)}
+      "16387xd32 lit (5) tagged": (5,),
+      # the dense backward WITHOUT the blend kernel's statistics (ops.py, _FusedGate.backward): a width that is no multiple of
+      # 4, and two literal panels of <= 4 columns that both want a weight gradient
+      "16387xd30 lits (2,12)": (2, 12), "16387xd32 lits (2,3)": (2, 3)}
+
+
+def fg_width(variant):
+    return int(variant.split("xd")[1].split()[0])
 
 
 def _fg_build(device, variant, small=False, seed=0):
-    n, d, ks = _rows(N_BIG, small), 32, FG[variant]
+    n, d, ks = _rows(N_BIG, small), fg_width(variant), FG[variant]
     gen = _gen(1000 + seed + len(variant))
     t = {"x": _rn(gen, n, d, std=0.5)}
     for i, k in enumerate(ks):
@@ -795,6 +807,14 @@ def fg_model_subset(inp):
     return frozenset(inp.slots) - set(fg_lits(inp))
 
 
+def fg_no_stats(inp, subset):
+    """Does the dense backward of this subset run without the blend kernel's statistics?  (ops.py, _FusedGate.backward: they
+    need a width that is a multiple of 4 and carry the weight gradient of at most ONE literal panel of <= 4 columns)"""
+    nl = inp.cfg["n_lit"]
+    narrow = [i for i in range(nl) if (f"wg{i + 1}" in subset or f"wz{i + 1}" in subset) and inp.t[f"lit{i}"].shape[1] <= 4]
+    return "tagged" not in inp.variant and (inp.t["x"].shape[1] % 4 != 0 or len(narrow) > 1)
+
+
 def _fg_expect(inp, subset, outs):
     nl = inp.cfg["n_lit"]
     want = [f"wg{i}" in subset or f"wz{i}" in subset for i in range(nl + 1)]       # a panel's [2d x k] product: either half wanted
@@ -805,9 +825,20 @@ def _fg_expect(inp, subset, outs):
                 ("bwd", "lkg_colsum_f32"): int("bg" in subset or "bz" in subset),
                 ("bwd", "products"): 2 * int("x" in subset) + sum(want) + n_lits,
                 ("bwd", "lkg_scatter_add_rows_range_f32"): int("x" in subset) + n_lits}
+    widths = [inp.t["x"].shape[1]] + [inp.t[f"lit{i}"].shape[1] for i in range(nl)]
+    if fg_no_stats(inp, subset):
+        # the blend kernel without its statistics, the data gradient still ONE tall product; the bias sums and the weight
+        # gradients are ops.weight_grads': every wanted panel of <= 8 columns one lkg_colsum_weighted_f32 (the first carries the
+        # bias sums; lkg_colsum_f32 when there is none), every wider one a product through ops.gemm
+        want_bias = "bg" in subset or "bz" in subset
+        n_narrow = sum(1 for i in range(nl + 1) if want[i] and widths[i] <= 8)
+        return {("bwd", "lkg_gate_blend_bwd_f32"): 1, ("bwd", "lkg_gate_blend_bwd_stats_f32"): False,
+                ("bwd", "lkg_gemm_wgrad_f32"): False, ("bwd", "lkg_gemm_tall_f32"): int("x" in subset),
+                ("bwd", "lkg_colsum_weighted_f32"): n_narrow, ("bwd", "lkg_colsum_f32"): int(want_bias and n_narrow == 0),
+                ("bwd", "products"): int("x" in subset) + sum(1 for i in range(nl + 1) if want[i] and widths[i] > 8) + n_lits}
     # the statistics of the blend kernel carry the bias sums and the weight gradient of the one literal panel of <= 4 columns:
     # neither a column sum nor a product is launched for them; every other wanted panel is one fp16 weight-gradient product
-    wide = [i for i in range(nl + 1) if i == 0 or inp.t[f"lit{i - 1}"].shape[1] > 4]
+    wide =[i for i in range(nl + 1) if i == 0 or inp.t[f"lit{i - 1}"].shape[1] > 4]
     n_wgrad = sum(1 for i in wide if want[i])
     e = {("bwd", "lkg_gate_blend_bwd_stats_f32"): 1, ("bwd", "lkg_gate_blend_bwd_f32"): False,
          ("bwd", "lkg_gemm_tall_f32"): int("x" in subset), ("bwd", "lkg_gemm_wgrad_f32"): n_wgrad,
