@@ -195,7 +195,11 @@ def _ln(p: Params, name: str, x: torch.Tensor) -> torch.Tensor:
 # --------------------------------------------------------------------------
 def aggregator_layer(p: Params, lp: str, cfg, ego: torch.Tensor, a_in: torch.Tensor,
                      earlier: List[torch.Tensor], layer_no: int,
-                     dropout_p: float = 0.0, training: bool = False) -> torch.Tensor:
+                     dropout_p: float = 0.0, training: bool = False,
+                     dropout_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """dropout_scale: an explicit scale per element of the layer's output (0 where dropped, 1 / (1 - p) where kept; 1
+    on rows nobody reads).  When given it REPLACES F.dropout: the step is then a function of its inputs alone, and a
+    training-mode step of the device path, whose masks are stated exactly, has a float64 reference."""
     kind = cfg.aggregation_type
     res = bool(cfg.use_residual)
     side = aggregate(a_in, ego)
@@ -229,6 +233,8 @@ def aggregator_layer(p: Params, lp: str, cfg, ego: torch.Tensor, a_in: torch.Ten
     else:
         raise NotImplementedError(kind)
     out = _ln(p, lp + "layer_normalize", out)
+    if dropout_scale is not None:
+        return out * dropout_scale.to(out.dtype)
     return F.dropout(out, dropout_p, training)
 
 
@@ -236,12 +242,14 @@ def aggregator_layer(p: Params, lp: str, cfg, ego: torch.Tensor, a_in: torch.Ten
 # a7  encoder driver                                       model.py:298-314
 # --------------------------------------------------------------------------
 def gat_embeddings(p: Params, cfg, a_in: torch.Tensor, num: Optional[torch.Tensor] = None,
-                   txt: Optional[torch.Tensor] = None, training: bool = False) -> torch.Tensor:
+                   txt: Optional[torch.Tensor] = None, training: bool = False,
+                   dropout_scales: Optional[Sequence[torch.Tensor]] = None) -> torch.Tensor:
+    """dropout_scales: one explicit scale tensor per layer (aggregator_layer's dropout_scale), instead of F.dropout."""
     cur = gate_embeddings(p, cfg, num, txt)
     kept = [cur]
     for k in range(cfg.n_conv_layers):
         cur = aggregator_layer(p, f"aggregator_layers.{k}.", cfg, cur, a_in, kept, k + 1,
-                               cfg.mess_dropout, training)
+                               cfg.mess_dropout, training, None if dropout_scales is None else dropout_scales[k])
         kept.append(F.normalize(cur, p=2.0, dim=1, eps=NORMALIZE_EPS))
     cat = torch.cat(kept, dim=1)
     if cfg.scale_gat_dim is not None:

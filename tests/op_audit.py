@@ -142,24 +142,29 @@ def grouped_scale(mode, seg, a, b, c0, beta, trans_b, b_period):
 
 
 # ---- LeakyReLU + LayerNorm + normalised copy (lkg_act_layernorm_*), BatchNorm(ReLU) (lkg_relu_batchnorm_*)
-def layernorm_fwd_eval(z, gamma, beta, slope, eps, norm_eps, dtype, mean_over=None):
-    """{mean, rstd, y, yn}.  mean_over: a planted fault for the host test (the row mean taken over that many elements)."""
+def layernorm_fwd_eval(z, gamma, beta, slope, eps, norm_eps, dtype, mean_over=None, drop=None):
+    """{mean, rstd, y, yn}.  mean_over: a planted fault for the host test (the row mean taken over that many elements).
+    drop: the dropout scale per element (0 or 1 / (1 - p), as float32 holds it), applied to y before the normalised copy."""
     a = leaky(z.to(dtype), slope)
     d = a.shape[1]
     mean = a.sum(1) / (mean_over or d)
     c = a - mean[:, None]
     rstd = 1.0 / torch.sqrt((c * c).sum(1) / d + eps)
     y = c * rstd[:, None] * gamma.to(dtype) + beta.to(dtype)
+    if drop is not None:
+        y = y * drop.to(dtype)
     nrm = torch.sqrt((y * y).sum(1))
     yn = y / nrm.clamp_min(norm_eps)[:, None]
     return dict(mean=mean, rstd=rstd, y=y, yn=yn)
 
 
-def layernorm_fwd_scale(z, gamma, beta, slope, eps, norm_eps):
-    w = layernorm_fwd_eval(z, gamma, beta, slope, eps, norm_eps, torch.float64)
+def layernorm_fwd_scale(z, gamma, beta, slope, eps, norm_eps, drop=None):
+    w = layernorm_fwd_eval(z, gamma, beta, slope, eps, norm_eps, torch.float64, drop=drop)
     a = leaky(z.double(), slope).abs()
     ma = a.mean(1)
     sy = (a + ma[:, None]) * w["rstd"][:, None] * gamma.double().abs() + beta.double().abs()
+    if drop is not None:
+        sy = sy * drop.double()
     nrm = torch.sqrt((w["y"] * w["y"]).sum(1)).clamp_min(norm_eps)
     return dict(mean=ma, rstd=w["rstd"], y=sy, yn=sy / nrm[:, None])
 
@@ -180,21 +185,26 @@ def _ln_upstream(y, gy, gyn, norm_eps, dtype):
     return g, ag
 
 
-def layernorm_bwd_eval(z, gamma, mean, rstd, y, gy, gyn, slope, norm_eps, dtype):
-    """{gz, g_gamma, g_beta} from the backward kernel's own float32 inputs (z, gamma, the saved mean / rstd / y, g_y, g_yn)"""
+def layernorm_bwd_eval(z, gamma, mean, rstd, y, gy, gyn, slope, norm_eps, dtype, drop=None):
+    """{gz, g_gamma, g_beta} from the backward kernel's own float32 inputs (z, gamma, the saved mean / rstd / y, g_y, g_yn).
+    drop: the dropout scale per element; y, g_y and g_yn then refer to the MASKED output, and G goes through the mask."""
     zz = z.to(dtype)
     xh = (leaky(zz, slope) - mean.to(dtype)[:, None]) * rstd.to(dtype)[:, None]
     g, _ = _ln_upstream(y, gy, gyn, norm_eps, dtype)
+    if drop is not None:
+        g = g * drop.to(dtype)
     dxh = g * gamma.to(dtype)
     da = rstd.to(dtype)[:, None] * (dxh - dxh.mean(1, keepdim=True) - xh * (dxh * xh).mean(1, keepdim=True))
     gz = da * torch.where(zz > 0, torch.ones_like(zz), torch.full_like(zz, slope))
     return dict(gz=gz, g_gamma=(g * xh).sum(0), g_beta=g.sum(0))
 
 
-def layernorm_bwd_scale(z, gamma, mean, rstd, y, gy, gyn, slope, norm_eps):
+def layernorm_bwd_scale(z, gamma, mean, rstd, y, gy, gyn, slope, norm_eps, drop=None):
     zz = z.double()
     xh = ((leaky(zz, slope) - mean.double()[:, None]) * rstd.double()[:, None]).abs()
     _, ag = _ln_upstream(y, gy, gyn, norm_eps, torch.float64)
+    if drop is not None:
+        ag = ag * drop.double()
     adx = ag * gamma.double().abs()
     gz = rstd.double()[:, None] * (adx + adx.mean(1, keepdim=True) + xh * (adx * xh).mean(1, keepdim=True))
     gz = gz * torch.where(zz > 0, torch.ones_like(zz), torch.full_like(zz, slope))

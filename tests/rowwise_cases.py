@@ -283,13 +283,20 @@ def ln_row_groups(case):
 
 
 def layernorm_fwd_f32(case, mean_over=None):
-    return A.layernorm_fwd_eval(case.z, case.gamma, case.beta, case.slope, case.eps, case.norm_eps, torch.float32, mean_over)
+    return A.layernorm_fwd_eval(case.z, case.gamma, case.beta, case.slope, case.eps, case.norm_eps, torch.float32, mean_over,
+                                drop=drop_of(case))
+
+
+def drop_of(case):
+    """the dropout scale per element of a case that has one (test_dropout_mask_gpu.py sets it from the host port), else None"""
+    return getattr(case, "drop", None)
 
 
 def check_layernorm_fwd(lines, case, got):
     """got: {mean, rstd, y, yn} (yn / y may be absent)"""
     args = (case.z, case.gamma, case.beta, case.slope, case.eps, case.norm_eps)
-    want, scale, ref32 = A.layernorm_fwd_eval(*args, torch.float64), A.layernorm_fwd_scale(*args), layernorm_fwd_f32(case)
+    want, scale = A.layernorm_fwd_eval(*args, torch.float64, drop=drop_of(case)), A.layernorm_fwd_scale(*args, drop=drop_of(case))
+    ref32 = layernorm_fwd_f32(case)
     for k in ("mean", "rstd", "y", "yn"):
         if got.get(k) is not None:
             for tag, rows in ln_row_groups(case):
@@ -305,15 +312,15 @@ def check_layernorm_fwd(lines, case, got):
 
 def layernorm_bwd_f32(case, mean, rstd, y, use_gy=True, use_gyn=True):
     return A.layernorm_bwd_eval(case.z, case.gamma, mean, rstd, y, case.gy if use_gy else None, case.gyn if use_gyn else None,
-                                case.slope, case.norm_eps, torch.float32)
+                                case.slope, case.norm_eps, torch.float32, drop=drop_of(case))
 
 
 def check_layernorm_bwd(lines, case, mean, rstd, y, got, use_gy=True, use_gyn=True, only=("gz", "g_gamma", "g_beta")):
     """got: {gz, g_gamma, g_beta}; mean / rstd / y: what the forward kept (the backward kernel's inputs)"""
     args = (case.z, case.gamma, mean, rstd, y, case.gy if use_gy else None, case.gyn if use_gyn else None, case.slope,
             case.norm_eps)
-    want, scale = A.layernorm_bwd_eval(*args, torch.float64), A.layernorm_bwd_scale(*args)
-    ref32 = A.layernorm_bwd_eval(*args, torch.float32)
+    want, scale = A.layernorm_bwd_eval(*args, torch.float64, drop=drop_of(case)), A.layernorm_bwd_scale(*args, drop=drop_of(case))
+    ref32 = A.layernorm_bwd_eval(*args, torch.float32, drop=drop_of(case))
     for k in only:
         for tag, rows in (ln_row_groups(case) if k == "gz" else [("", slice(None))]):
             check_reduction(lines, f"{case.what} {k}{tag}", got[k][rows], want[k][rows], scale[k][rows], ref32[k][rows])

@@ -385,7 +385,8 @@ def run_case(L, O, gpu_device, c, seed, value_seed):
                     in_f32_device(mlp_loss, params_mlp), grad_tol)
 
     # ---- training mode with message dropout: the row-sparse backward machinery against the dense backward of the same model
-    # (no oracle: the masks come from this package's generator; from 16 384 rows on the machinery is active)
+    # (from 16 384 rows on the machinery is active.  The oracle is not asked here: test_dropout_model_gpu.py holds a training-mode
+    # step to the float64 oracle under the very masks the kernels draw, rebuilt by the host port of dropout_cases.py)
     if n >= 16384 and not c["prune"]:
         from literalkg_amd import ops as _ops
         for layer in m.aggregator_layers:
