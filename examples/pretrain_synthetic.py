@@ -24,7 +24,7 @@ from literalkg_amd import LiteralKG                      # noqa: E402  (the one-
 from literalkg_amd import KnownTriples, distinct_queries   # noqa: E402  (--filtered, --objective kvs_all)
 from literalkg_amd import product_route                  # noqa: E402  (--ordered-products)
 from literalkg_amd import group_sampled_batch            # noqa: E402  (--objective self_adversarial)
-from literalkg_amd import NegativeSampler, TripleEpoch, subsampling_weights   # noqa: E402  (--sampler triples)
+from literalkg_amd import NegativeSampler, TripleEpoch, subsampling_weights   # noqa: E402  (--sampler triples, --eval-sampled)
 from literalkg_amd.synth import make_batch, make_kg      # noqa: E402
 
 
@@ -90,6 +90,9 @@ def main():
                     help="with --prune-to-batch: a row aggregates at most this many of its stored neighbours per training "
                          "step, drawn anew every step (model.neighbor_fanout)")
     ap.add_argument("--neighbor-seed", type=int, default=0, help="with --fanout: the seed of the neighbour draws")
+    ap.add_argument("--eval-sampled", type=int, default=0, metavar="K",
+                    help="after training, rank a held-out slice of the triples against K filtered negatives per side, "
+                         "drawn under a fixed seed (evaluate_list_ranking: the protocol of ogbl-wikikg2 / ogbl-biokg)")
     a = ap.parse_args()
     if a.fanout is not None and not a.prune_to_batch:
         ap.error("--fanout goes with --prune-to-batch")
@@ -163,6 +166,14 @@ def main():
         torch.cuda.synchronize()
         print(f"epoch {epoch}: mean loss {total / a.iters:.4f} | {a.iters} iters {t1 - t0:.2f} s "
               f"({(t1 - t0) / a.iters * 1e3:.1f} ms/iter) | update_att {time.time() - t1:.3f} s")
+    if a.eval_sampled > 0:
+        every = known if known is not None else KnownTriples(h_list, r_list, t_list, a.entities, 16)
+        eh, er, et = (x[-min(10_000, x.numel()):] for x in (h_list, r_list, t_list))      # the held-out slice
+        neg_t = NegativeSampler(a.entities, every, corrupt="tail").sample(eh, er, et, a.eval_sampled, seed=2022)
+        neg_h = NegativeSampler(a.entities, every, corrupt="head").sample(eh, er, et, a.eval_sampled, seed=2022)
+        m = model.evaluate_list_ranking(eh, er, et, tail_lists=neg_t.neg, head_lists=neg_h.neg, known=every)
+        print(f"sampled ranking, {eh.numel()} triples x {a.eval_sampled} filtered negatives per side: " +
+              " | ".join(f"{k_} {v:.4f}" for k_, v in m.items() if isinstance(v, float)))
     path = "/tmp/pre-training_model_epoch%d.pth" % a.epochs
     torch.save({"model_state_dict": model.state_dict(), "epoch": a.epochs}, path)
     back = LiteralKG(args, a.entities, 16)

@@ -29,6 +29,7 @@ from .relation_loss import relation_loss, relation_softmax_loss   # noqa: F401  
 from .gemm_ordered import (current_route, gemm_ordered, gemm_ordered_splits, matmul_ordered,   # noqa: F401  (gemm_ordered: the
                            product_route)                                                      # FUNCTION here, as above)
 from .pruned import sample_neighbors   # noqa: F401
+from .lists import ListRanks, evaluate_list_ranking, rank_in_lists, score_lists   # noqa: F401
 
 __all__ = ["LiteralKG", "Aggregator", "Gate", "GateMul", "KGStructure", "KnownTriples", "RankResult", "evaluate_ranking",
            "TopKResult", "predict_topk", "FoldedMLPHead", "fold_mlp_head", "mlp_scores", "rank_pairs_mlp",
@@ -40,4 +41,5 @@ __all__ = ["LiteralKG", "Aggregator", "Gate", "GateMul", "KGStructure", "KnownTr
            "NegativeSampler", "NegativeBatch", "TripleEpoch", "RelationCardinalities", "relation_cardinalities",
            "answer_counts", "subsampling_weights", "sampled_negative_loss", "relation_loss", "relation_softmax_loss",
            "gemm_ordered", "gemm_ordered_splits", "matmul_ordered", "product_route", "current_route",
-           "sample_neighbors", "predict_accepted_mlp", "count_accepted_mlp"]
+           "sample_neighbors", "predict_accepted_mlp", "count_accepted_mlp", "ListRanks", "score_lists", "rank_in_lists",
+           "evaluate_list_ranking"]

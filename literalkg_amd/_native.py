@@ -176,6 +176,11 @@ PAIR_ACCEPT_PROTOTYPES = {
     "lkg_pair_mlp_accept_append_f32": _PAIR_ACCEPT_HEAD + [i64, vp, vp, vp, vp, vp],
     "lkg_pair_mlp_accept_emit_f32": _PAIR_ACCEPT_HEAD + [vp, vp, vp, vp, vp, vp, vp],
 }
+# the ninth table: include/literalkg_hip_lists.h (scores and ranks against per-query candidate lists), mirrored the same way
+LIST_PROTOTYPES = {
+    "lkg_list_scores_f32": [i64, i64, i64, i32, vp, i64, vp, vp, i64, vp, vp, i64, i32, vp, i64, vp],
+    "lkg_list_count_f32": [i64, i64, i64, i32, vp, i64, vp, i64, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+}
 _RESTYPE = {"lkg_last_error": C.c_char_p, "lkg_csr_build_device_workspace": C.c_int64,
             "lkg_gemm_tall_workspace": C.c_int64, "lkg_gemm_workspace": C.c_int64,
             "lkg_linear_act_layernorm_workspace": C.c_int64, "lkg_narrow_layer_bwd_workspace": C.c_int64,
@@ -207,7 +212,7 @@ def load():
     for name, argtypes in list(PROTOTYPES.items()) + list(EXTRA_PROTOTYPES.items()) + list(TRAIN_PROTOTYPES.items()) + \
             list(SAMPLE_PROTOTYPES.items()) + list(RELATION_TRAIN_PROTOTYPES.items()) + \
             list(ORDERED_GEMM_PROTOTYPES.items()) + list(NEIGHBOR_PROTOTYPES.items()) + \
-            list(PAIR_ACCEPT_PROTOTYPES.items()):
+            list(PAIR_ACCEPT_PROTOTYPES.items()) + list(LIST_PROTOTYPES.items()):
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
         fn.argtypes = argtypes
         fn.restype = _RESTYPE.get(name, C.c_int)

@@ -17,7 +17,7 @@ SOURCES = ["lkg_graph_host.cpp", "lkg_spmm.hip", "lkg_attention.hip", "lkg_score
            "lkg_gemm.hip", "lkg_batch.hip", "lkg_csr_device.hip", "lkg_gemm_tall.hip", "lkg_gemm_wgrad.hip", "lkg_layer.hip",
            "lkg_rank.hip", "lkg_topk.hip", "lkg_pairmlp.hip", "lkg_triples.hip", "lkg_relations.hip",
            "lkg_accept.hip", "lkg_retrieval.hip", "lkg_softmax.hip", "lkg_kvsall.hip", "lkg_nssa.hip", "lkg_negatives.hip",
-           "lkg_relation_loss.hip", "lkg_gemm_ordered.hip", "lkg_neighbors.hip"]
+           "lkg_relation_loss.hip", "lkg_gemm_ordered.hip", "lkg_neighbors.hip", "lkg_lists.hip"]
 FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17"]
 
 
@@ -26,7 +26,7 @@ def _headers():
            [os.path.join(HERE, "..", "include", h) for h in ("literalkg_hip.h", "literalkg_hip_ext.h", "literalkg_hip_train.h",
                                                                 "literalkg_hip_sample.h", "literalkg_hip_relation_train.h",
                                                                 "literalkg_hip_gemm_ordered.h", "literalkg_hip_neighbors.h",
-                                                                "literalkg_hip_pair_accept.h")]
+                                                                "literalkg_hip_pair_accept.h", "literalkg_hip_lists.h")]
 
 
 TAG_FILE = os.path.join(HERE, "lib", "flags.tag")

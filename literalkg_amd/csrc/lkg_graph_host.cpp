@@ -58,9 +58,10 @@ int lkg_internal_preload_negatives();
 int lkg_internal_preload_relation_loss();
 int lkg_internal_preload_gemm_ordered();
 int lkg_internal_preload_neighbors();
+int lkg_internal_preload_lists();
 
 extern "C" int lkg_preload(void) {
-    const int failed = lkg_internal_preload_spmm() + lkg_internal_preload_attention() + lkg_internal_preload_batch() + lkg_internal_preload_csr_device() + lkg_internal_preload_gemm() + lkg_internal_preload_gemm_tall() + lkg_internal_preload_gemm_wgrad() + lkg_internal_preload_rowwise() + lkg_internal_preload_score() + lkg_internal_preload_layer() + lkg_internal_preload_rank() + lkg_internal_preload_topk() + lkg_internal_preload_pairmlp() + lkg_internal_preload_triples() + lkg_internal_preload_relations() + lkg_internal_preload_accept() + lkg_internal_preload_retrieval() + lkg_internal_preload_softmax() + lkg_internal_preload_kvsall() + lkg_internal_preload_nssa() + lkg_internal_preload_negatives() + lkg_internal_preload_relation_loss() + lkg_internal_preload_gemm_ordered() + lkg_internal_preload_neighbors();
+    const int failed = lkg_internal_preload_spmm() + lkg_internal_preload_attention() + lkg_internal_preload_batch() + lkg_internal_preload_csr_device() + lkg_internal_preload_gemm() + lkg_internal_preload_gemm_tall() + lkg_internal_preload_gemm_wgrad() + lkg_internal_preload_rowwise() + lkg_internal_preload_score() + lkg_internal_preload_layer() + lkg_internal_preload_rank() + lkg_internal_preload_topk() + lkg_internal_preload_pairmlp() + lkg_internal_preload_triples() + lkg_internal_preload_relations() + lkg_internal_preload_accept() + lkg_internal_preload_retrieval() + lkg_internal_preload_softmax() + lkg_internal_preload_kvsall() + lkg_internal_preload_nssa() + lkg_internal_preload_negatives() + lkg_internal_preload_relation_loss() + lkg_internal_preload_gemm_ordered() + lkg_internal_preload_neighbors() + lkg_internal_preload_lists();
     if (failed) {
         lkg_set_error("lkg_preload: %d of the library's code objects could not be loaded on the current device", failed);
         return LKG_ERR_HIP;

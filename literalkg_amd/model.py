@@ -845,6 +845,29 @@ class LiteralKG(nn.Module):
         return evaluate_triple_classification(self, h, r, t, labels, thresholds, scoring=scoring,
                                               batch_size=batch_size)
 
+    def score_lists(self, ids, r, lists, side: str = "tail", scoring: Optional[str] = None, kernel_scores: bool = False,
+                    batch_size: Optional[int] = None):
+        """float32[B, M]: the score of every slot of every query's own candidate list int64[B, M] (a negative entry: an
+        empty slot, NaN), with the bits score_triples returns for it (literalkg_amd/lists.py, score_lists)."""
+        from .lists import score_lists
+        return score_lists(self, ids, r, lists, side=side, scoring=scoring, kernel_scores=kernel_scores,
+                           batch_size=batch_size)
+
+    def rank_in_lists(self, h, r, t, lists, side: str = "tail", known=None, scoring: Optional[str] = None,
+                      batch_size: Optional[int] = None):
+        """The filtered rank of every triple's truth among the slots of its own candidate list
+        (literalkg_amd/lists.py, rank_in_lists).  Returns a lists.ListRanks (better, equal, kept, rank)."""
+        from .lists import rank_in_lists
+        return rank_in_lists(self, h, r, t, lists, side=side, known=known, scoring=scoring, batch_size=batch_size)
+
+    def evaluate_list_ranking(self, h, r, t, tail_lists=None, head_lists=None, known=None, ks=(1, 3, 10),
+                              scoring: Optional[str] = None, batch_size: Optional[int] = None):
+        """MR, MRR and Hits@k of the triples against given negatives per side
+        (literalkg_amd/lists.py, evaluate_list_ranking)."""
+        from .lists import evaluate_list_ranking
+        return evaluate_list_ranking(self, h, r, t, tail_lists=tail_lists, head_lists=head_lists, known=known, ks=ks,
+                                     scoring=scoring, batch_size=batch_size)
+
     def score_relations(self, h, t, scoring: Optional[str] = None, side: str = "tail", batch_size: Optional[int] = None,
                         relation_chunk: Optional[int] = None):
         """float32[P, n_relations]: the score of (h_i, j, t_i) under every relation j, with the bits score_triples

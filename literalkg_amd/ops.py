@@ -2716,6 +2716,95 @@ def triple_scores(p: torch.Tensor, q_idx: torch.Tensor, c_idx: torch.Tensor, pn:
     return out, (counts if want_counts else None)
 
 
+# ----------------------------------------------------------------------------- per-query candidate lists (lkg_lists.hip)
+def checked_list_ids(n_rows: int, lists: torch.Tensor) -> torch.Tensor:
+    """The int64[B, M] slots of per-query lists as rows that are safe to gather through: a negative entry is an empty slot
+    and stays as it is, an id at or past n_rows becomes an empty slot on the device and is counted; the count surfaces as
+    an IndexError at the next poll (``check_deferred_errors()`` waits for it), as checked_ids' does."""
+    _need_gpu(lists)
+    src = _i64(lists)
+    out = torch.empty_like(src)
+    bad = torch.empty(1, dtype=torch.int32, device=src.device)
+    N.call("lkg_sanitize_ids_i64", src.numel(), N.ptr(src), -2 ** 63, int(n_rows), N.ptr(out), N.ptr(bad), _stream())
+    _Deferred.poll()
+    _Deferred.watch(bad, IndexError, "{n} " + f"entity id(s) at or past {int(n_rows)} in the candidate lists handed to the "
+                    "model (made empty slots on the device; the results of that call are meaningless)")
+    return out
+
+
+def _list_operands(what: str, q, p, pn, lists):
+    _need_gpu(q, p, pn, lists)
+    q, p = _f32_rows(q), _f32_rows(p)
+    if lists.dim() != 2 or lists.dtype != torch.int64 or lists.shape[0] != q.shape[0] or lists.shape[1] < 1:
+        raise ValueError(f"{what}: lists must be int64[{q.shape[0]}, M >= 1], got {lists.dtype} {tuple(lists.shape)}")
+    if lists.stride(1) != 1 or (lists.shape[0] > 1 and lists.stride(0) < lists.shape[1]):
+        lists = lists.contiguous()
+    if p.shape[1] != q.shape[1] or (q.shape[0] and p.shape[0] == 0):
+        raise ValueError(f"{what}: queries {tuple(q.shape)}, candidate rows {tuple(p.shape)}")
+    if pn is not None and (pn.dtype != torch.float32 or pn.numel() != p.shape[0] or not pn.is_contiguous()):
+        raise ValueError(f"{what}: pn must be a contiguous float32[{p.shape[0]}]")
+    return q, p, lists
+
+
+def list_scores(q: torch.Tensor, p: torch.Tensor, pn: Optional[torch.Tensor], lists: torch.Tensor,
+                qn: Optional[torch.Tensor] = None, reported: bool = True, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """float32[B, M] (lkg_list_scores_f32): the score of query row q[i] against row lists[i, j] of p, NaN where
+    lists[i, j] < 0 (an empty slot).  The kernel score is s = pn[c] - 2 q.p_c (pn None: dot scoring, s = -2 q.p_c), the
+    bits triple_scores and rank_count produce for that pair; reported=True gives qn[i] + s (qn: rank_sqnorm of q, made
+    here when absent) or -s / 2 for dot.  out: an optional contiguous float32[B, M] to write to.  Ids inside p."""
+    q, p, lists = _list_operands("list_scores", q, p, pn, lists)
+    b, m = lists.shape
+    dev = q.device
+    if out is None:
+        out = torch.empty((b, m), dtype=torch.float32, device=dev)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (b, m) or not out.is_contiguous() or out.device != dev:
+        raise ValueError(f"list_scores: out must be a contiguous float32[{b}, {m}] on {dev}")
+    if b == 0:
+        return out
+    if reported and pn is not None:
+        if qn is None:
+            qn = rank_sqnorm(q)
+        elif qn.dtype != torch.float32 or qn.numel() != b or not qn.is_contiguous():
+            raise ValueError(f"list_scores: qn must be a contiguous float32[{b}]")
+    else:
+        qn = None
+    N.call("lkg_list_scores_f32", b, m, p.shape[0], q.shape[1], N.ptr(q), _ld(q), N.ptr(qn), N.ptr(p), _ld(p), N.ptr(pn),
+           N.ptr(lists), _ld(lists), 1 if reported else 0, N.ptr(out), m, _stream())
+    return out
+
+
+def list_count(q: torch.Tensor, p: torch.Tensor, pn: Optional[torch.Tensor], lists: torch.Tensor, truth: torch.Tensor,
+               filt=None, filter_row: Optional[torch.Tensor] = None, filter_rel: Optional[torch.Tensor] = None,
+               cand_ids: Optional[torch.Tensor] = None):
+    """(better, equal, kept) int64[B] of lkg_list_count_f32: query row q[i] against its own slots lists[i, :] (rows of p,
+    negative = empty), truth[i] the row of p its truth lies in.  A slot is counted unless it is empty, is the truth's
+    row, or forms a known triple: filt = (rowptr, col, eptr, rel) of csr_build_device over entity ids, query i dropping
+    the cols of row filter_row[i] under relation filter_rel[i] (negative: under any); cand_ids[row] is the entity id of a
+    row of p (None: the row number).  No score is stored."""
+    q, p, lists = _list_operands("list_count", q, p, pn, lists)
+    _need_gpu(truth, cand_ids)
+    b, m = lists.shape
+    dev = q.device
+    truth = _i64(truth.reshape(-1))
+    if truth.numel() != b:
+        raise ValueError(f"list_count: {truth.numel()} truths for {b} queries")
+    if cand_ids is not None:
+        cand_ids = _i64(cand_ids.reshape(-1))
+        if cand_ids.numel() != p.shape[0]:
+            raise ValueError(f"list_count: {cand_ids.numel()} entity ids for {p.shape[0]} candidate rows")
+    elif filt is not None and filt[0].numel() != p.shape[0] + 1:
+        raise ValueError(f"list_count: the filter covers {filt[0].numel() - 1} rows, the candidates {p.shape[0]}")
+    better = torch.zeros(b, dtype=torch.int64, device=dev)
+    equal = torch.zeros(b, dtype=torch.int64, device=dev)
+    kept = torch.zeros(b, dtype=torch.int64, device=dev)
+    fargs = _filter_args("list_count", filt, filter_row, filter_rel, b)
+    if b:
+        N.call("lkg_list_count_f32", b, m, p.shape[0], q.shape[1], N.ptr(q), _ld(q), N.ptr(p), _ld(p), N.ptr(pn),
+               N.ptr(lists), _ld(lists), N.ptr(truth), N.ptr(cand_ids) if filt is not None else None, *fargs(),
+               N.ptr(better), N.ptr(equal), N.ptr(kept), _stream())
+    return better, equal, kept
+
+
 def threshold_fit(scores: torch.Tensor, labels: torch.Tensor, rel: Optional[torch.Tensor], n_relations: int,
                   lower_is_better: bool):
     """(thr float32[n_relations], stats int64[n_relations, 4]) of lkg_threshold_fit_f32, both on the device: per
