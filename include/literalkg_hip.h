@@ -956,6 +956,345 @@ int lkg_softmax_all_weights_masked_f32(int64_t n_q, int64_t n_cand, int32_t k, c
                                        const int32_t *xptr, const int32_t *xcol, int64_t n_excl, float *v, int64_t ldv,
                                        void *stream);
 
+/* ------------------------------------------------- KvsAll training loss -- */
+
+/* KvsAll training loss (lkg_kvsall.hip; literalkg_amd/kvs_all.py): binary cross-entropy with logits of EVERY candidate
+ * against the multi-hot vector of a query's known answers.  Queries, candidates and the kernel score s(i, c) as for
+ * lkg_rank_* / lkg_softmax_all_*, bit for bit.  The logit is
+ *     z(i, c) = fl(fl(-scale * beta * s(i, c)) + bias[i])      (pn given: beta = 1; pn NULL: beta = 1/2, s = -2 q.p),
+ * bias float[n_q] or NULL (= 0); scale > 0, finite.  The positives of query i are the candidate POSITIONS
+ * ycol[yptr[i] .. yptr[i + 1]) (ascending, unique, n_pos = yptr[n_q] < 2^31 entries in all; lkg_softmax_excluded with
+ * truth = -1 builds them); yptr NULL = every list empty, with the same bits.  With y = 1 on a positive and 0 elsewhere,
+ *     loss_i = sum_c softplus(z) - y' z,      y' = (1 - eps) y + eps / n,      0 <= eps < 1  (label smoothing),
+ * each term as softplus(y ? -z : z) + ce_y z with ce_1 = eps (1 - 1/n), ce_0 = -eps / n formed in double and rounded once;
+ * with eps == 0 the product is not executed.  A NaN logit poisons its own row only.
+ *
+ * lkg_sigmoid_all_partial_f32: per split j and query i  ws[j * n_q + i] = the sum of the terms of the split's candidates
+ *     (splits = lkg_softmax_all_splits(n_q, n_cand, splits); n = n_cand).  The n_q x n_cand logits are never stored.
+ * lkg_sigmoid_all_finish_f32 : loss[i] = fl32(sum_j ws[j * n_q + i]), added in split order in float64 (any splits >= 1: it
+ *     also adds the row sums of lkg_sigmoid_all_weights_f32 over that call's tiles).
+ * lkg_sigmoid_all_weights_f32: the backward's recompute for a chunk of n_cand candidates that starts at candidate c_base
+ *     of the n_total candidates the forward pass ran over (p and pn point AT the chunk; bias and g are per query; the lists
+ *     hold positions of the whole table, and n of the smoothing is n_total, not the chunk's width):
+ *         v[i * ldv + c] = scale * beta * g[i] * (sigma(z(i, c_base + c)) - y'(i, c_base + c)),
+ *     evaluated as ce_1 - sigma(-z) for a positive and sigma(z) + ce_0 otherwise.  With it  dQ = 2 V P,
+ *     dP = 2 V^T Q - 2 diag(colsum V) P  (the second term only with pn)  and  dbias = rowsum(V) / (scale * beta).
+ *     rowsum (nullable) float[ceil(n_cand / 256) * n_q]: rowsum[t * n_q + i] = the sum of v[i, 256 t .. 256 t + 255] as
+ *     stored, added in a fixed order in registers and LDS.
+ * No float atomics: for a given number of splits every output repeats bit for bit.  n_q == 0 launches nothing;
+ * addressing is 64-bit.                                                                                               */
+int lkg_sigmoid_all_partial_f32(int64_t n_q, int64_t n_cand, int32_t k, const float *q, int64_t ldq, const float *p,
+                                int64_t ldp, const float *pn, const float *bias, float scale, double eps, int32_t splits,
+                                const int32_t *yptr, const int32_t *ycol, int64_t n_pos, float *ws, void *stream);
+int lkg_sigmoid_all_finish_f32(int64_t n_q, int32_t splits, const float *ws, float *loss, void *stream);
+int lkg_sigmoid_all_weights_f32(int64_t n_q, int64_t n_cand, int32_t k, const float *q, int64_t ldq, const float *p,
+                                int64_t ldp, const float *pn, const float *bias, int64_t c_base, int64_t n_total,
+                                const float *g, float scale, double eps, const int32_t *yptr, const int32_t *ycol,
+                                int64_t n_pos, float *v, int64_t ldv, float *rowsum, void *stream);
+
+/* ------------------------------- training objectives on sampled rows -- */
+
+/* Self-adversarial negative-sampling loss on grouped rows (lkg_nssa.hip; literalkg_amd/self_adversarial.py).  n_groups
+ * groups; group g has the anchor row q[g * ldq ..], the positive row p[g * ldp ..] and the n_neg >= 1 negative rows
+ * n[(g * n_neg + j) * ldn ..], all of k float32 columns with free row strides.  With s(x) = sum_c (q_c - x_c)^2 summed
+ * directly (distance != 0) or s(x) = sum_c q_c x_c (distance == 0), the logit of a row is
+ *     z(x) = fl(scale * fl(margin - s(x)))   (distance)        z(x) = fl(scale * fl(margin + s(x)))   (dot),
+ * scale > 0 and finite, margin finite.  The weights are  w_j = e_j / sum_j e_j,  e_j = exp(temperature z_j - max_j
+ * temperature z_j),  temperature >= 0 and finite (0: every w_j = fl(1 / n_neg)); they are constants of the loss
+ *     loss_g = softplus(-z+) + sum_j w_j softplus(z_j),
+ * every softplus evaluated as max(x, 0) + log1p(exp(-|x|)).
+ *
+ * lkg_nssa_fwd_f32: z_pos[n_groups], z_neg[n_groups * n_neg], w[n_groups * n_neg] and loss[n_groups], each written once.
+ * lkg_nssa_bwd_f32: from the upstream g[n_groups] and the kept z_pos, z_neg, w, with a_0 = -g sigma(-z+),
+ *     a_j = g w_j sigma(z_j) (sigma on the side that does not cancel) and c_x = (distance ? 2 scale : scale) a_x:
+ *         distance:  dp = c_0 (q - p),   dn_j = c_j (q - n_j),   dq = -sum_x c_x (q - x)
+ *         dot:       dp = c_0 q,         dn_j = c_j q,           dq = sum_x c_x x
+ *     into dq[g * lddq ..], dp[g * lddp ..], dn[(g * n_neg + j) * lddn ..], every element stored once.  dq, dp or dn may
+ *     be NULL: that output is not computed, the others keep their bits.
+ * A group's outputs depend on its own rows alone (not on n_groups, its position or other groups), the sums run in a fixed
+ * order and there are no atomics: every output repeats bit for bit, and the 16-byte and the scalar load path give the
+ * same bits.  n_groups == 0 launches nothing; addressing is 64-bit.                                                    */
+int lkg_nssa_fwd_f32(int64_t n_groups, int64_t n_neg, int32_t k, const float *q, int64_t ldq, const float *p,
+                     int64_t ldp, const float *n, int64_t ldn, int32_t distance, float margin, float scale,
+                     float temperature, float *z_pos, float *z_neg, float *w, float *loss, void *stream);
+int lkg_nssa_bwd_f32(int64_t n_groups, int64_t n_neg, int32_t k, const float *q, int64_t ldq, const float *p,
+                     int64_t ldp, const float *n, int64_t ldn, int32_t distance, float scale, const float *g,
+                     const float *z_pos, const float *z_neg, const float *w, float *dq, int64_t lddq, float *dp,
+                     int64_t lddp, float *dn, int64_t lddn, void *stream);
+
+/* ---------------------------- negative sampling for given positives --
+ * The known triples are two structures of lkg_csr_build_device over n_entities rows, int32 (rowptr, col, eptr, rel): "head_*"
+ * has rows = heads with their tails (it answers "is (h, r, c) known?", the tail side), "tail_*" rows = tails with their
+ * heads ("is (c, r, t) known?", the head side).  n_raw is the number of raw triples either was built from (eptr[nnz]).
+ */
+
+#define LKG_SAMPLE_MAX_TRIES 64
+#define LKG_CORRUPT_TAIL 0
+#define LKG_CORRUPT_HEAD 1
+#define LKG_CORRUPT_BOTH 2
+#define LKG_CORRUPT_BERNOULLI 3
+
+/* lkg_sample_negatives (lkg_negatives.hip; literalkg_amd/negatives.py): for the n_groups positives (h[g], r[g], t[g]) and
+ * n_slots >= 1 slots each, neg int64[n_groups * n_slots], head_side uint8[n_groups] and unfiltered uint8[n_groups *
+ * n_slots], every element stored once by plain stores.  The draw is counter-based; with mix64 splitmix64's finaliser, all
+ * arithmetic mod 2^64 and gid = group_offset + g,
+ *     key(seed, gid)      = mix64(seed ^ (0xD1B54A32D192ED03 * (gid + 1)))
+ *     value(seed, gid, c) = mix64(key(seed, gid) + 0x9E3779B97F4A7C15 * c).
+ * Counter 0 decides the side: LKG_CORRUPT_TAIL never the head, LKG_CORRUPT_HEAD always, LKG_CORRUPT_BOTH iff value % 2 == 1,
+ * LKG_CORRUPT_BERNOULLI iff value % (H + Tl) < Tl with H = rel_heads[r[g]], Tl = rel_tails[r[g]] (the distinct heads and
+ * tails of the relation, lkg_relation_cardinality; H + Tl == 0, or r[g] outside [0, n_relations): the tail).  Slot j, try i
+ * (0 <= i < LKG_SAMPLE_MAX_TRIES) uses counter 1 + j * LKG_SAMPLE_MAX_TRIES + i; its candidate is pool[value % pool_len]
+ * of the side's pool (tail_pool / head_pool, entity ids drawn by position), or value % n_entities with a NULL pool.  A
+ * candidate is rejected when it equals the truth of the corrupted slot (t[g], or h[g] on the head side) or when filtered != 0
+ * and (h[g], r[g], cand) -- head side: (cand, r[g], t[g]) -- is known; any_relation != 0: known under any relation.  The
+ * first candidate that passes is stored; after LKG_SAMPLE_MAX_TRIES rejections the last candidate is stored with its
+ * unfiltered flag set.  A candidate equal to the anchor entity and duplicates inside a group are NOT rejected: a slot
+ * depends on (seed, gid, h, r, t, j) alone.  One thread per (group, slot); no atomics.  Only the structures of a side that
+ * can be corrupted are read, and only with filtered != 0; an h / t outside [0, n_entities) reads no row (callers refuse
+ * such ids before the launch).  n_groups == 0 launches nothing; n_groups * n_slots <= 2^38.                          */
+int lkg_sample_negatives(int64_t n_groups, int64_t n_slots, uint64_t seed, int64_t group_offset, const int64_t *h,
+                         const int64_t *r, const int64_t *t, int64_t n_entities, int64_t n_relations, int32_t mode,
+                         int32_t filtered, int32_t any_relation, const int32_t *head_rowptr, const int32_t *head_col,
+                         const int32_t *head_eptr, const int32_t *head_rel, const int32_t *tail_rowptr,
+                         const int32_t *tail_col, const int32_t *tail_eptr, const int32_t *tail_rel,
+                         const int64_t *rel_heads, const int64_t *rel_tails, const int64_t *tail_pool,
+                         int64_t tail_pool_len, const int64_t *head_pool, int64_t head_pool_len, int64_t *neg,
+                         uint8_t *head_side, uint8_t *unfiltered, void *stream);
+
+/* lkg_relation_cardinality: per relation r of n_relations <= LKG_RELATION_MAX, n_triples[r] = the distinct known (h, r, t),
+ * n_heads[r] = the distinct h and n_tails[r] = the distinct t among them, each int64[n_relations] (a duplicated triple
+ * counts once; a relation id outside [0, n_relations) nowhere).  head_nnz = the entries of the head structure.  One wave per
+ * row with a bitmap of the row's relations in LDS for the heads and the tails, one thread per raw triple for the triples;
+ * integer atomics only, so the result does not depend on any order.  The outputs are zeroed on the stream first.    */
+int lkg_relation_cardinality(int64_t n_entities, int64_t n_relations, int64_t n_raw, const int32_t *head_rowptr,
+                             const int32_t *head_eptr, const int32_t *head_rel, int64_t head_nnz,
+                             const int32_t *tail_rowptr, const int32_t *tail_eptr, const int32_t *tail_rel,
+                             int64_t *n_triples, int64_t *n_heads, int64_t *n_tails, void *stream);
+
+/* lkg_answer_counts: per triple g of n, n_tails[g] = the distinct known tails of (h[g], r[g], ?) and n_heads[g] = the
+ * distinct known heads of (?, r[g], t[g]), int64[n] each, stored once; r[g] < 0: under any relation (the row's entry
+ * count).  An h / t outside [0, n_entities) counts 0.  One thread per (triple, side); no atomics.                   */
+int lkg_answer_counts(int64_t n, const int64_t *h, const int64_t *r, const int64_t *t, int64_t n_entities,
+                      const int32_t *head_rowptr, const int32_t *head_eptr, const int32_t *head_rel,
+                      const int32_t *tail_rowptr, const int32_t *tail_eptr, const int32_t *tail_rel, int64_t *n_tails,
+                      int64_t *n_heads, void *stream);
+
+/* ------------------------------- relation-slot training objective -- */
+
+/* Softmax cross-entropy of the true relation of a pair against every relation (lkg_relation_loss.hip;
+ * literalkg_amd/relation_loss.py).  n pairs, n_rel >= 1 relations, k >= 1 float32 columns per block.
+ *
+ * Slab mode (rel_stride > 0): pair i, relation j owns the block u[i * ldu + j * rel_stride ..] of k columns
+ * (rel_stride >= k, ldu >= (n_rel - 1) * rel_stride + k).  Shared mode (rel_stride == 0): pair i owns the ONE row
+ * u[i * ldu ..] of k columns, read for every relation (ldu >= k).  With e[j * lde ..] the relation's row (lde >= k),
+ *     s_ij = sum_c (u_ijc + e_jc)^2   summed directly (one fma chain per lane over its 4-column units lane, lane + 64, ...,
+ *                                     then one butterfly over the wave),
+ *     z_ij = -fl(scale * s_ij),       scale > 0 and finite.
+ * A filter (rowptr != NULL: the four arrays of lkg_csr_build_device, filter_row[n] and filter_col[n] in its row and column
+ * ids, all in range) makes every relation rr != truth[i] listed under the entry (filter_row[i], filter_col[i]) ineligible:
+ * z[i, rr] = -inf.  truth[i] in [0, n_rel) is never dropped; duplicates in the filter change nothing.  Then
+ *     m_i = max_j z_ij,   sum_i = sum_j exp(z_ij - m_i),   lse_i = m_i + log(sum_i),
+ *     loss_i = (m_i - z_i,truth_i) + log(sum_i)
+ * (a pair whose only eligible relation is the truth: exactly 0).
+ *
+ * lkg_relation_loss_fwd_f32 stores z[i * ldz + j] (ldz >= n_rel), lse[n] and loss[n], each element once (a dropped
+ * relation's logit twice: the value, then -inf).
+ * lkg_relation_loss_bwd_f32 reads the upstream g[n], z and truth, takes m_i and sum_i from the stored row again (the
+ * forward's own passes: the same bits; exp(z_ij - lse_i) would carry half an ulp of lse into every softmax) and forms
+ *     c_ij = fl(fl(-2 scale * g_i) * (exp(z_ij - m_i) / sum_i - [j == truth_i])),      exactly 0.0 where z_ij = -inf.
+ *   Slab mode: every block of u is OVERWRITTEN in place by c_ij (u_ij + e_j), each element stored once (zeros, not
+ *     products, where z_ij = -inf); gd and c must be NULL.
+ *   Shared mode: u is only read; gd[i * ldgd ..] = sum_j c_ij (u_i + e_j), added in increasing j (ldgd >= k), and
+ *     c[i * ldc + j] = c_ij (ldc >= n_rel).  Either of gd, c may be NULL: it is not computed, the other keeps its bits.
+ *
+ * One wave per pair.  A pair's outputs depend on its own blocks, e, its truth and its filter entry alone -- not on n, on
+ * its position or on other pairs -- the sums run in a fixed order and there are no atomics: every output repeats bit for
+ * bit, and the 16-byte and the scalar load path (taken when k, a stride or a pointer is not a multiple of 4 elements /
+ * 16 bytes) give the same bits.  n == 0 launches nothing; addressing is 64-bit.                                          */
+int lkg_relation_loss_fwd_f32(int64_t n, int32_t n_rel, int32_t k, const float *u, int64_t ldu, int64_t rel_stride,
+                              const float *e, int64_t lde, const int64_t *truth, const int64_t *filter_row,
+                              const int64_t *filter_col, const int32_t *rowptr, const int32_t *col, const int32_t *eptr,
+                              const int32_t *rel, float scale, float *z, int64_t ldz, float *lse, float *loss,
+                              void *stream);
+int lkg_relation_loss_bwd_f32(int64_t n, int32_t n_rel, int32_t k, float *u, int64_t ldu, int64_t rel_stride,
+                              const float *e, int64_t lde, const int64_t *truth, float scale, const float *g,
+                              const float *z, int64_t ldz, float *gd, int64_t ldgd, float *c, int64_t ldc,
+                              void *stream);
+
+/* ----------------------------------------------- ordered split-K GEMM -- */
+
+/* C = alpha * op(A) op(B) + beta * C (+ bias[n]) in float32 for products with a SMALL output and a LONG reduction
+ * (lkg_gemm_ordered.hip; literalkg_amd/gemm_ordered.py): the reduction is spread over the chip as lkg_gemm_f32's atomic
+ * split does, but the pieces are added in a fixed order, so every output repeats bit for bit.  op(A) is m x k (A stored
+ * k x m with trans_a), op(B) is k x n (B stored n x k with trans_b), row-major with free row strides; ldc >= n.
+ *
+ * The partition.  For `splits` = S in [1, 256]:
+ *     per   = 16 * ceil(ceil(k / S) / 16)          (0 for k == 0)
+ *     S_eff = ceil(k / per)                        (0 for k == 0; at most min(S, ceil(k / 16)))
+ * and split z in [0, S_eff) covers k in [z * per, min(k, (z + 1) * per)): every boundary but the last is a multiple of
+ * 16.  lkg_gemm_ordered_partition returns S_eff and stores per (per may be NULL); a negative lkg_status on bad arguments.
+ *
+ * The arithmetic.  A first launch of (output tiles) x S_eff workgroups computes, per element and split, the partial
+ *     p_z = the k-ordered fmaf chain of the exact f32-input MFMA (v_mfma_f32_32x32x2_f32) over the split's k, from 0.0,
+ *           one rounding per product -- the bits an UNSPLIT call over the k-slice alone produces with alpha = 1, beta = 0,
+ * and stores it with plain vector stores into workspace[z][m][n] (float32, contiguous).  A second launch forms
+ *     s   = ((p_0 + p_1) + p_2) + ...               float32 adds in ascending z
+ *     t   = fmaf(alpha, s, bias[j])                 (bias NULL: 0.0f)
+ *     out = beta == 0 ? t : fmaf(beta, C_old, t)    (C is not read when beta == 0)
+ * With S_eff == 1 the first launch applies the last two lines to s = p_0 itself: no workspace, no second launch.  k == 0
+ * gives s = 0.0, that is beta * C + bias.  There are no atomics, no counters and no in-launch combine.
+ *
+ * The property.  An output element is a function of its row of op(A), its column of op(B), k, per, alpha, beta, its old C
+ * and its bias -- not of m, n, other rows or columns, alignment, strides, the stream, the workspace's previous contents
+ * or the run.  The 16-byte load path and the clamped scalar one (edge tiles; an operand whose address is not a multiple of
+ * 16 bytes or whose row stride is not a multiple of 4 elements) give the same bits.
+ *
+ * lkg_gemm_ordered_splits: the default S, a pure function of its five arguments (no device query, no environment):
+ *     tiles = ceil(m / 128) * ceil(n / 128)
+ *     S     = max(1, min(512 / tiles, k / 512, 2^26 / (m * n), 256))          (integer divisions)
+ * about two workgroups per CU of a 256-CU device, no split shorter than 512 k, partials within 256 MB.
+ * lkg_gemm_ordered_workspace: the bytes lkg_gemm_ordered_f32 needs for (m, n, k, splits): S_eff * m * n * 4, 0 for
+ * S_eff <= 1; a negative lkg_status on bad arguments.
+ * lkg_gemm_ordered_f32: splits outside [1, 256], a workspace shorter than that, a leading dimension smaller than the
+ * stored row or a null operand is LKG_ERR_INVALID_ARG before any launch.  m == 0 or n == 0 launches nothing.               */
+int32_t lkg_gemm_ordered_splits(int32_t trans_a, int32_t trans_b, int64_t m, int64_t n, int64_t k);
+int64_t lkg_gemm_ordered_partition(int64_t k, int32_t splits, int64_t *per);
+int64_t lkg_gemm_ordered_workspace(int64_t m, int64_t n, int64_t k, int32_t splits);
+int lkg_gemm_ordered_f32(int32_t trans_a, int32_t trans_b, int64_t m, int64_t n, int64_t k, int32_t splits, float alpha,
+                         const float *a, int64_t lda, const float *b, int64_t ldb, float beta, float *c, int64_t ldc,
+                         const float *bias, void *workspace, int64_t workspace_bytes, void *stream);
+
+/* ---------------- neighbour sampling for the batch-pruned training step -- */
+
+/* lkg_csr_extract_rows with a fixed fanout (lkg_neighbors.hip; literalkg_amd/pruned.py): of every selected row at most
+ * `fanout` stored entries are copied into the compact CSR, chosen by a counter-based draw.  The argument conventions are
+ * those of lkg_csr_extract_rows: sel_rows[n_sel] the (sorted) global row ids, (rowptr, col, val) the CSR they are taken
+ * from, out_rowptr[n_sel + 1] the CALLER'S exclusive scan of min(d_i, fanout), out_col / out_val the destinations; col
+ * keeps the original ids.
+ *
+ * The draw.  mix64 is splitmix64's finaliser, arithmetic is mod 2^64, G = 0xD1B54A32D192ED03, S = 0x9E3779B97F4A7C15.
+ * For row i (its global id) with d stored entries at positions j = 0 .. d - 1 in CSR order:
+ *     d <= fanout   every entry is kept, col and val unchanged to the bit (what lkg_csr_extract_rows writes)
+ *     d >  fanout   epoch_key = mix64(seed ^ (G * (draw + 1)))
+ *                   row_key   = mix64(epoch_key ^ (G * (i + 1)))
+ *                   value(j)  = mix64(row_key + S * (j + 1))
+ *                   kept: the `fanout` smallest entries under the order (value(j), j), written in ascending j
+ *                   rescale != 0: a kept value is val[j] * scale, scale = float32(d) / float32(fanout) -- two conversions
+ *                   to nearest even, one float32 division, one rounded product; rescale == 0: the value is copied
+ * A row's sample is a function of (seed, draw, i, the row's entries, fanout, rescale) alone: not of the other selected
+ * rows, of alignment, of the stream or of the run.  Every output element is stored once with a plain store; there are no
+ * atomics on global memory and no workspace.
+ *
+ * fanout < 1, n_sel < 0 or (with n_sel > 0) a null pointer is LKG_ERR_INVALID_ARG before any launch; n_sel == 0 launches
+ * nothing.                                                                                                                */
+int lkg_csr_sample_rows(int64_t n_sel, const int64_t *sel_rows, const int32_t *rowptr, const int32_t *col,
+                        const float *val, int32_t fanout, uint64_t seed, uint64_t draw, int32_t rescale,
+                        const int32_t *out_rowptr, int32_t *out_col, float *out_val, void *stream);
+
+/* ------------------------ threshold retrieval under the MLP pair head --
+ * literalkg_amd/pairmlp.py (predict_accepted_mlp, count_accepted_mlp) drives it. */
+
+/* The three entry points below share their operands with lkg_pair_mlp_select_f32 (lkg_pairmlp.hip): uq[n_q x 128] the
+ * projected query rows (fc1's bias included), v[n_cand x 128] the projected candidate rows, (w2, b2, w3, b3) the folded
+ * head, cand_ids[n_cand] the entity id of every candidate row (NULL: the row number), and the known-triples filter
+ * (filter_row[n_q], filter_rel[n_q], rowptr, col, eptr, rel) of lkg_csr_build_device over entity ids: query i drops the
+ * candidates whose id is a col of row filter_row[i] under relation filter_rel[i] (-1: under any).  The filter is absent
+ * (rowptr NULL) or complete.  thr[n_q] holds one float32 logit threshold per query.
+ *
+ * The decision.  z(i, c) is the logit lkg_pair_mlp_scores_f32 stores for the pair, bit for bit, whatever tile, wave,
+ * split or launch computes it.  Candidate c of query i is ACCEPTED iff z(i, c) > thr[i] in one float32 compare, strictly
+ * (a NaN logit or a NaN threshold accepts nothing; thr = +inf accepts nothing; thr = -inf accepts every logit that is
+ * neither NaN nor -inf), and the filter does not drop it.  Only a candidate that passes the compare is looked up in the
+ * filter.
+ *
+ *   lkg_pair_mlp_accept_count_f32    counts[i] += the number of accepted candidates of query i.  The caller zeroes
+ *                                    counts.  Integer atomics only: the counts do not depend on the order of anything.
+ *   lkg_pair_mlp_accept_append_f32   the same counts, and in the same pass every accepted entry takes a slot from the
+ *                                    ONE 64-bit cursor (*cursor, zeroed by the caller).  A slot below `capacity` writes
+ *                                    out_rows[slot] = i, out_ids[slot] = the id, out_logits[slot] = z; a slot at or past
+ *                                    it writes nothing.  The counts are exact whether or not the buffer overflows, and
+ *                                    overflow is sum(counts) > capacity (then *cursor == sum(counts) too).  The entries
+ *                                    are in no particular order.  capacity == 0 needs no output buffers.
+ *   lkg_pair_mlp_accept_emit_f32     the second pass of the two-pass route: counts[n_q] are those of a count over the
+ *                                    same arguments, base[n_q] their exclusive scan (int64), cursor[n_q] zeroed by the
+ *                                    caller.  Every accepted entry of query i takes slot = cursor[i]++ and writes
+ *                                    out_ids / out_scores (s = -2 z, exact, the ascending key of lkg_accept_order) /
+ *                                    out_logits at base[i] + slot when 0 <= slot < counts[i]; otherwise it writes
+ *                                    nothing and sets *flag to 1.  With the counts of the same arguments the flag stays 0.
+ *                                    A row's entries are in no particular order; (s, id) is unique within a row, so
+ *                                    lkg_accept_order makes the result unique.
+ *
+ * splits: candidate splits per launch, 0 = automatic, else 1 .. LKG_TOPK_MAX_SPLITS; resolved by lkg_pair_mlp_splits.
+ * No result depends on it.
+ *
+ * Conventions: uq and v hold DENSE rows of 128 floats -- row i starts at element 128 i; there is no row-stride argument
+ * (the projections that feed these entry points are dense, and every row-strided operand of this library is an operand
+ * that has to be exercised past 2^32 elements) -- and uq, v and w2 are 16-byte aligned; n_q, n_cand and capacity below
+ * 2^31 - 1; n_q == 0 or n_cand == 0 launches nothing; a bad size, a null pointer, a misaligned operand or an incomplete
+ * filter is LKG_ERR_INVALID_ARG before any launch.  No float atomics.                                                      */
+int lkg_pair_mlp_accept_count_f32(int64_t n_q, int64_t n_cand, const float *uq, const float *v,
+                                  const float *w2, const float *b2, const float *w3, const float *b3, const float *thr,
+                                  const int64_t *cand_ids, const int64_t *filter_row, const int64_t *filter_rel,
+                                  const int32_t *rowptr, const int32_t *col, const int32_t *eptr, const int32_t *rel,
+                                  int32_t splits, int32_t *counts, void *stream);
+
+int lkg_pair_mlp_accept_append_f32(int64_t n_q, int64_t n_cand, const float *uq, const float *v,
+                                   const float *w2, const float *b2, const float *w3, const float *b3, const float *thr,
+                                   const int64_t *cand_ids, const int64_t *filter_row, const int64_t *filter_rel,
+                                   const int32_t *rowptr, const int32_t *col, const int32_t *eptr, const int32_t *rel,
+                                   int32_t splits, int32_t *counts, int64_t capacity, int64_t *cursor, int32_t *out_rows,
+                                   int32_t *out_ids, float *out_logits, void *stream);
+
+int lkg_pair_mlp_accept_emit_f32(int64_t n_q, int64_t n_cand, const float *uq, const float *v,
+                                 const float *w2, const float *b2, const float *w3, const float *b3, const float *thr,
+                                 const int64_t *cand_ids, const int64_t *filter_row, const int64_t *filter_rel,
+                                 const int32_t *rowptr, const int32_t *col, const int32_t *eptr, const int32_t *rel,
+                                 int32_t splits, const int32_t *counts, const int64_t *base, int32_t *cursor,
+                                 int64_t *out_ids, float *out_scores, float *out_logits, int32_t *flag, void *stream);
+
+/* ------------- scoring and ranking against per-query candidate lists --
+ * literalkg_amd/lists.py (score_lists, rank_in_lists, evaluate_list_ranking) drives it. */
+
+/* Operands of both entry points.  q[n_q x k] (row stride q_stride) the query rows lkg_rank_queries_f32 makes; p[n_rows x k]
+ * (row stride p_stride) the candidate rows with their squared norms pn[n_rows] (lkg_rank_sqnorm_f32; NULL: dot scoring);
+ * lists[n_q x m] (row stride lists_stride, m >= 1) the slots of every query: slot j of query i holds a row number of p, or a
+ * negative value for an EMPTY slot.  A row number at or past n_rows is treated as an empty slot (nothing is read out of
+ * bounds); callers check their ids beforehand.
+ *
+ * The kernel score of (query i, row c) is s = pn[c] - 2 q_i . p_c (dot scoring: -2 q_i . p_c), the bits
+ * lkg_rank_count_f32 compares and lkg_triple_scores_f32 stores for that (query, candidate), whatever slot, slice, wave
+ * or launch computes it.
+ *
+ *   lkg_list_scores_f32   out[i * out_stride + j] = the score of slot j of query i, NaN for an empty slot.  flags bit 0
+ *                         (reported): qn[i] + s with pn given (qn[n_q]: lkg_rank_sqnorm_f32 over q, required then) or
+ *                         -s / 2 for dot scoring; flags 0: s itself (qn is not read).
+ *   lkg_list_count_f32    truth[n_q] holds the row of p that is query i's truth; its score comes from the same chain.
+ *                         Slot j of query i is COUNTED unless it is empty, its row is truth[i], or the filter drops it:
+ *                         (filter_row[n_q], filter_rel[n_q], rowptr, col, eptr, rel) of lkg_csr_build_device over entity
+ *                         ids, query i dropping the slots whose entity id is a col of row filter_row[i] under relation
+ *                         filter_rel[i] (negative: under any).  cand_ids[n_rows] is the entity id of every row of p
+ *                         (NULL: the row number).  The filter is absent (rowptr NULL) or complete.
+ *                         kept[i] += the counted slots, better[i] += those with s < s_truth, equal[i] += those with
+ *                         s == s_truth, by float32 compares (a NaN on either side is neither).  The caller zeroes the
+ *                         three int64 arrays; the additions are integer atomics, so no order enters.  No score is stored.
+ *
+ * The row strides are named *_stride, in elements: tests/test_lists_gpu.py places p itself past 2^31 and 2^32 elements
+ * (the ledger of tests/wide_cases.py follows the arguments named ld* of the training and query entry points).
+ *
+ * Conventions: n_q * ceil(m / 256) below 2^31 - 1 (one workgroup per query and slice of 256 slots); n_rows below
+ * 2^31 - 1; all row offsets are 64-bit; 16-byte loads are used only where q, p and their strides allow them; n_q == 0 launches
+ * nothing; a bad size, a null pointer or an incomplete filter is LKG_ERR_INVALID_ARG before any launch.  No float
+ * atomics.                                                                                                             */
+int lkg_list_scores_f32(int64_t n_q, int64_t m, int64_t n_rows, int32_t k, const float *q, int64_t q_stride, const float *qn,
+                        const float *p, int64_t p_stride, const float *pn, const int64_t *lists, int64_t lists_stride,
+                        int32_t flags, float *out, int64_t out_stride, void *stream);
+
+int lkg_list_count_f32(int64_t n_q, int64_t m, int64_t n_rows, int32_t k, const float *q, int64_t q_stride, const float *p,
+                       int64_t p_stride, const float *pn, const int64_t *lists, int64_t lists_stride, const int64_t *truth,
+                       const int64_t *cand_ids, const int64_t *filter_row, const int64_t *filter_rel,
+                       const int32_t *rowptr, const int32_t *col, const int32_t *eptr, const int32_t *rel,
+                       int64_t *better, int64_t *equal, int64_t *kept, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,9 +5,11 @@ import os
 _LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "liblkg_hip.so")
 _lib = None
 
-i64, i32, f32, vp, u64 = C.c_int64, C.c_int32, C.c_float, C.c_void_p, C.c_uint64
+i64, i32, f32, f64, vp, u64 = C.c_int64, C.c_int32, C.c_float, C.c_double, C.c_void_p, C.c_uint64
 
-# name -> argtypes (restype is int unless listed in _RESTYPE); mirrors include/literalkg_hip.h
+_PAIR_ACCEPT_HEAD = [i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp]   # .. splits, counts
+# name -> argtypes (restype is int unless listed in _RESTYPE); mirrors include/literalkg_hip.h, the whole ABI, by hand:
+# tests/test_native_abi.py compares every row with the header's declaration, argument by argument
 PROTOTYPES = {
     "lkg_version": [],
     "lkg_last_error": [],
@@ -132,52 +134,34 @@ PROTOTYPES = {
     "lkg_softmax_all_partial_masked_f32": [i64, i64, i32, vp, i64, vp, i64, vp, f32, i32, vp, vp, i64, vp, vp, vp],
     "lkg_softmax_all_weights_masked_f32": [i64, i64, i32, vp, i64, vp, i64, vp, i64, vp, vp, vp, vp, f32, vp, vp, i64, vp,
                                            i64, vp],
-}
-# the second table: include/literalkg_hip_ext.h, mirrored the same way (load() types both)
-f64 = C.c_double
-EXTRA_PROTOTYPES = {
+    # KvsAll training loss
     "lkg_sigmoid_all_partial_f32": [i64, i64, i32, vp, i64, vp, i64, vp, vp, f32, f64, i32, vp, vp, i64, vp, vp],
     "lkg_sigmoid_all_finish_f32": [i64, i32, vp, vp, vp],
     "lkg_sigmoid_all_weights_f32": [i64, i64, i32, vp, i64, vp, i64, vp, vp, i64, i64, vp, f32, f64, vp, vp, i64, vp, i64,
                                     vp, vp],
-}
-# the third table: include/literalkg_hip_train.h (training objectives on sampled rows), mirrored the same way
-TRAIN_PROTOTYPES = {
+    # training objectives on sampled rows
     "lkg_nssa_fwd_f32": [i64, i64, i32, vp, i64, vp, i64, vp, i64, i32, f32, f32, f32, vp, vp, vp, vp, vp],
     "lkg_nssa_bwd_f32": [i64, i64, i32, vp, i64, vp, i64, vp, i64, i32, f32, vp, vp, vp, vp, vp, i64, vp, i64, vp, i64, vp],
-}
-# the fourth table: include/literalkg_hip_sample.h (negative sampling for given positives), mirrored the same way
-SAMPLE_PROTOTYPES = {
+    # negative sampling for given positives
     "lkg_sample_negatives": [i64, i64, u64, i64, vp, vp, vp, i64, i64, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
                              vp, i64, vp, i64, vp, vp, vp, vp],
     "lkg_relation_cardinality": [i64, i64, i64, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp],
     "lkg_answer_counts": [i64, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp],
-}
-# the fifth table: include/literalkg_hip_relation_train.h (the relation-slot training objective), mirrored the same way
-RELATION_TRAIN_PROTOTYPES = {
+    # the relation-slot training objective
     "lkg_relation_loss_fwd_f32": [i64, i32, i32, vp, i64, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, f32, vp, i64, vp, vp, vp],
     "lkg_relation_loss_bwd_f32": [i64, i32, i32, vp, i64, i64, vp, i64, vp, f32, vp, vp, i64, vp, i64, vp, i64, vp],
-}
-# the sixth table: include/literalkg_hip_gemm_ordered.h (the ordered split-K GEMM), mirrored the same way
-ORDERED_GEMM_PROTOTYPES = {
+    # the ordered split-K GEMM
     "lkg_gemm_ordered_splits": [i32, i32, i64, i64, i64],
     "lkg_gemm_ordered_partition": [i64, i32, vp],
     "lkg_gemm_ordered_workspace": [i64, i64, i64, i32],
     "lkg_gemm_ordered_f32": [i32, i32, i64, i64, i64, i32, f32, vp, i64, vp, i64, f32, vp, i64, vp, vp, i64, vp],
-}
-# the seventh table: include/literalkg_hip_neighbors.h (neighbour sampling for the batch-pruned step), mirrored the same way
-NEIGHBOR_PROTOTYPES = {
+    # neighbour sampling for the batch-pruned step
     "lkg_csr_sample_rows": [i64, vp, vp, vp, vp, i32, u64, u64, i32, vp, vp, vp, vp],
-}
-# the eighth table: include/literalkg_hip_pair_accept.h (threshold retrieval under the MLP pair head), mirrored the same way
-_PAIR_ACCEPT_HEAD = [i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp]   # .. splits, counts
-PAIR_ACCEPT_PROTOTYPES = {
+    # threshold retrieval under the MLP pair head
     "lkg_pair_mlp_accept_count_f32": _PAIR_ACCEPT_HEAD + [vp],
     "lkg_pair_mlp_accept_append_f32": _PAIR_ACCEPT_HEAD + [i64, vp, vp, vp, vp, vp],
     "lkg_pair_mlp_accept_emit_f32": _PAIR_ACCEPT_HEAD + [vp, vp, vp, vp, vp, vp, vp],
-}
-# the ninth table: include/literalkg_hip_lists.h (scores and ranks against per-query candidate lists), mirrored the same way
-LIST_PROTOTYPES = {
+    # scores and ranks against per-query candidate lists
     "lkg_list_scores_f32": [i64, i64, i64, i32, vp, i64, vp, vp, i64, vp, vp, i64, i32, vp, i64, vp],
     "lkg_list_count_f32": [i64, i64, i64, i32, vp, i64, vp, i64, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
 }
@@ -187,7 +171,8 @@ _RESTYPE = {"lkg_last_error": C.c_char_p, "lkg_csr_build_device_workspace": C.c_
             "lkg_csr_transpose_device_workspace": C.c_int64, "lkg_binary_curve_workspace": C.c_int64,
             "lkg_threshold_fit_workspace": C.c_int64, "lkg_accept_order_workspace": C.c_int64,
             "lkg_gemm_ordered_splits": C.c_int32, "lkg_gemm_ordered_partition": C.c_int64,
-            "lkg_gemm_ordered_workspace": C.c_int64}
+            "lkg_gemm_ordered_workspace": C.c_int64, "lkg_topk_splits": C.c_int32, "lkg_pair_mlp_splits": C.c_int32,
+            "lkg_softmax_all_splits": C.c_int32}
 
 
 class LkgError(RuntimeError):
@@ -209,10 +194,7 @@ def load():
             "`python -c 'import __graft_entry__ as g; g.build()'` (or `python -m literalkg_amd.build`). "
             "literalkg_amd has no CPU fallback.")
     lib = C.CDLL(_LIB_PATH)
-    for name, argtypes in list(PROTOTYPES.items()) + list(EXTRA_PROTOTYPES.items()) + list(TRAIN_PROTOTYPES.items()) + \
-            list(SAMPLE_PROTOTYPES.items()) + list(RELATION_TRAIN_PROTOTYPES.items()) + \
-            list(ORDERED_GEMM_PROTOTYPES.items()) + list(NEIGHBOR_PROTOTYPES.items()) + \
-            list(PAIR_ACCEPT_PROTOTYPES.items()) + list(LIST_PROTOTYPES.items()):
+    for name, argtypes in PROTOTYPES.items():
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
         fn.argtypes = argtypes
         fn.restype = _RESTYPE.get(name, C.c_int)

@@ -23,10 +23,7 @@ FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17"]
 
 def _headers():
     return [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith(".h")] + \
-           [os.path.join(HERE, "..", "include", h) for h in ("literalkg_hip.h", "literalkg_hip_ext.h", "literalkg_hip_train.h",
-                                                                "literalkg_hip_sample.h", "literalkg_hip_relation_train.h",
-                                                                "literalkg_hip_gemm_ordered.h", "literalkg_hip_neighbors.h",
-                                                                "literalkg_hip_pair_accept.h", "literalkg_hip_lists.h")]
+           [os.path.join(HERE, "..", "include", "literalkg_hip.h")]
 
 
 TAG_FILE = os.path.join(HERE, "lib", "flags.tag")

@@ -1,5 +1,5 @@
 // Ordered split-K fp32 GEMM: long reductions into small outputs, spread over the chip WITHOUT atomics, bit for bit repeatable
-// (include/literalkg_hip_gemm_ordered.h states the contract).
+// (include/literalkg_hip.h states the contract).
 //
 //   C[m,n] = alpha * sum_k opA(A)[m,k] * opB(B)[k,n] + beta * C[m,n] (+ bias[n])
 //
@@ -20,7 +20,6 @@
 #include <type_traits>
 
 #include "lkg_common.h"
-#include "../../include/literalkg_hip_gemm_ordered.h"
 
 namespace {
 

@@ -75,7 +75,7 @@ __device__ __forceinline__ int known_entry_of_raw(const int *__restrict__ eptr, 
     return lo;
 }
 
-// splitmix64's finaliser: the samplers' counter-based streams (include/literalkg_hip_sample.h)
+// splitmix64's finaliser: the samplers' counter-based streams (include/literalkg_hip.h)
 __device__ __forceinline__ unsigned long long mix64(unsigned long long z) {
     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
     z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;

@@ -27,8 +27,6 @@
 // every list is empty and yptr is never read.
 #include "lkg_all_entity_common.h"
 
-#include "../../include/literalkg_hip_ext.h"
-
 #pragma clang fp contract(off)
 
 namespace {

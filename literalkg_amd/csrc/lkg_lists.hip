@@ -23,8 +23,6 @@
 #include "lkg_rank_common.h"
 #include "lkg_known.h"
 
-#include "../../include/literalkg_hip_lists.h"
-
 namespace {
 
 constexpr int LS_THREADS = 256;

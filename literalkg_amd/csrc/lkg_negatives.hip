@@ -1,4 +1,4 @@
-// Negative sampling for given positive triples (include/literalkg_hip_sample.h; literalkg_amd/negatives.py): the draw itself,
+// Negative sampling for given positive triples (include/literalkg_hip.h; literalkg_amd/negatives.py): the draw itself,
 // the per-relation cardinalities its Bernoulli side choice needs, and the per-triple answer counts of the subsampling
 // weights.  Every structure is the known triples of lkg_known.h: rows = heads with their tails (the tail side) and rows =
 // tails with their heads (the head side).
@@ -6,7 +6,6 @@
 
 #include "lkg_common.h"
 #include "lkg_known.h"
-#include "../../include/literalkg_hip_sample.h"
 
 namespace {
 

@@ -1,4 +1,4 @@
-// Neighbour sampling for the batch-pruned step (include/literalkg_hip_neighbors.h states the contract; pruned.py calls it
+// Neighbour sampling for the batch-pruned step (include/literalkg_hip.h states the contract; pruned.py calls it
 // in place of lkg_csr_extract_rows): a selected row keeps at most `fanout` of its stored entries, the ones with the smallest
 // (value(j), j) of a counter-based hash of (seed, draw, row id, position).
 //
@@ -14,7 +14,6 @@
 // LDS atomics only; nothing in global memory is added to, and there is no workspace.
 #include "lkg_common.h"
 #include "lkg_known.h"
-#include "../../include/literalkg_hip_neighbors.h"
 
 namespace {
 

@@ -25,8 +25,6 @@
 // Floating-point contraction is off in this file: every rounding is one the references count.
 #include "lkg_common.h"
 
-#include "../../include/literalkg_hip_train.h"
-
 #pragma clang fp contract(off)
 
 namespace {

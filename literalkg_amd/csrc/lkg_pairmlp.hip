@@ -26,7 +26,6 @@
 // every tile, so a push always lands.
 #include "lkg_rank_common.h"
 #include "lkg_topk_common.h"
-#include "../../include/literalkg_hip_pair_accept.h"
 
 namespace {
 
@@ -451,7 +450,7 @@ __global__ __launch_bounds__(PM_THREADS) void pair_mlp_pairs_kernel(
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// Threshold retrieval under the head (predict_accepted_mlp, count_accepted_mlp; include/literalkg_hip_pair_accept.h):
+// Threshold retrieval under the head (predict_accepted_mlp, count_accepted_mlp; include/literalkg_hip.h):
 // the count kernel's loop with ONE compare per logit, z > thr[row], and the filter lookup only on a pass.  Three modes
 // share every instruction up to the decision:
 //   PM_ACC_COUNT   the pass is added to the row's LDS counter; one integer global add per row and workgroup.

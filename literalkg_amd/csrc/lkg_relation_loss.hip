@@ -30,8 +30,6 @@
 #include "lkg_common.h"
 #include "lkg_known.h"
 
-#include "../../include/literalkg_hip_relation_train.h"
-
 #pragma clang fp contract(off)
 
 namespace {

@@ -1,4 +1,4 @@
-"""Ordered split-K GEMM (include/literalkg_hip_gemm_ordered.h, lkg_gemm_ordered.hip): a product with a small output and a
+"""Ordered split-K GEMM (include/literalkg_hip.h, lkg_gemm_ordered.hip): a product with a small output and a
 long reduction, spread over the chip in k-splits whose partial outputs are added in a fixed order -- no float atomics, so
 for given arguments (``splits`` among them) the result repeats bit for bit.
 

@@ -1,4 +1,4 @@
-"""Negatives for GIVEN positive triples, drawn on the device (lkg_negatives.hip; include/literalkg_hip_sample.h): either
+"""Negatives for GIVEN positive triples, drawn on the device (lkg_negatives.hip; include/literalkg_hip.h): either
 side corrupted ('tail', 'head', 'both' by a fair coin per triple, 'bernoulli' by TransH's tph / (tph + hpt) per relation),
 false negatives filtered against every known triple of the corrupted side, candidates from all entities or from a pool, and
 the subsampling weights RotatE and DGL-KE pair with the self-adversarial loss.  It is the sampling half of

@@ -17,7 +17,7 @@ Index bookkeeping (unique / searchsorted / cumsum over a few thousand ids) uses 
 Neighbour sampling (opt-in on top: ``model.neighbor_fanout = f``, training mode only).  Where the frontier explodes -- a hub
 row pulls its whole neighbourhood in at every level -- a row may aggregate at most f of its stored entries per step:
 ``lkg_csr_sample_rows`` stands in for ``lkg_csr_extract_rows`` at every level.  The draw is counter-based and stated exactly
-(include/literalkg_hip_neighbors.h): a row's sample depends on (seed, draw, row id, the row's entries) alone, the same at
+(include/literalkg_hip.h): a row's sample depends on (seed, draw, row id, the row's entries) alone, the same at
 every level, so a sampled step is the EXACT step of the matrix ``sample_neighbors(graph, val, f, seed, draw)``.
 """
 from __future__ import annotations
@@ -72,7 +72,7 @@ def sample_rows(graph: KGStructure, val: torch.Tensor, rows: torch.Tensor, fanou
                 rescale: bool = True):
     """At most ``fanout`` stored entries of every row of ``rows`` (sorted int64 ids) as a compact CSR
     (out_rowptr, out_col, out_val), out_col holding the original ids: lkg_csr_sample_rows, whose header
-    (include/literalkg_hip_neighbors.h) states the draw.  A row's sample depends on (seed, draw, its id, its entries) alone.
+    (include/literalkg_hip.h) states the draw.  A row's sample depends on (seed, draw, its id, its entries) alone.
     One host read: the number of kept entries, as the exact extraction does."""
     fanout = checked_fanout(fanout)
     ops._need_gpu(rows, val)

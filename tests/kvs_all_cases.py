@@ -2,7 +2,7 @@
 literalkg_amd/kvs_all.py), shared by test_kvs_all_host.py (on the CPU: the checks accept a float32 restatement of the
 kernel's algorithm and reject planted faults), test_kvs_all_gpu.py and test_kvs_all_surface_gpu.py.
 
-Contract (include/literalkg_hip_ext.h): s_ic = |p_c|^2 - 2 q_i.p_c (dot: -2 q_i.p_c), z_ic = -scale beta s_ic + bias_i with
+Contract (include/literalkg_hip.h): s_ic = |p_c|^2 - 2 q_i.p_c (dot: -2 q_i.p_c), z_ic = -scale beta s_ic + bias_i with
 beta = 1 (distance) or 1/2 (dot), L_i = sum_c softplus(z_ic) - y'_ic z_ic, y' = (1 - eps) y + eps / n;
 V_ic = scale beta g_i (sigma(z_ic) - y'_ic), dQ = 2 V P, dP = 2 V^T Q - 2 diag(colsum V) P (the second term with distance
 only), dbias = rowsum(V) / (scale beta) = g_i sum_c (sigma - y').  bias is an input of its own: dQ holds no term of it.

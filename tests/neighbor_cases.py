@@ -1,5 +1,5 @@
 """Reference, graph and checker shared by test_neighbors_host.py (numpy alone, planted faults) and test_neighbors_gpu.py
-(lkg_csr_sample_rows on the device, through the SAME checker): the neighbour sample of include/literalkg_hip_neighbors.h.
+(lkg_csr_sample_rows on the device, through the SAME checker): the neighbour sample of include/literalkg_hip.h.
 
 The draw, in numpy uint64 (arithmetic mod 2^64), for row i with d stored entries and fanout f:
     d <= f   every entry kept, col and val untouched

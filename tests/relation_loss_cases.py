@@ -2,7 +2,7 @@
 literalkg_amd/relation_loss.py), shared by test_relation_loss_host.py (on the CPU: the checks accept a float32 restatement
 of the kernels' steps and reject planted faults), test_relation_loss_gpu.py and test_relation_loss_model_gpu.py.
 
-Contract (include/literalkg_hip_relation_train.h): P pairs, R relations, blocks of D columns.  A slab u3[P, R, D] holds
+Contract (include/literalkg_hip.h): P pairs, R relations, blocks of D columns.  A slab u3[P, R, D] holds
 u_ij = d_i W_j (slab mode) or d_i for every j (shared mode); s_ij = sum_c (u_ijc + e_jc)^2, z_ij = -scale s_ij, a dropped
 relation (mask[i, j]; never the truth) has z_ij = -inf, loss_i = logsumexp_j z_ij - z_i,t_i.  Gradient: c_ij =
 -2 scale g_i (softmax_ij - [j == t_i]), G_ij = c_ij (u_ij + e_j); shared mode gd_i = sum_j G_ij; the whole op

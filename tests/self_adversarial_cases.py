@@ -3,7 +3,7 @@
 float32 restatement of the kernel's algorithm and reject planted faults), test_self_adversarial_gpu.py and
 test_self_adversarial_model_gpu.py.
 
-Contract (include/literalkg_hip_train.h): G groups of an anchor row q_g, a positive row p_g and K negative rows n_gj
+Contract (include/literalkg_hip.h): G groups of an anchor row q_g, a positive row p_g and K negative rows n_gj
 (row g K + j of n); z+ = scale (margin - ||q - p||^2), z_j = scale (margin - ||q - n_j||^2) (dot: scale (margin + q.x));
 w_j = softmax_j(temperature z_j), constants; L_g = softplus(-z+) + sum_j w_j softplus(z_j).  Gradient: a_0 = -g sigma(-z+),
 a_j = g w_j sigma(z_j), c_x = cs a_x with cs = 2 scale (dot: scale); distance: dp = c_0 (q - p), dn_j = c_j (q - n_j),

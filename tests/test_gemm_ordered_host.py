@@ -1,11 +1,10 @@
-"""CPU tier of the ordered split-K GEMM (literalkg_amd/gemm_ordered.py, include/literalkg_hip_gemm_ordered.h; the device
-tier is test_gemm_ordered_gpu.py): the header and its ctypes table mirror each other, the partition tiles [0, k) as the
+"""CPU tier of the ordered split-K GEMM (literalkg_amd/gemm_ordered.py, include/literalkg_hip.h; the device
+tier is test_gemm_ordered_gpu.py): the entry points are declared and bound, the partition tiles [0, k) as the
 header states it, the default split count is a pure bounded function, product_route() is a thread-local stack, and the
 argument errors that need no device."""
 import importlib
 import math
 import os
-import re
 import threading
 
 import pytest
@@ -13,7 +12,6 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ["lkg_gemm_ordered_f32", "lkg_gemm_ordered_partition", "lkg_gemm_ordered_splits", "lkg_gemm_ordered_workspace"]
-CTYPE_OF = {"int64_t": "c_long", "int32_t": "c_int", "float": "c_float", "double": "c_double"}
 KS = (0, 1, 15, 16, 17, 4096, 4097, 76800)
 SPLITS = (1, 2, 3, 7, 256)
 
@@ -25,27 +23,12 @@ def GO():
     return importlib.import_module("literalkg_amd.gemm_ordered")      # (the package attribute of that name is the function)
 
 
-def test_prototypes_mirror_the_header_and_the_library_exports_them(GO):
+def test_the_entry_points_are_declared_and_bound_and_the_package_exports_the_api(GO):
     from literalkg_amd import _native, build
+    from wide_cases import prototypes
     assert "lkg_gemm_ordered.hip" in build.SOURCES
     assert os.path.exists(os.path.join(ROOT, "literalkg_amd", "csrc", "lkg_gemm_ordered.hip"))
-    assert any(os.path.basename(h) == "literalkg_hip_gemm_ordered.h" and os.path.exists(h) for h in build._headers())
-    text = open(os.path.join(ROOT, "include", "literalkg_hip_gemm_ordered.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    names = sorted(set(re.findall(r"\b(lkg_[a-z0-9_]+)\s*\(", text)))
-    assert sorted(_native.ORDERED_GEMM_PROTOTYPES) == names == NAMES
-    others = set(_native.PROTOTYPES) | set(_native.EXTRA_PROTOTYPES) | set(_native.TRAIN_PROTOTYPES) | \
-        set(_native.SAMPLE_PROTOTYPES) | set(_native.RELATION_TRAIN_PROTOTYPES)
-    assert not set(names) & others
-    lib = _native.load()
-    for name in names:
-        fn = getattr(lib, name)                                       # exported
-        assert list(fn.argtypes) == list(_native.ORDERED_GEMM_PROTOTYPES[name])
-        ret, decl = re.search(r"\b(int|int32_t|int64_t)\s+" + name + r"\s*\(([^)]*)\)", text).groups()
-        want = ["c_void_p" if "*" in arg else CTYPE_OF[arg.strip().replace("const ", "").split()[0]] for arg in decl.split(",")]
-        got = [t.__name__ for t in _native.ORDERED_GEMM_PROTOTYPES[name]]
-        assert got == want, (name, got, want)                         # argument by argument, by C type
-        assert fn.restype.__name__ == {"int": "c_int", "int32_t": "c_int", "int64_t": "c_long"}[ret], name
+    assert set(NAMES) <= set(_native.PROTOTYPES) and set(NAMES) <= set(prototypes())
     import literalkg_amd as L
     for name in ("gemm_ordered", "gemm_ordered_splits", "matmul_ordered", "product_route", "current_route"):
         assert name in L.__all__ and getattr(L, name) is getattr(GO, name)

@@ -9,7 +9,8 @@ output that is deterministic, by same_bits against the plain run.
      with a correct twin
   b. the query side through the public functions and the ops wrappers
   c. the training side: the bodies of the existing direct-drive tests, called with explicit arguments
-  d. the ledger: which C entry point was launched under which perturbation (REQUIRED / HOST_ONLY / NOT_REACHED)
+  d. the ledger: which C entry point was launched under which perturbation (REQUIRED / HOST_ONLY / NOT_REACHED /
+     ELSEWHERE: the case is in the family's own module)
 
 Which shape enters which branch (from the kernels' dispatch code):
 
@@ -225,6 +226,7 @@ HOST_ONLY = {
     "lkg_binary_curve_workspace", "lkg_threshold_fit_workspace", "lkg_accept_order_workspace",
     "lkg_topk_splits", "lkg_pair_mlp_splits", "lkg_softmax_all_splits",
     "lkg_gemm_longk_ok", "lkg_gemm_smallm_ok", "lkg_gemm_skinny_ok", "lkg_narrow_layer_bwd_ok", "lkg_gemm_f32_engine",
+    "lkg_gemm_ordered_splits", "lkg_gemm_ordered_partition", "lkg_gemm_ordered_workspace",
 }
 # takes a stream, not launched by any case of this module: name -> why
 NOT_REACHED = {
@@ -260,11 +262,30 @@ TRAINING_SIDE = {
 }
 # launched under every perturbation by the cases of this module (test_ledger asserts it)
 REQUIRED = (QUERY_SIDE | TRAINING_SIDE) - set(NOT_REACHED)
+# takes a stream; its poison and side-stream case lives in its family's own module: name -> "file::test"
+# (test_invariance_host.py holds every named test to it: it exists, enters both perturbations and reaches the caller)
+_KVS_ALL = "test_kvs_all_surface_gpu.py::test_entry_points_keep_their_bits_under_poison_and_on_a_side_stream"
+_NSSA = "test_self_adversarial_gpu.py::test_entry_points_keep_their_bits_under_poison_and_on_a_side_stream"
+_NEGATIVES = "test_negatives_gpu.py::test_poisoned_scratch_and_a_side_stream_give_the_same_bits"
+_RELATION_LOSS = "test_relation_loss_gpu.py::test_the_op_keeps_its_bits_under_poison_and_on_a_side_stream"
+ELSEWHERE = {
+    "lkg_sigmoid_all_partial_f32": _KVS_ALL, "lkg_sigmoid_all_finish_f32": _KVS_ALL, "lkg_sigmoid_all_weights_f32": _KVS_ALL,
+    "lkg_nssa_fwd_f32": _NSSA, "lkg_nssa_bwd_f32": _NSSA,
+    "lkg_sample_negatives": _NEGATIVES, "lkg_relation_cardinality": _NEGATIVES, "lkg_answer_counts": _NEGATIVES,
+    "lkg_relation_loss_fwd_f32": _RELATION_LOSS, "lkg_relation_loss_bwd_f32": _RELATION_LOSS,
+    "lkg_gemm_ordered_f32": "test_gemm_ordered_gpu.py::test_runs_poison_and_a_side_stream_change_no_bit",
+    "lkg_csr_sample_rows": "test_neighbors_gpu.py::test_a_rows_sample_depends_on_the_row_alone",
+    "lkg_pair_mlp_accept_count_f32": "test_pair_accepted_gpu.py::test_invariance",
+    "lkg_pair_mlp_accept_append_f32": "test_pair_accepted_gpu.py::test_invariance",
+    "lkg_pair_mlp_accept_emit_f32": "test_pair_accepted_gpu.py::test_invariance",
+    "lkg_list_scores_f32": "test_lists_gpu.py::test_invariance", "lkg_list_count_f32": "test_lists_gpu.py::test_invariance",
+}
 
 
 def check_ledger_partition(prototypes):
     names = set(prototypes)
-    sets = {"REQUIRED": set(REQUIRED), "HOST_ONLY": set(HOST_ONLY), "NOT_REACHED": set(NOT_REACHED)}
+    sets = {"REQUIRED": set(REQUIRED), "HOST_ONLY": set(HOST_ONLY), "NOT_REACHED": set(NOT_REACHED),
+            "ELSEWHERE": set(ELSEWHERE)}
     for a in sets:
         assert sets[a] <= names, (a, sorted(sets[a] - names))
         for b in sets:
@@ -994,8 +1015,8 @@ def test_training_side_body(bodies, name):
 
 # ----------------------------------------------------------------------------- d. the ledger
 def test_ledger(N):
-    """Every entry point is classified, and every one that takes a stream (NOT_REACHED aside) was launched under all three
-    perturbations by the cases above: run the module whole."""
+    """Every entry point is classified, and every one that takes a stream (NOT_REACHED aside, and ELSEWHERE, whose cases
+    other modules hold) was launched under all three perturbations by the cases above: run the module whole."""
     check_ledger_partition(N.PROTOTYPES)
     assert len(NOT_REACHED) <= 8 and not set(NOT_REACHED) & QUERY_SIDE, sorted(NOT_REACHED)
     ran = set(RAN)

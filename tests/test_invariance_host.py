@@ -175,9 +175,78 @@ def test_side_stream_delays_device_allocations_only():
 
 # ----------------------------------------------------------------------------- the ledger
 def test_the_ledger_partitions_the_entry_points():
-    """REQUIRED, HOST_ONLY and NOT_REACHED of test_invariance_gpu.py hold every entry point of _native.PROTOTYPES exactly
-    once: a new entry point must be classified before the suite passes."""
+    """REQUIRED, HOST_ONLY, NOT_REACHED and ELSEWHERE of test_invariance_gpu.py hold every entry point of
+    _native.PROTOTYPES -- the whole ABI -- exactly once: a new entry point must be classified before the suite passes."""
     import test_invariance_gpu as G
     from literalkg_amd import _native
     G.check_ledger_partition(_native.PROTOTYPES)
     assert len(G.NOT_REACHED) <= 8 and not set(G.NOT_REACHED) & G.QUERY_SIDE
+    assert len(_native.PROTOTYPES) >= 129 and len(G.ELSEWHERE) == 17
+
+
+def _definitions(path):
+    """(source, {name: [node]}) of every function and class a file defines, at any depth"""
+    with open(path) as f:
+        src = f.read()
+    found = {}
+    for node in ast.walk(ast.parse(src)):
+        if isinstance(node, (ast.FunctionDef, ast.ClassDef)):
+            found.setdefault(node.name, []).append(node)
+    return src, found
+
+
+def _names(node):
+    return {n.id for n in ast.walk(node) if isinstance(n, ast.Name)} | \
+           {n.attr for n in ast.walk(node) if isinstance(n, ast.Attribute)}
+
+
+# an autograd Function's passes are entered through its class (X.apply), never by these names alone
+NOT_FOLLOWED = {"forward", "backward", "apply"}
+
+
+def _reached_literals(test_node, local, package):
+    """every string constant of the test, of the functions of its own module and of the package's functions and classes
+    that it reaches by name, transitively"""
+    seen, todo, strings = set(), [test_node], set()
+    while todo:
+        node = todo.pop()
+        if id(node) in seen:
+            continue
+        seen.add(id(node))
+        strings |= {c.value for c in ast.walk(node) if isinstance(c, ast.Constant) and isinstance(c.value, str)}
+        for name in _names(node) - NOT_FOLLOWED:
+            todo += local.get(name, []) + package.get(name, [])
+    return strings
+
+
+def test_every_entry_point_listed_elsewhere_has_its_case_there():
+    """ELSEWHERE names, per entry point, the test of another module that runs it under poisoned scratch and on a side
+    stream.  Each such test exists, enters poisoned( and side_stream( -- itself or through its module's perturbation(
+    helper -- and reaches, by the names it calls, a function of the package that passes the entry point's name to the
+    library."""
+    import test_invariance_gpu as G
+    package = {}
+    for path in package_sources():
+        for name, nodes in _definitions(path)[1].items():
+            package.setdefault(name, []).extend(nodes)
+    here = os.path.dirname(os.path.abspath(__file__))
+    modules = {}
+    for entry, where in G.ELSEWHERE.items():
+        file, test = where.split("::")
+        path = os.path.join(here, file)
+        assert os.path.exists(path), (entry, file)
+        if file not in modules:
+            modules[file] = _definitions(path)
+        src, local = modules[file]
+        assert len(local.get(test, [])) == 1, f"{entry}: {file} does not define {test} (once)"
+        node = local[test][0]
+        assert "pytest.mark.gpu" in src
+        text = ast.get_source_segment(src, node)
+        if "perturbation(" in text:
+            text += "".join(ast.get_source_segment(src, h) for h in local["perturbation"])
+        assert "poisoned(" in text and "side_stream(" in text, f"{entry}: {where} does not enter both perturbations"
+        assert entry in _reached_literals(node, local, package), f"{entry}: {where} reaches no caller of it"
+    # the check can fail: a test that calls nothing of the family reaches no caller
+    src, local = modules["test_neighbors_gpu.py"]
+    assert "lkg_csr_sample_rows" not in _reached_literals(local["test_draw_and_seed_change_the_hubs_sample"][0], {}, package)
+    assert "lkg_list_count_f32" not in _reached_literals(local["test_a_rows_sample_depends_on_the_row_alone"][0], local, package)

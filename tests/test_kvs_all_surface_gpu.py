@@ -1,5 +1,5 @@
 """GPU: what the closed lists of test_invariance_gpu.py and tests/autograd_cases.py give the other entry points and
-Functions, written out for the KvsAll ones (their entry points live in _native.EXTRA_PROTOTYPES, their Function in
+Functions, written out for the KvsAll ones (their entry points are in ELSEWHERE of that ledger, their Function in
 literalkg_amd/kvs_all.py): every new entry point gives the same bits under the perturbations of tests/invariance.py
 (poisoned scratch of either byte, a side stream behind the host with poisoned scratch), and the Function under every
 non-empty subset of {q, p, bias} requiring grad gives the needed gradients with the bits of the all-trainable run and None

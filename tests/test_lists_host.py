@@ -1,9 +1,8 @@
 """CPU tier of ranking against per-query candidate lists (literalkg_amd/lists.py: score_lists, rank_in_lists,
-evaluate_list_ranking; include/literalkg_hip_lists.h; the device tier is test_lists_gpu.py): the new header, its ctypes
-table and the built library name the same entry points; the reference of list_cases.py is what it says on a hand-written
+evaluate_list_ranking; include/literalkg_hip.h; the device tier is test_lists_gpu.py): the entry points are declared,
+bound and exported; the reference of list_cases.py is what it says on a hand-written
 case and its comparator rejects every planted fault; every argument error is raised before any device work."""
 import os
-import re
 from types import SimpleNamespace
 
 import pytest
@@ -12,35 +11,18 @@ import torch
 import list_cases as LC
 from test_topk_gpu import StandIn
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CTYPE_OF = {"int64_t": "c_long", "int32_t": "c_int", "uint64_t": "c_ulong", "float": "c_float"}
 NAMES = ["lkg_list_count_f32", "lkg_list_scores_f32"]
 NAN = float("nan")
 
 
-# ----------------------------------------------------------------------------- the header, the table, the library
-def test_prototypes_mirror_the_header_and_the_library_exports_them():
+# ----------------------------------------------------------------------------- the entry points and the package
+def test_the_entry_points_are_declared_and_bound_and_the_package_exports_the_api():
     import __graft_entry__ as ge
     ge.build()
     from literalkg_amd import _native, build
-    assert any(os.path.basename(h) == "literalkg_hip_lists.h" and os.path.exists(h) for h in build._headers())
-    assert "lkg_lists.hip" in build.SOURCES
-    text = open(os.path.join(ROOT, "include", "literalkg_hip_lists.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    names = sorted(set(re.findall(r"\b(lkg_[a-z0-9_]+)\s*\(", text)))
-    assert sorted(_native.LIST_PROTOTYPES) == names == NAMES
-    others = set(_native.PROTOTYPES) | set(_native.EXTRA_PROTOTYPES) | set(_native.TRAIN_PROTOTYPES) | \
-        set(_native.SAMPLE_PROTOTYPES) | set(_native.RELATION_TRAIN_PROTOTYPES) | set(_native.ORDERED_GEMM_PROTOTYPES) | \
-        set(_native.NEIGHBOR_PROTOTYPES) | set(_native.PAIR_ACCEPT_PROTOTYPES)
-    assert not set(names) & others
-    lib = _native.load()
-    for name in names:
-        fn = getattr(lib, name)                                              # exported
-        assert list(fn.argtypes) == list(_native.LIST_PROTOTYPES[name])
-        ret, decl = re.search(r"\b(int)\s+" + name + r"\s*\(([^)]*)\)", text).groups()
-        want = ["c_void_p" if "*" in arg else CTYPE_OF[arg.strip().replace("const ", "").split()[0]]
-                for arg in decl.split(",")]
-        assert [t.__name__ for t in fn.argtypes] == want and fn.restype.__name__ == "c_int", name
+    from wide_cases import prototypes
+    assert "lkg_lists.hip" in build.SOURCES and os.path.exists(os.path.join(build.CSRC, "lkg_lists.hip"))
+    assert set(NAMES) <= set(_native.PROTOTYPES) and set(NAMES) <= set(prototypes())
     import literalkg_amd as L
     from literalkg_amd import lists
     for name in ("ListRanks", "score_lists", "rank_in_lists", "evaluate_list_ranking"):

@@ -34,6 +34,35 @@ def test_library_exports_every_declared_symbol(native):
     assert lib.lkg_version() >= 100
 
 
+def declared_return_types():
+    """{entry point: the C type in front of its name} of every declaration in include/literalkg_hip.h"""
+    text = open(os.path.join(ROOT, "include", "literalkg_hip.h")).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    return {m.group(2): re.sub(r"\s+", " ", m.group(1)).replace(" *", "*").strip()
+            for m in re.finditer(r"^((?:const\s+)?\w+\s*\*?)\s*\b(lkg_\w+)\s*\([^;{()]*\)\s*;", text, re.M)}
+
+
+def test_the_table_mirrors_the_header_argument_by_argument(native):
+    """One header, one table: include/ holds literalkg_hip.h alone, and every declaration in it is exported, bound with the
+    row of _native.PROTOTYPES, and that row is the declaration's, argument by argument, by C type -- a pointer is c_void_p
+    (`const char *`: c_char_p), a scalar the ctypes type of its width -- and so is the return type."""
+    import ctypes as C
+    from wide_cases import prototypes
+    assert sorted(os.listdir(os.path.join(ROOT, "include"))) == ["literalkg_hip.h"]
+    scalar = {"int64_t": C.c_int64, "int32_t": C.c_int32, "uint64_t": C.c_uint64, "float": C.c_float, "double": C.c_double}
+    returns = {**scalar, "int": C.c_int, "const char*": C.c_char_p}
+    lib = native.load()
+    declared, restypes = prototypes(), declared_return_types()
+    assert sorted(declared) == sorted(restypes) == sorted(native.PROTOTYPES) == header_symbols() and len(declared) >= 129
+    for name, params in declared.items():
+        fn = getattr(lib, name)
+        assert list(fn.argtypes) == list(native.PROTOTYPES[name]), name
+        want = [(C.c_char_p if p.ctype.replace(" ", "") == "constchar*" else C.c_void_p) if p.pointer else scalar[p.ctype]
+                for p in params]
+        assert list(native.PROTOTYPES[name]) == want, (name, [(p.name, p.ctype) for p in params])
+        assert fn.restype is returns[restypes[name]], (name, restypes[name], fn.restype)
+
+
 def test_error_convention(native):
     h = np.array([0, 5], np.int64)
     t = np.array([1, 1], np.int64)

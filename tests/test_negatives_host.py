@@ -126,35 +126,18 @@ def test_the_checks_reject_planted_faults(fault):
         assert C.violations(bad, *C.positives(), C.pools(pool), True, any_relation) == 0
 
 
-# ----------------------------------------------------------------------------- the fourth ABI table
-CTYPE_OF = {"int64_t": "c_long", "int32_t": "c_int", "uint64_t": "c_ulong", "float": "c_float", "double": "c_double"}
+# ----------------------------------------------------------------------------- the entry points and the published constants
+NAMES = ["lkg_answer_counts", "lkg_relation_cardinality", "lkg_sample_negatives"]
 
 
-def test_sample_prototypes_mirror_the_sample_header_and_the_library_exports_them():
+def test_the_three_entry_points_are_declared_and_bound_and_the_header_publishes_the_constants():
     import __graft_entry__ as ge
     ge.build()
     from literalkg_amd import _native, build, negatives
-    assert "lkg_negatives.hip" in build.SOURCES
-    assert any(os.path.basename(h) == "literalkg_hip_sample.h" and os.path.exists(h) for h in build._headers())
-    raw = open(os.path.join(ROOT, "include", "literalkg_hip_sample.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
-    names = sorted(set(re.findall(r"\b(lkg_[a-z0-9_]+)\s*\(", text)))
-    assert sorted(_native.SAMPLE_PROTOTYPES) == names == ["lkg_answer_counts", "lkg_relation_cardinality",
-                                                          "lkg_sample_negatives"]
-    others = set(_native.PROTOTYPES) | set(_native.EXTRA_PROTOTYPES) | set(_native.TRAIN_PROTOTYPES)
-    assert not set(_native.SAMPLE_PROTOTYPES) & others
-    lib = _native.load()
-    for name in names:
-        fn = getattr(lib, name)
-        assert list(fn.argtypes) == list(_native.SAMPLE_PROTOTYPES[name])
-        decl = re.search(r"\bint\s+" + name + r"\s*\(([^)]*)\)", text).group(1)
-        want = []
-        for arg in decl.split(","):
-            arg = arg.strip()
-            want.append("c_void_p" if "*" in arg else CTYPE_OF[arg.replace("const ", "").split()[0]])
-        got = [t.__name__ for t in _native.SAMPLE_PROTOTYPES[name]]
-        assert got == want, (name, got, want)                       # argument by argument, by C type
-    # the published constants
+    from wide_cases import prototypes
+    assert "lkg_negatives.hip" in build.SOURCES and os.path.exists(os.path.join(build.CSRC, "lkg_negatives.hip"))
+    assert set(NAMES) <= set(_native.PROTOTYPES) and set(NAMES) <= set(prototypes())
+    raw = open(os.path.join(ROOT, "include", "literalkg_hip.h")).read()
     assert int(re.search(r"#define LKG_SAMPLE_MAX_TRIES (\d+)", raw).group(1)) == negatives.MAX_TRIES == C.MAX_TRIES == 64
     for i, mode in enumerate(negatives.CORRUPT):
         assert int(re.search(r"#define LKG_CORRUPT_" + mode.upper() + r" (\d+)", raw).group(1)) == i

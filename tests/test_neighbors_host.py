@@ -1,9 +1,8 @@
-"""CPU tier of neighbour sampling (include/literalkg_hip_neighbors.h, literalkg_amd/pruned.py; the device tiers are
-test_neighbors_gpu.py and test_neighbors_model_gpu.py): the header and its ctypes table mirror each other, the reference
+"""CPU tier of neighbour sampling (include/literalkg_hip.h, literalkg_amd/pruned.py; the device tiers are
+test_neighbors_gpu.py and test_neighbors_model_gpu.py): the entry point is declared and bound, the reference
 of neighbor_cases.py is a usable sampler (every entry of a row kept equally often, the rescaled sum unbiased), the numpy
 form agrees with Python integers, and the checker rejects every planted fault."""
 import os
-import re
 
 import numpy as np
 import pytest
@@ -11,28 +10,16 @@ import pytest
 import index_cases as I
 import neighbor_cases as NC
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CTYPE_OF = {"int64_t": "c_long", "int32_t": "c_int", "uint64_t": "c_ulong", "float": "c_float"}
+NAMES = ["lkg_csr_sample_rows"]
 
 
-def test_prototype_mirrors_the_header_and_the_library_exports_it():
+def test_the_entry_point_is_declared_and_bound_and_the_package_exports_the_sampler():
     import __graft_entry__ as ge
     ge.build()
     from literalkg_amd import _native, build
-    assert "lkg_neighbors.hip" in build.SOURCES
-    assert any(os.path.basename(h) == "literalkg_hip_neighbors.h" and os.path.exists(h) for h in build._headers())
-    text = open(os.path.join(ROOT, "include", "literalkg_hip_neighbors.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    names = sorted(set(re.findall(r"\b(lkg_[a-z0-9_]+)\s*\(", text)))
-    assert sorted(_native.NEIGHBOR_PROTOTYPES) == names == ["lkg_csr_sample_rows"]
-    others = set(_native.PROTOTYPES) | set(_native.EXTRA_PROTOTYPES) | set(_native.TRAIN_PROTOTYPES) | \
-        set(_native.SAMPLE_PROTOTYPES) | set(_native.RELATION_TRAIN_PROTOTYPES) | set(_native.ORDERED_GEMM_PROTOTYPES)
-    assert not set(names) & others
-    fn = getattr(_native.load(), "lkg_csr_sample_rows")                  # exported
-    assert list(fn.argtypes) == list(_native.NEIGHBOR_PROTOTYPES["lkg_csr_sample_rows"])
-    ret, decl = re.search(r"\b(int)\s+lkg_csr_sample_rows\s*\(([^)]*)\)", text).groups()
-    want = ["c_void_p" if "*" in arg else CTYPE_OF[arg.strip().replace("const ", "").split()[0]] for arg in decl.split(",")]
-    assert [t.__name__ for t in fn.argtypes] == want and fn.restype.__name__ == "c_int"
+    from wide_cases import prototypes
+    assert "lkg_neighbors.hip" in build.SOURCES and os.path.exists(os.path.join(build.CSRC, "lkg_neighbors.hip"))
+    assert set(NAMES) <= set(_native.PROTOTYPES) and set(NAMES) <= set(prototypes())
     import literalkg_amd as L
     from literalkg_amd import pruned
     assert "sample_neighbors" in L.__all__ and L.sample_neighbors is pruned.sample_neighbors

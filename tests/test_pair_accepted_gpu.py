@@ -1,5 +1,5 @@
 """GPU: threshold retrieval under the MLP pair head (literalkg_amd/pairmlp.py: predict_accepted_mlp, count_accepted_mlp;
-lkg_pairmlp.hip: pair_mlp_accept_kernel; include/literalkg_hip_pair_accept.h) against the references of
+lkg_pairmlp.hip: pair_mlp_accept_kernel; include/literalkg_hip.h) against the references of
 pair_accept_cases.py -- without tolerance: the object is unique.
 
 The op tier runs on small-integer operands, where every logit is an exact integer in float32 and the int64 reference is

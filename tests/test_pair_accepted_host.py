@@ -1,9 +1,8 @@
 """CPU tier of threshold retrieval under the MLP pair head (literalkg_amd/pairmlp.py: predict_accepted_mlp,
-count_accepted_mlp; include/literalkg_hip_pair_accept.h; the device tier is test_pair_accepted_gpu.py): the checker of
-pair_accept_cases.py rejects every planted fault, every argument error is raised before any device work, and the new
-header, its ctypes table and the built library name the same entry points."""
+count_accepted_mlp; include/literalkg_hip.h; the device tier is test_pair_accepted_gpu.py): the checker of
+pair_accept_cases.py rejects every planted fault, every argument error is raised before any device work, and the
+entry points are declared, bound and exported."""
 import os
-import re
 from types import SimpleNamespace
 
 import numpy as np
@@ -13,33 +12,17 @@ import torch
 import pair_accept_cases as PA
 from test_pairmlp_gpu import StandIn, random_head
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CTYPE_OF = {"int64_t": "c_long", "int32_t": "c_int", "uint64_t": "c_ulong", "float": "c_float"}
 NAMES = ["lkg_pair_mlp_accept_append_f32", "lkg_pair_mlp_accept_count_f32", "lkg_pair_mlp_accept_emit_f32"]
 
 
-# ----------------------------------------------------------------------------- the header, the table, the library
-def test_prototypes_mirror_the_header_and_the_library_exports_them():
+# ----------------------------------------------------------------------------- the entry points and the package
+def test_the_entry_points_are_declared_and_bound_and_the_package_exports_the_api():
     import __graft_entry__ as ge
     ge.build()
     from literalkg_amd import _native, build
-    assert any(os.path.basename(h) == "literalkg_hip_pair_accept.h" and os.path.exists(h) for h in build._headers())
-    text = open(os.path.join(ROOT, "include", "literalkg_hip_pair_accept.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    names = sorted(set(re.findall(r"\b(lkg_[a-z0-9_]+)\s*\(", text)))
-    assert sorted(_native.PAIR_ACCEPT_PROTOTYPES) == names == NAMES
-    others = set(_native.PROTOTYPES) | set(_native.EXTRA_PROTOTYPES) | set(_native.TRAIN_PROTOTYPES) | \
-        set(_native.SAMPLE_PROTOTYPES) | set(_native.RELATION_TRAIN_PROTOTYPES) | set(_native.ORDERED_GEMM_PROTOTYPES) | \
-        set(_native.NEIGHBOR_PROTOTYPES)
-    assert not set(names) & others
-    lib = _native.load()
-    for name in names:
-        fn = getattr(lib, name)                                              # exported
-        assert list(fn.argtypes) == list(_native.PAIR_ACCEPT_PROTOTYPES[name])
-        ret, decl = re.search(r"\b(int)\s+" + name + r"\s*\(([^)]*)\)", text).groups()
-        want = ["c_void_p" if "*" in arg else CTYPE_OF[arg.strip().replace("const ", "").split()[0]]
-                for arg in decl.split(",")]
-        assert [t.__name__ for t in fn.argtypes] == want and fn.restype.__name__ == "c_int", name
+    from wide_cases import prototypes
+    assert "lkg_pairmlp.hip" in build.SOURCES and os.path.exists(os.path.join(build.CSRC, "lkg_pairmlp.hip"))
+    assert set(NAMES) <= set(_native.PROTOTYPES) and set(NAMES) <= set(prototypes())
     import literalkg_amd as L
     from literalkg_amd import pairmlp
     for name in ("predict_accepted_mlp", "count_accepted_mlp"):

