@@ -583,7 +583,10 @@ int lkg_gemm_f32(int32_t trans_a, int32_t trans_b, int64_t m, int64_t n, int64_t
  * instruction count on a 16x faster pipe.
  *   a / lda / ka       host arrays of n_panels (1..3) device pointers / row strides / widths: A's K-panels, possibly
  *                      from different arrays (nn.Linear over a concatenated input WITHOUT the concatenation:
- *                      gate.py:23 [x | num | txt], model.py:116 [ego | side]); any alignment, any width;
+ *                      gate.py:23 [x | num | txt], model.py:116 [ego | side]); any alignment, any width -- but a panel
+ *                      must span one 16-byte window, (m - 1) lda[p] + ka[p] >= 4 floats (a single row narrower than 4,
+ *                      two rows of one): the kernel loads whole windows clamped to the panel's last one, and a
+ *                      shorter panel is LKG_ERR_INVALID_ARG before any launch;
  *   a_rowmax           device float[m]: max_k |A[i, k]| over all panels (lkg_row_absmax_f32; accumulate = 1 folds a
  *                      further panel in).  It only has to BOUND the row (a stale larger value costs precision, a
  *                      smaller one overflows fp16): callers cache it for constant panels;

@@ -1104,6 +1104,10 @@ static int tall_call(int64_t m, int32_t n, int32_t n_panels, const float *const 
     bd.interleave = epilogue == EPI_GATE ? 1 : 0;
     for (int p = 0; p < n_panels; ++p) {
         LKG_REQUIRE(ka[p] > 0 && a[p] && lda[p] >= ka[p], "lkg_gemm_tall_f32: bad A panel %d", p);
+        // (the kernel reads A in 16-byte windows clamped to the panel's LAST whole window: a panel that ends before its
+        // fourth float has none, and the clamp would start 4 .. 12 bytes in front of it)
+        LKG_REQUIRE((m - 1) * lda[p] + ka[p] >= 4, "lkg_gemm_tall_f32 / lkg_linear_act_layernorm_fwd_f32: A panel %d spans fewer than 4 floats (%lld rows of %d): "
+                    "it holds no 16-byte window", p, (long long)m, ka[p]);
         g.a[p] = a[p]; g.lda[p] = lda[p]; g.ka[p] = ka[p]; g.ktiles[p] = (ka[p] + TK - 1) / TK;
         bd.k[p] = ka[p];
         for (int gr = 0; gr < n_groups; ++gr) {

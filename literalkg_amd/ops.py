@@ -628,13 +628,28 @@ def gemm_tall(a_panels: Sequence[torch.Tensor], b_blocks: Sequence[Sequence[torc
     """C = sum_p a_panels[p] @ op(B_p) (+ bias) for a tall A (lkg_gemm_tall_f32).  b_blocks[g][p]: block of B for row
     group g (1 group; 2 = the gate's stacked g / z projections with the blend epilogue on gate_x) and panel p; trans_b:
     blocks stored [n, k_p] (nn.Linear weights) else [k_p, n].  keep = (g_out, z_out) for the gate's backward.
-    variant: None = the library's default tiling, or a key of TALL_VARIANTS (tests and tools run them side by side)."""
+    variant: None = the library's default tiling, or a key of TALL_VARIANTS (tests and tools run them side by side).
+    A panel that spans fewer than 4 floats (one row of 1 to 3 columns, two or three rows of one) is widened with zero
+    columns, as is its block of B: the entry point refuses it.  Under the gate epilogue such a panel is a ValueError."""
     if rowmax is None:
         rowmax = rows_absmax(a_panels)          # (before any .contiguous(): the producers' tags live on these objects)
     a_panels = [_f32_rows(a) for a in a_panels]
     m = a_panels[0].shape[0]
     if any(a.shape[0] != m for a in a_panels):
         raise ValueError(f"gemm_tall: the K-panels have {[a.shape[0] for a in a_panels]} rows")
+    # the kernel loads A in 16-byte windows and the entry point refuses a panel that spans fewer than 4 floats (one row of 1
+    # to 3 columns, two or three rows of one): such a panel, and its blocks of B, get zero columns up to 4 -- the same sum
+    short = [p for p, a in enumerate(a_panels) if 0 < (m - 1) * _ld(a) + a.shape[1] < 4]
+    if short:
+        if gate_x is not None:
+            raise ValueError("gemm_tall: the gate epilogue blends its first K-panel as it stands (gate_x is a[0]); a panel "
+                             "that spans fewer than 4 floats cannot be widened under it")
+        a_panels, b_blocks = list(a_panels), [list(grp) for grp in b_blocks]
+        for p in short:
+            k = a_panels[p].shape[1]
+            a_panels[p] = _f32_rows(torch.nn.functional.pad(a_panels[p], (0, 4 - k)))
+            for grp in b_blocks:
+                grp[p] = torch.nn.functional.pad(grp[p], (0, 4 - k) if trans_b else (0, 0, 0, 4 - k))
     if rowmax.numel() != m:
         raise ValueError(f"gemm_tall: {rowmax.numel()} row maxima for {m} rows")
     ks = [a.shape[1] for a in a_panels]
@@ -769,7 +784,7 @@ def edge_softmax(g: KGStructure, ent: torch.Tensor, relemb: torch.Tensor, want_l
     else:
         rp = g.host("rowptr")
         e_lo, e_hi = int(rp[row_lo]), int(rp[row_hi])
-    N.call("lkg_edge_softmax_f32", row_hi - row_lo, row_lo, ent.shape[1], g.rowptr.data_ptr() + 4 * row_lo,
+    N.call("lkg_edge_softmax_f32", row_hi - row_lo, row_lo, ent.shape[1], N.ptr(g.rowptr) + 4 * row_lo,
            N.ptr(g.col), N.ptr(g.eptr), N.ptr(g.rel), N.ptr(g.rel_first), *dup, e_lo, e_hi,
            N.ptr(ent), _ld(ent), N.ptr(relemb), _ld(relemb), N.ptr(val),
            N.ptr(logits), N.ptr(long_rows), 0 if long_rows is None else long_rows.numel(), LONG_ROW_THRESHOLD,

@@ -430,6 +430,10 @@ WAIVED = {
     ("lkg_accept_emit_f32", "out_ids"): (None, "lkg_accept.hip: slot = atomicAdd(cursor + grow, 1)"),
     ("lkg_accept_emit_f32", "out_scores"): (None, "lkg_accept.hip: slot = atomicAdd(cursor + grow, 1)"),
     ("lkg_accept_emit_f32", "out_values"): (None, "lkg_accept.hip: slot = atomicAdd(cursor + grow, 1)"),
+    **{("lkg_pair_mlp_accept_append_f32", out): (None, "lkg_pairmlp.hip: slot = atomicAdd(gcursor, 1ull)")
+       for out in ("out_rows", "out_ids", "out_logits")},
+    **{("lkg_pair_mlp_accept_emit_f32", out): (None, "lkg_pairmlp.hip: slot = atomicAdd(cursor + grow, 1)")
+       for out in ("out_ids", "out_scores", "out_logits")},
 }
 
 # Operands whose rows an id list selects: (entry point, operand) -> the id arguments.  A wide pass of such an operand must
@@ -544,11 +548,10 @@ class Harness:
         return block, offs
 
     @contextlib.contextmanager
-    def running(self, target, twin_pass=None):
-        """one pass: the twin pass (target None) or the pass with `target` wide, compared against `twin_pass`"""
-        import invariance as V
+    def boundary(self, ps, twin_pass):
+        """the C boundary for the length of one pass: _native.ptr records which tensor each address came from, _native.call
+        hands every launch to self._launch, ops._f32_rows records the tall GEMM's panels"""
         torch, N = self.torch, self.N
-        ps = Pass(target)
         real_call, real_ptr = N.call, N.ptr
         self.registry = {}
 
@@ -574,17 +577,25 @@ class Harness:
                 self.registry.setdefault(r.data_ptr(), []).append(r)
             return r
 
+        N.call, N.ptr, ops._f32_rows = call, ptr, f32_rows
+        try:
+            yield
+        finally:
+            N.call, N.ptr, ops._f32_rows = real_call, real_ptr, real_rows
+            self.registry = {}
+
+    @contextlib.contextmanager
+    def running(self, target, twin_pass=None):
+        """one pass: the twin pass (target None) or the pass with `target` wide, compared against `twin_pass`"""
+        import invariance as V
+        torch = self.torch
+        ps = Pass(target)
         torch.cuda.synchronize()
         if target is not None:
             poison(self.store)
         torch.manual_seed(0)
-        N.call, N.ptr, ops._f32_rows = call, ptr, f32_rows
-        try:
-            with V.poisoned(0xFF):
-                yield ps
-        finally:
-            N.call, N.ptr, ops._f32_rows = real_call, real_ptr, real_rows
-            self.registry = {}
+        with self.boundary(ps, twin_pass), V.poisoned(0xFF):
+            yield ps
         torch.cuda.synchronize()
         self.passes += 1
         if target is not None:
